@@ -16,6 +16,12 @@ x 128 replicas over 8 GPUs): by default every rank merges its own 25M x 128 shar
 Timing: W untimed warmup steps, then K steps bracketed by barrier + device sync on both sides; the
 wall time is max over ranks.  The kernel's own average duration comes from HIP events recorded on
 the library's stream around the same K launches (`roofline.achieved`).  rank 0 prints ONE JSON line.
+
+A plain run (`--gpus 1 --steps K --warmup W`) measures the headline alone: it synthesises the PN-Counter
+store and batch, warms up, times the K steps and prints the line.  `--full` adds every other leg (the OR-Set
+batch merge, exchange, wire-format apply, digests, the apply loops and the producer path) and the CPU
+baselines; `--workload` picks one of them and needs `--full` for anything but the headline.
+`--dump-outputs DIR` writes what the headline's timed path left behind (DIR/pnc_*.npy, see dump_pnc).
 """
 from __future__ import annotations
 
@@ -232,13 +238,36 @@ def pnc_shard(shape: str, scaling: str, rank: int, world: int) -> tuple[int, int
     return key0, n, R
 
 
-def bench_pnc(jg, ctx, sync, rank, world, steps, warmup, shape="c2", scaling="weak"):
+DUMP_KEYS = 16384  # sampled rows of --dump-outputs: 2 x 16384 x 64 float64 = 16 MB at C2, 32 MB at C4
+
+
+def dump_pnc(store, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last step.  jg_pnc_merge_batch merges in
+    place, so that is the store: the merged P and N rows (jg_pnc_read_rows) and the counters' values with
+    their overflow flags (jg_pnc_values) of a fixed sample of keys: the first, the last and DUMP_KEYS seeded
+    draws, ascending (`pnc_keys`).  float64 holds them exactly: the synthetic cells are below 2^31 or the
+    ABSENT marker -2^63, a value sums R of them.  At N > 1 every rank writes its shard's sample (`_rank<r>`)."""
+    import numpy as np
+    rng = np.random.default_rng(SEED)
+    keys = np.unique(np.concatenate(([0, store.n_keys - 1], rng.integers(0, store.n_keys, DUMP_KEYS)))).astype(np.uint32)
+    P, N = store.read_rows(keys)
+    val, ovf = store.values(keys)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, a in (("keys", keys), ("P", P), ("N", N), ("values", val), ("overflow", ovf)):
+        np.save(d / f"pnc_{name}{tag}.npy", a.astype(np.float64))
+
+
+def bench_pnc(jg, ctx, sync, rank, world, steps, warmup, shape="c2", scaling="weak", dump=None):
     key0, n_keys, R = pnc_shard(shape, scaling, rank, world)
     store = jg.PNCStore(ctx, n_keys, R, PNC_EB)
     rows = jg.Rows(ctx, n_keys, R, PNC_EB)
     store.synth(SEED + rank)
     rows.synth(SEED + rank, key0=0)  # per-rank seed: every shard holds its own synthetic keys
     wall, ev = timed(ctx, sync, lambda: store.merge_batch(rows, async_=True), steps, warmup)
+    if dump:
+        dump_pnc(store, dump, rank, world)
     store.close()
     rows.close()
     cells = n_keys * R
@@ -905,14 +934,27 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--workload", choices=["all", "pnc", "orset", "pnc-orset", "exchange", "digest", "json", "producer"], default="all")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline (the PN-Counter batch merge): every other leg and the CPU baselines")
+    ap.add_argument("--workload", choices=["all", "pnc", "orset", "pnc-orset", "exchange", "digest", "json", "producer"], default=None,
+                    help="with --full: one leg instead of all of them; without it only pnc (the headline, the default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the headline path's outputs as DIR/pnc_*.npy (float64 sample, dump_pnc)")
     ap.add_argument("--pnc-shape", choices=["auto"] + sorted(PNC_SHAPES), default="auto",
                     help="per-GPU PN-Counter shard: c2 = BASELINE configs[1], c4 = 1/8 of configs[3]; "
                          "auto (default) = c2 on one GPU, c4 on N > 1")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: a fixed shard per GPU; strong: configs[3]'s 200M keys split over N >= 4 GPUs")
     args = ap.parse_args()
+    if args.workload is None:
+        args.workload = "all" if args.full else "pnc"
+    if not args.full and args.workload != "pnc":
+        ap.error(f"--workload {args.workload} needs --full: a plain run measures the headline (pnc) alone")
+    if args.dump_outputs and args.workload not in ("all", "pnc", "pnc-orset"):
+        ap.error("--dump-outputs writes the headline path's outputs: the workload must include pnc")
+    if not args.full:
+        args.no_cpu_baseline = True
 
     world, rank, local = dist_env()
     if args.pnc_shape == "auto":
@@ -921,9 +963,11 @@ def main():
         sys.exit("--scaling strong needs N >= 4: configs[3]'s 200M keys x 128 replicas (A + B = 819.2 GB) do not fit fewer MI355X")
     if world != args.gpus and world > 1:
         print(f"warning: WORLD_SIZE={world} but --gpus {args.gpus}", file=sys.stderr)
-    if world > 1 or args.workload in ("all", "exchange", "digest", "json"):
+    if world > 1 or not args.full or args.workload in ("all", "exchange", "digest", "json"):
         # torch (device buffers + RCCL) is loaded before libjanusgpu so both bind ONE HIP runtime
-        # instance (torch's libraries also name the runtime by an unversioned soname)
+        # instance (torch's libraries also name the runtime by an unversioned soname).  A plain run loads it
+        # too, although the headline needs no torch buffer: the headline is then measured on the HIP / HSA
+        # runtime torch ships, the one the --full run and the test suite run it on, not on the system's
         import torch  # noqa: F401
     sync = Sync(world, local, os.environ.get("JANUS_BENCH_BACKEND", "nccl"))
     import janus_gpu as jg
@@ -931,7 +975,8 @@ def main():
 
     res = {}
     if args.workload in ("all", "pnc", "pnc-orset"):
-        res["pnc"] = bench_pnc(jg, ctx, sync, rank, world, args.steps, args.warmup, args.pnc_shape, args.scaling)
+        res["pnc"] = bench_pnc(jg, ctx, sync, rank, world, args.steps, args.warmup, args.pnc_shape, args.scaling,
+                               args.dump_outputs)
     if args.workload in ("all", "orset", "pnc-orset"):
         res["orset"] = bench_orset(jg, ctx, sync, rank, world, max(1, args.steps // 2), args.warmup, args.scaling)
     if world > 1 and rank == 0 and args.workload in ("all", "exchange") and ("pnc" in res or "orset" in res):

@@ -10,14 +10,14 @@ export TMPDIR=/tmp
 for i in 1 2 3; do
   for v in A B; do
     lib=$A; [ $v = B ] && lib=$B
-    JANUS_GPU_LIB=$lib timeout -k 10 200 python bench.py --workload json --steps 20 --no-cpu-baseline > "$OUT/b$v$i.json" 2>/dev/null || exit 1
+    JANUS_GPU_LIB=$lib timeout -k 10 200 python bench.py --full --workload json --steps 20 --no-cpu-baseline > "$OUT/b$v$i.json" 2>/dev/null || exit 1
     python3 -c "import json;d=json.loads(open('$OUT/b$v$i.json').read().strip().splitlines()[-1]);l=d['legs']['json_apply'];print('$v', l.get('ms_per_wave'), l.get('cold_wave_ms'))"
   done
 done
 for v in A B; do
   lib=$A; [ $v = B ] && lib=$B
   for C in FETCH_SIZE WRITE_SIZE; do
-    JANUS_GPU_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc $C -d "$OUT/pmc_${v}_$C" -o run --output-format csv -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload json > "$OUT/pmc_${v}_$C.out" 2>&1 || exit 1
+    JANUS_GPU_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc $C -d "$OUT/pmc_${v}_$C" -o run --output-format csv -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload json > "$OUT/pmc_${v}_$C.out" 2>&1 || exit 1
   done
 done
 echo ab-done

@@ -7,7 +7,7 @@ OUT=${1:-gpurun_out/pmc_orset}
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 ORSET="janus-crdt_amd/build/bench_orset --sets 2000 --msgs 200000 --waves 2 --cpu-msgs 0 --device 0 --direct"
-JSON="python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload json"
+JSON="python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload json"
 SQ1=SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_INSTS_VMEM,SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_WAVE_CYCLES,SQ_BUSY_CYCLES
 SQ2=SQ_ACTIVE_INST_ANY,SQ_INSTS_SMEM,SQ_WAIT_INST_LDS,SQ_LDS_BANK_CONFLICT,SQ_LDS_IDX_ACTIVE
 TCC=TCC_ATOMIC_sum,TCC_HIT_sum,TCC_MISS_sum,TCC_EA0_RDREQ_sum

@@ -24,10 +24,10 @@ pass() {  # pass <name> <counters> <command...>
     step "pmc $name ($ctr)"
     timeout -s KILL 150 rocprofv3 --pmc "$ctr" -d "$OUT/$name" -o run --output-format csv -- "$@" > "$OUT/$name.out" 2> "$OUT/$name.err" || exit 1
 }
-PNC_ORSET="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --workload pnc-orset"
-EXCH="python3 bench.py --steps 16 --warmup 2 --no-cpu-baseline --workload exchange"
-JSON="python3 bench.py --steps 8 --warmup 1 --no-cpu-baseline --workload json"
-DIGEST="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --workload digest"
+PNC_ORSET="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --workload pnc-orset"
+EXCH="python3 bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --workload exchange"
+JSON="python3 bench.py --full --steps 8 --warmup 1 --no-cpu-baseline --workload json"
+DIGEST="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --workload digest"
 APPLY="janus-crdt_amd/build/bench_apply --accounts 1000000 --ops 1000000 --waves 3 --cpu-msgs 0 --device 0"
 ORSET_LOOP="janus-crdt_amd/build/bench_orset --sets 2000 --msgs 200000 --waves 3 --cpu-msgs 0 --device 0 --direct"
 PHASES=${PHASES:-"trace pmc summary bench"}
@@ -45,13 +45,13 @@ trace trace_orset_loop 300 $ORSET_LOOP
 fi
 if has pmc; then
 for C in FETCH_SIZE WRITE_SIZE; do
-    pass pmc_$C $C python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --workload pnc-orset
-    pass pmc_exch_$C $C python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload exchange
-    pass pmc_json_$C $C python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload json
+    pass pmc_$C $C python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --workload pnc-orset
+    pass pmc_exch_$C $C python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload exchange
+    pass pmc_json_$C $C python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload json
     pass pmc_orset_loop_$C $C $ORSET_LOOP
 done
-pass sq_json $SQ python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload json
-pass sq2_json $SQ2 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload json
+pass sq_json $SQ python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload json
+pass sq2_json $SQ2 python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload json
 pass sq_orset_loop $SQ $ORSET_LOOP
 pass sq2_orset_loop $SQ2 $ORSET_LOOP
 pass tcc_orset_loop $TCC $ORSET_LOOP
@@ -68,11 +68,11 @@ if [ -n "$WITH_BENCH" ] && has bench; then
     step bench
     mkdir -p profiles
     if [ -f "$OUT/pmc_$LABEL.json" ]; then cp "$OUT/pmc_$LABEL.json" "profiles/pmc_$LABEL.json"; fi
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_final" -o run --output-format csv -- python3 bench.py \
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_final" -o run --output-format csv -- python3 bench.py --full \
         > "$OUT/bench_final.json" 2> "$OUT/bench_final.err" || exit 1
     # and the same command without the profiler: the trace's per-dispatch cost shows on the apply loops' many
     # short kernels (the OR-Set wave: 5.50 ms traced, 5.31 ms not), not on the ms-scale merges
     step bench_untraced
-    timeout -k 10 600 python3 bench.py > "$OUT/bench_final_untraced.json" 2> "$OUT/bench_final_untraced.err" || exit 1
+    timeout -k 10 600 python3 bench.py --full > "$OUT/bench_final_untraced.json" 2> "$OUT/bench_final_untraced.err" || exit 1
 fi
 echo profile-done

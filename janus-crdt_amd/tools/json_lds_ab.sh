@@ -11,8 +11,8 @@ for LIB in "$@"; do
     name=$(basename "$LIB" .so)
     echo "[$(date +%H:%M:%S)] $name"
     JANUS_GPU_LIB=$PWD/$LIB timeout -s KILL 150 rocprofv3 --pmc $CTR -d "$OUT/$name" -o run --output-format csv -- \
-        python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload json > "$OUT/$name.pmc.out" 2> "$OUT/$name.pmc.err" || exit 1
-    JANUS_GPU_LIB=$PWD/$LIB timeout -k 10 150 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --workload json \
+        python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --workload json > "$OUT/$name.pmc.out" 2> "$OUT/$name.pmc.err" || exit 1
+    JANUS_GPU_LIB=$PWD/$LIB timeout -k 10 150 python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --workload json \
         > "$OUT/$name.json" 2> "$OUT/$name.err" || exit 1
     python3 - "$OUT/$name" <<'EOF' || exit 1
 import csv, glob, sys, collections
