@@ -529,6 +529,113 @@ int jg_waves_update_digests(const jg_wave* const* waves, uint64_t n_waves, const
 int jg_wave_sha256(const jg_wave* wave, void* d_out, uint8_t async);
 
 /* ---------------------------------------------------------------------------------------------
+ * Key-space set (csrc/tpset.hip) — one TPSet<string?> resident on the device
+ * (MergeSharp/MergeSharp/CRDTs/2P-Set.cs:60-213), the CRDT Janus keeps its own key space in
+ * (BFT-CRDT/CRDTManagers/KeySpaceManager.cs:34,87: every key as key + "\0" + guid).  Additive to ABI v10: these
+ * entry points are new names, nothing existing changes (JG_ABI_VERSION stays 10); jg_apply_committed /
+ * jg_apply_block still skip key-space messages, a caller opts in by calling these.
+ * Strings are UTF-8 bytes; the C# null element (HashSet<string?> holds it) is carried as a flag.  A string's
+ * ORDINAL is its index in addSet's (or removeSet's) enumeration order: nothing is ever removed from either
+ * HashSet, so that is first-insertion order.  String batches are (off[n + 1], off[0] = 0, bytes) as elsewhere.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct jg_tpset jg_tpset;
+/* new TPSet<string>() (2P-Set.cs:93-97) with room for cap_strings distinct strings (the null element not
+ * counted) of cap_bytes UTF-8 bytes in all. */
+int jg_tpset_create(jg_ctx* ctx, uint64_t cap_strings, uint64_t cap_bytes, jg_tpset** out);
+int jg_tpset_destroy(jg_tpset* set);
+/* addSet.Count, removeSet.Count (Count, 2P-Set.cs:76-82, is *n_add - *n_rem, reported literally even when a
+ * merge put strings into removeSet that addSet lacks) and the string bytes held.  Any pointer may be NULL. */
+int jg_tpset_size(jg_tpset* set, uint64_t* n_add, uint64_t* n_rem, uint64_t* n_bytes);
+/* Add (2P-Set.cs:106-109, op[i] = 1) and Remove (:117-126, op[i] = 2: only if Contains) of string i (the null
+ * element where is_null != NULL && is_null[i]), in op order.  result[i] (optional) = 1 for an Add, Remove's bool
+ * for a Remove.  Any other op id, or bytes that are not well-formed UTF-8: JG_EINVAL; out of strings or bytes:
+ * JG_ESTATE; nothing applied either way. */
+int jg_tpset_apply_ops(jg_tpset* set, uint64_t n, const uint8_t* op, const uint64_t* off, const uint8_t* bytes, const uint8_t* is_null,
+                       uint8_t* result);
+/* Contains (2P-Set.cs:169-172): out[i] = in addSet and not in removeSet. */
+int jg_tpset_contains(jg_tpset* set, uint64_t n, const uint64_t* off, const uint8_t* bytes, const uint8_t* is_null, uint8_t* out);
+/* LookupAll (2P-Set.cs:133-136): addSet.Except(removeSet) in addSet's order, from add ordinal from_ord on.  Member
+ * k: ord[k], bytes[off[k], off[k+1]), is_null[k] = the null element (no bytes).  ord / off / bytes / is_null all
+ * NULL = size query (*n members, *n_bytes bytes); else *n / *n_bytes hold the buffers' capacities on entry (off
+ * has room for *n + 1) and the sizes on return; JG_ESTATE if a buffer is short (sizes still returned). */
+int jg_tpset_lookup_all(jg_tpset* set, uint64_t from_ord, uint64_t* n, uint64_t* n_bytes, uint64_t* ord, uint64_t* off, uint8_t* bytes,
+                        uint8_t* is_null);
+/* ApplySynchronizedUpdate (2P-Set.cs:195-199) -> TPSetMsg.Decode (:40-46) -> Merge (:188-192) of n encoded
+ * states {"addSet":[...],"removeSet":[...]}, message after message: addSet.UnionWith then removeSet.UnionWith, new
+ * strings taking ordinals in the arrays' order.  The accepted form is oracle/json.hpp's contract (whitespace,
+ * members in any order, unknown members skipped to depth 64, a repeated member's last occurrence, full JSON strings,
+ * a string repeated in one array de-duplicated, `null` elements).  One rule differs on purpose from the PN-Counter /
+ * OR-Set decoders: Merge walks addSet first, so a message whose addSet is valid but whose removeSet is missing or
+ * null has its addSet merged and the call stops there with *partial = 1 (the reference throws between the two
+ * UnionWith calls); a message whose addSet is missing or null, or that is malformed anywhere, applies nothing.
+ * Every message before the first such message is applied and nothing after it: JG_EINVAL with *bad_msg = its
+ * index (UINT64_MAX on success).  JG_ESTATE (out of strings or bytes): nothing applied.
+ * mode 0 = automatic: messages in flat form (one object, addSet then removeSet, each once, arrays of strings or
+ * nulls, any whitespace) go through the parallel scanner, every other message through the serial parser, which is
+ * the definition; mode 1 = the serial parser only.  Both give the same store. */
+int jg_tpset_merge_json(jg_tpset* set, uint64_t n, const uint64_t* off, const uint8_t* bytes, uint32_t mode, uint64_t* bad_msg, uint8_t* partial);
+/* GetLastSynchronizedUpdate().Encode() (2P-Set.cs:210-213, :49-52) of the whole set, byte for byte System.Text.Json's
+ * compact output (strings escaped by JavaScriptEncoder.Default).  out NULL = size query; JG_ESTATE if *n_bytes >
+ * cap (out untouched). */
+int jg_tpset_encode_json(jg_tpset* set, uint64_t* n_bytes, uint8_t* out, uint64_t cap);
+/* Figures of the set's last jg_tpset_merge_json: messages and payload bytes each parser took, array elements the
+ * applied messages held (strings_seen), entries appended to addSet or removeSet (strings_new), the scanner's tile
+ * size, device seconds (hipEvents around the call's kernels). */
+typedef struct jg_tpset_stats {
+    uint64_t msgs_parallel, bytes_parallel, msgs_serial, bytes_serial;
+    uint64_t strings_seen, strings_new;
+    uint64_t tile_bytes;
+    double device_s;
+    uint64_t stage_bytes; /* the encoder's write pass stages this many wire bytes per window                     */
+    double encode_s;      /* device seconds of the set's last jg_tpset_encode_json that wrote: length pass, scan   */
+                          /* (one host read of the total between them) and write pass; the copy out excluded      */
+} jg_tpset_stats;
+int jg_tpset_last_stats(jg_tpset* set, jg_tpset_stats* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Key space (csrc/tpset.hip) — KeySpaceManager's state on the device (BFT-CRDT/CRDTManagers/KeySpaceManager.cs): the
+ * set above, the keySpaces dictionary (key string -> Guid, :30) and the LastKeySpaceSet watermark (:35).  Additive
+ * to ABI v10.  Keys are UTF-8 bytes in (off[n + 1], off[0] = 0, bytes) batches; Guids are jg_guid.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct jg_keyspace jg_keyspace;
+/* new KeySpaceManager: room for cap_keys entries of cap_bytes bytes in all (an entry is key + "\0" + 36-byte guid). */
+int jg_keyspace_create(jg_ctx* ctx, uint64_t cap_keys, uint64_t cap_bytes, jg_keyspace** out);
+int jg_keyspace_destroy(jg_keyspace* ks);
+/* The underlying set (owned by the key space), for jg_tpset_encode_json (GetLastSynchronizedUpdate of the key-space
+ * CRDT, what CreateNewKVPair ships) and queries.  Merge into it only through jg_keyspace_receive. */
+int jg_keyspace_set(jg_keyspace* ks, jg_tpset** set);
+/* CreateNewKVPair (KeySpaceManager.cs:121-136) for a batch, in order: keySpaces.TryAdd(key, guid) (:130; added[i] =
+ * its bool, optional) and then, whatever it returned, keySpaceCRDT.Add(key + "\0" + guid.ToString()) (:131). */
+int jg_keyspace_create_keys(jg_keyspace* ks, uint64_t n, const uint64_t* off, const uint8_t* key_bytes, const jg_guid* guid, uint8_t* added);
+/* The key-space CRDT's ApplySynchronizedUpdate followed by OnNext (KeySpaceManager.cs:151-178), message after
+ * message (jg_tpset_merge_json's contract per message, mode included; each message is one merge on the device, so
+ * many small states in one call cost one round of launches each).  OnNext takes LookupAll().Except(LastKeySpaceSet):
+ * an entry is SEEN by the OnNext of the message that added it unless that message or an earlier one put it in
+ * removeSet; a removal by a later message does not unsee it.  For each seen entry, in ordinal order: key = the
+ * bytes before the first NUL, guid = the segment between the first and the second NUL (Split("\0")[1]) in "D" form
+ * of either case; a key the dictionary lacks is added with that guid (the first entry wins) and journalled.
+ * A message Decode / Merge rejects stops the call as in jg_tpset_merge_json (JG_EINVAL, *bad_msg, *partial; its
+ * OnNext does not run: entries a partial merge added are seen by the next message's OnNext).  *n_new = journal
+ * records this call appended.  JG_ESTATE from the dictionary or the journal (neither can fill before the set does)
+ * comes after that message's merge, which is not rolled back: the watermark stays and the next call's OnNext takes
+ * those entries.
+ * DEPARTURE (stated, parity-unpinned): the reference throws out of OnNext on an entry without a NUL
+ * (IndexOutOfRangeException), with a guid segment Guid.Parse rejects (FormatException) or on the null element (NRE),
+ * before LastKeySpaceSet advances, and so wedges on that entry at every later message; Guid.Parse also accepts forms
+ * other than "D", which an honest node never writes.  Here such an entry is journalled with a status, not added to
+ * the dictionary, and processing goes on; only the "D" form is a guid. */
+int jg_keyspace_receive(jg_keyspace* ks, uint64_t n, const uint64_t* off, const uint8_t* bytes, uint32_t mode, uint64_t* bad_msg, uint8_t* partial,
+                        uint64_t* n_new);
+/* The journal of OnNext's outcomes since record `from`, in the style of jg_orset_names_since: records [from, *to)
+ * with *to = the journal's length now; record i - from = bytes[off[i], off[i+1]), guid[i], status[i]: 0 = key added
+ * (bytes = the key); 1 = the entry has no NUL; 2 = its guid segment is not in "D" form; 3 = the null element (1-3:
+ * bytes = the raw entry, guid zero, nothing added).  off / bytes / guid / status all NULL = size query (*to,
+ * *n_bytes); else *n_bytes holds bytes' capacity on entry (JG_ESTATE if short) and off has *to - from + 1 entries. */
+int jg_keyspace_new_keys(jg_keyspace* ks, uint64_t from, uint64_t* to, uint64_t* n_bytes, uint64_t* off, uint8_t* bytes, jg_guid* guid, uint8_t* status);
+/* keySpaces[key] (GetKeySpace, KeySpaceManager.cs:99-110): found[i], guid[i] (zero when absent). */
+int jg_keyspace_lookup(jg_keyspace* ks, uint64_t n, const uint64_t* off, const uint8_t* key_bytes, jg_guid* guid, uint8_t* found);
+
+/* ---------------------------------------------------------------------------------------------
  * Synthetic workloads (bench / size-independent parity): device-side counter-based generators,
  * defined in DESIGN.md §Synthetic inputs and mirrored on the host by the test oracle.
  * ------------------------------------------------------------------------------------------- */

@@ -41,6 +41,10 @@ EXPORTS = [
     "jg_apply_committed", "jg_apply_block", "jg_apply_stream_begin", "jg_apply_stream_append", "jg_apply_stream_end",
     "jg_comm_unique_id", "jg_comm_init", "jg_comm_destroy", "jg_pnc_exchange", "jg_orset_exchange", "jg_comm_last_stats",
     "jg_comm_init_host", "jg_exchange_plan", "jg_global_key",
+    "jg_tpset_create", "jg_tpset_destroy", "jg_tpset_size", "jg_tpset_apply_ops", "jg_tpset_contains", "jg_tpset_lookup_all",
+    "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
+    "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
+    "jg_keyspace_new_keys", "jg_keyspace_lookup",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -143,6 +147,22 @@ _SIGS = {
     "jg_pnc_exchange": ([_vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_orset_exchange": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_comm_last_stats": ([_vp, _vp], C.c_int),
+    "jg_tpset_create": ([_vp, _u64, _u64, C.POINTER(_vp)], C.c_int),
+    "jg_tpset_destroy": ([_vp], C.c_int),
+    "jg_tpset_size": ([_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)], C.c_int),
+    "jg_tpset_apply_ops": ([_vp, _u64, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_tpset_contains": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_tpset_lookup_all": ([_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
+    "jg_tpset_merge_json": ([_vp, _u64, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(C.c_uint8)], C.c_int),
+    "jg_tpset_encode_json": ([_vp, C.POINTER(_u64), _vp, _u64], C.c_int),
+    "jg_tpset_last_stats": ([_vp, _vp], C.c_int),
+    "jg_keyspace_create": ([_vp, _u64, _u64, C.POINTER(_vp)], C.c_int),
+    "jg_keyspace_destroy": ([_vp], C.c_int),
+    "jg_keyspace_set": ([_vp, C.POINTER(_vp)], C.c_int),
+    "jg_keyspace_create_keys": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_keyspace_receive": ([_vp, _u64, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(C.c_uint8), C.POINTER(_u64)], C.c_int),
+    "jg_keyspace_new_keys": ([_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
+    "jg_keyspace_lookup": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
 }
 GUID_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])  # jg_guid
 
@@ -984,6 +1004,168 @@ class Comm:
         if self._h:
             _check(load().jg_comm_destroy(self._h))
             self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class TPSetStats(C.Structure):
+    """jg_tpset_stats: what each parser took in the last merge_json, strings seen / appended, tile size, device s."""
+    _fields_ = [("msgs_parallel", C.c_uint64), ("bytes_parallel", C.c_uint64), ("msgs_serial", C.c_uint64), ("bytes_serial", C.c_uint64),
+                ("strings_seen", C.c_uint64), ("strings_new", C.c_uint64), ("tile_bytes", C.c_uint64), ("device_s", C.c_double), ("stage_bytes", C.c_uint64), ("encode_s", C.c_double)]
+
+
+def _pack_strings(items):
+    """[bytes | None] -> (off u64[n+1], payload u8, is_null u8[n]); None = the C# null element."""
+    is_null = np.array([x is None for x in items], np.uint8)
+    data, off = pack_wave([b"" if x is None else bytes(x) for x in items])
+    return off, data, is_null
+
+
+class TPSet:
+    """One TPSet<string?> on the device (jg_tpset_*, csrc/tpset.hip): the replicated key-space set.  Strings are
+    bytes (UTF-8), None is the null element."""
+
+    def __init__(self, ctx: Context, cap_strings: int, cap_bytes: int):
+        self._h = _vp()
+        _check(load().jg_tpset_create(ctx.handle, cap_strings, cap_bytes, C.byref(self._h)))
+
+    def size(self) -> tuple[int, int, int]:
+        a, r, b = _u64(), _u64(), _u64()
+        _check(load().jg_tpset_size(self._h, C.byref(a), C.byref(r), C.byref(b)))
+        return a.value, r.value, b.value
+
+    def count(self) -> int:
+        a, r, _ = self.size()
+        return a - r
+
+    def apply_ops(self, ops) -> list[bool]:
+        """ops: [(1 | 2, bytes | None)] = Add / Remove in order; returns each op's bool (Add: True)."""
+        op = np.array([o for o, _ in ops], np.uint8)
+        off, data, is_null = _pack_strings([s for _, s in ops])
+        res = np.zeros(len(ops), np.uint8)
+        _check(load().jg_tpset_apply_ops(self._h, len(ops), _ptr(op), _ptr(off), _ptr(data), _ptr(is_null), _ptr(res)))
+        return [bool(x) for x in res]
+
+    def add(self, s) -> None:
+        self.apply_ops([(1, s)])
+
+    def remove(self, s) -> bool:
+        return self.apply_ops([(2, s)])[0]
+
+    def contains(self, items) -> list[bool]:
+        off, data, is_null = _pack_strings(items)
+        out = np.zeros(len(items), np.uint8)
+        _check(load().jg_tpset_contains(self._h, len(items), _ptr(off), _ptr(data), _ptr(is_null), _ptr(out)))
+        return [bool(x) for x in out]
+
+    def lookup_all(self, from_ord: int = 0, with_ords: bool = False):
+        """LookupAll from add ordinal from_ord on: [bytes | None] in addSet's order (with_ords: (ord, item) pairs)."""
+        n, nb = _u64(), _u64()
+        _check(load().jg_tpset_lookup_all(self._h, from_ord, C.byref(n), C.byref(nb), None, None, None, None))
+        ord_ = np.zeros(n.value, np.uint64)
+        off = np.zeros(n.value + 1, np.uint64)
+        data = np.zeros(max(nb.value, 1), np.uint8)
+        is_null = np.zeros(max(n.value, 1), np.uint8)
+        _check(load().jg_tpset_lookup_all(self._h, from_ord, C.byref(n), C.byref(nb), _ptr(ord_), _ptr(off), _ptr(data), _ptr(is_null)))
+        raw = data.tobytes()
+        items = [None if is_null[k] else raw[int(off[k]):int(off[k + 1])] for k in range(n.value)]
+        return list(zip((int(o) for o in ord_), items)) if with_ords else items
+
+    def merge_json(self, msgs, mode: int = 0) -> None:
+        """Merge encoded TPSetMsg states in order.  Raises JanusError (bad_msg, partial set) at the first bad one."""
+        data, off = pack_wave([bytes(m) for m in msgs])
+        bad, partial = _u64(), C.c_uint8()
+        rc = load().jg_tpset_merge_json(self._h, len(msgs), _ptr(off), _ptr(data), mode, C.byref(bad), C.byref(partial))
+        try:
+            _check(rc, bad.value)
+        except JanusError as e:
+            e.partial = bool(partial.value)
+            raise
+
+    def encode_json(self) -> bytes:
+        n = _u64()
+        _check(load().jg_tpset_encode_json(self._h, C.byref(n), None, 0))
+        out = np.zeros(n.value, np.uint8)
+        _check(load().jg_tpset_encode_json(self._h, C.byref(n), _ptr(out), n.value))
+        return out.tobytes()
+
+    def stats(self) -> TPSetStats:
+        st = TPSetStats()
+        _check(load().jg_tpset_last_stats(self._h, C.cast(C.byref(st), _vp)))
+        return st
+
+    def close(self) -> None:
+        if self._h:
+            _check(load().jg_tpset_destroy(self._h))
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class KeySpace:
+    """KeySpaceManager's state on the device (jg_keyspace_*): the set, the keySpaces dictionary, the watermark and the
+    journal of new keys.  Keys are bytes, guids (lo, hi) pairs."""
+
+    def __init__(self, ctx: Context, cap_keys: int, cap_bytes: int):
+        self._h = _vp()
+        _check(load().jg_keyspace_create(ctx.handle, cap_keys, cap_bytes, C.byref(self._h)))
+        h = _vp()
+        _check(load().jg_keyspace_set(self._h, C.byref(h)))
+        self.set = TPSet.__new__(TPSet)  # a view: the key space owns the handle
+        self.set._h = h
+
+    def create_keys(self, pairs) -> list[bool]:
+        """[(key, (lo, hi))]: CreateNewKVPair in order; returns each TryAdd's bool."""
+        data, off = pack_wave([bytes(k) for k, _ in pairs])
+        guid = np.array([g for _, g in pairs], dtype=np.uint64).reshape(-1, 2).view(GUID_DTYPE).reshape(-1)
+        added = np.zeros(len(pairs), np.uint8)
+        _check(load().jg_keyspace_create_keys(self._h, len(pairs), _ptr(off), _ptr(data), _ptr(guid), _ptr(added)))
+        return [bool(x) for x in added]
+
+    def receive(self, msgs, mode: int = 0) -> int:
+        """Merge + OnNext per message; returns the journal records appended.  JanusError (bad_msg, partial, n_new)."""
+        data, off = pack_wave([bytes(m) for m in msgs])
+        bad, partial, n_new = _u64(), C.c_uint8(), _u64()
+        rc = load().jg_keyspace_receive(self._h, len(msgs), _ptr(off), _ptr(data), mode, C.byref(bad), C.byref(partial), C.byref(n_new))
+        try:
+            _check(rc, bad.value)
+        except JanusError as e:
+            e.partial, e.n_new = bool(partial.value), n_new.value
+            raise
+        return n_new.value
+
+    def new_keys(self, from_: int = 0):
+        """The journal from record from_: ([(bytes, (lo, hi), status)], to)."""
+        to, nb = _u64(), _u64()
+        _check(load().jg_keyspace_new_keys(self._h, from_, C.byref(to), C.byref(nb), None, None, None, None))
+        n = to.value - from_
+        off, data = np.zeros(n + 1, np.uint64), np.zeros(max(nb.value, 1), np.uint8)
+        guid, status = np.zeros(max(n, 1), GUID_DTYPE), np.zeros(max(n, 1), np.uint8)
+        nb = _u64(len(data))
+        _check(load().jg_keyspace_new_keys(self._h, from_, C.byref(to), C.byref(nb), _ptr(off), _ptr(data), _ptr(guid), _ptr(status)))
+        raw = data.tobytes()
+        return [(raw[int(off[i]):int(off[i + 1])], (int(guid["lo"][i]), int(guid["hi"][i])), int(status[i])) for i in range(n)], to.value
+
+    def lookup(self, keys):
+        """[(lo, hi) | None] per key."""
+        data, off = pack_wave([bytes(k) for k in keys])
+        guid, found = np.zeros(max(len(keys), 1), GUID_DTYPE), np.zeros(max(len(keys), 1), np.uint8)
+        _check(load().jg_keyspace_lookup(self._h, len(keys), _ptr(off), _ptr(data), _ptr(guid), _ptr(found)))
+        return [(int(guid["lo"][i]), int(guid["hi"][i])) if found[i] else None for i in range(len(keys))]
+
+    def close(self) -> None:
+        if self._h:
+            _check(load().jg_keyspace_destroy(self._h))
+            self._h = _vp()
+            self.set._h = _vp()
 
     def __enter__(self):
         return self
