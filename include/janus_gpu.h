@@ -110,6 +110,38 @@ int jg_pnc_apply_ops(jg_pnc* pnc, uint64_t n_ops, const uint32_t* key, const uin
  * where a checked Sum throws; the call still returns JG_OK.  key_idx NULL = keys 0..n-1. */
 int jg_pnc_values(jg_pnc* pnc, const uint32_t* key_idx, uint64_t n, int64_t* out, uint8_t* overflow);
 
+/* The store's current shape (any output may be NULL).  It changes only through jg_pnc_reserve and the
+ * widening jg_pnc_set_max_replicas allows. */
+int jg_pnc_shape(jg_pnc* pnc, uint64_t* n_keys, uint32_t* n_replicas, uint32_t* elem_bytes);
+/* Grow the store in place, on the device, to at least n_keys x n_replicas.  It stands in for what the
+ * reference gets for free: a PNCounter's Dictionary<Guid,int> takes any number of replicas as Merge meets
+ * them (PNCounters.cs:131-144), and KeySpaceManager.CreateNewKVPair (KeySpaceManager.cs:121-136) creates a
+ * key whenever one is learnt.  Never shrinks: a request at or below the current shape in both dimensions
+ * returns JG_OK and does nothing.  Afterwards every old cell (k, c) of P and N holds its value and every
+ * new cell is 0 (= absent); if the replica table exists, every old slot keeps its Guid, a new key has no
+ * columns and every new slot is all-zero; if it does not exist yet it is created at first use, at the new
+ * shape.  Refused, the store untouched: n_keys > 2^32 - 1 or n_replicas > 2^30 - 1 (JG_EINVAL);
+ * n_replicas > 256 while the replica table exists (JG_EINVAL); a jg_pnc_wave_begin wave is open or a node
+ * wave holds the store (JG_EINVAL); an allocation fails (JG_ENOMEM).  The old and the new buffers are
+ * resident together during the call (every new buffer is allocated before anything is copied): the device
+ * needs room for both.  The call waits for everything queued on the context (an async jg_pnc_merge_batch
+ * included) before it releases the old buffers.  A jg_rows batch created for the old n_replicas keeps being
+ * refused by jg_pnc_merge_batch: create the batches of the new shape. */
+int jg_pnc_reserve(jg_pnc* pnc, uint64_t n_keys, uint32_t n_replicas);
+/* Opt-in automatic widening (the same Dictionary growth, PNCounters.cs:131-144; a node whose keys arrive
+ * through KeySpaceManager.cs:121-136 cannot know their replicas in advance).  0, the default = a fixed
+ * shape: a state naming more replicas than the store's columns fails with JG_ESTATE as ever.  With
+ * max_replicas > n_replicas, a jg_pnc_merge_json / _merge_wave / _wave_commit, a jg_pnc_intern or a node
+ * wave (jg_apply_committed, jg_apply_block, jg_apply_stream_end) that would fail for row capacity is
+ * rolled back as ever, the store widened to min(2 x n_replicas, max_replicas) (and at most the replica
+ * table's 256) and the call run again, until it succeeds or the bound is reached.  At the bound the call
+ * fails exactly as a fixed store's: same code, same *bad_msg, contents rolled back; the store may stay
+ * wider than it was, its contents then the earlier ones padded with zeros.  The caller's bound matters: it
+ * is what keeps one faulty peer, naming ever new replicas, from inflating every row of the store.  Keys
+ * never grow by themselves: an out-of-range key_idx stays the caller's error.  Read the shape back with
+ * jg_pnc_shape after a call that may have widened. */
+int jg_pnc_set_max_replicas(jg_pnc* pnc, uint32_t max_replicas);
+
 /* Device-resident received batch (the committed state messages of a wave, decoded to rows).
  * key_idx NULL at upload = identity rows (requires n_rows == the store's n_keys at merge time). */
 int jg_rows_create(jg_ctx* ctx, uint64_t n_rows, uint32_t n_replicas, uint32_t elem_bytes, jg_rows** out);

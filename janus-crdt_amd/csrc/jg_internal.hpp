@@ -18,6 +18,8 @@ namespace jg {
 // Row / set id of a message of another kind in a node wave (csrc/node.hip): the PN-Counter and OR-Set
 // passes run over the same uploaded wave and skip each other's messages.
 constexpr uint32_t kSkipIdx = 0xFFFFFFFFu;
+// Replicas per key the replica table holds (json.hip: per-vector duplicate masks are 4 x 64 bits).
+constexpr uint32_t kMaxTableReplicas = 256;
 
 // ---- the one owner rule of a sharded node -------------------
 // A key uid belongs to rank shard_of_uid(uid, world) (the apply loop's shard shortcut, jg_shard_of); its
@@ -132,6 +134,7 @@ struct jg_pnc {
     uint64_t n_keys;
     uint32_t R;
     uint32_t eb;  // elem bytes (4 | 8)
+    uint32_t max_R = 0;  // jg_pnc_set_max_replicas: a row-capacity failure widens R up to this (0: fixed shape)
     jg::DevBuf P, N;
     // replica table (json.hip): [n_keys x R] 16-byte Guids + [n_keys] column counts, first use only
     jg::DevBuf cols, ncols;
@@ -253,6 +256,10 @@ void sync_counts(jg_orset* s);   // fold a pending async count into the host cop
 void set_dense(jg_ctx* ctx, jg_stream_soa& s, uint64_t n);
 // pnc.hip: scatter-max of n_rows device rows into the store's keys (async on the store's stream).
 void pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t* d_keys, uint64_t n_rows);
+// pnc.hip: the store grown to at least [n_keys x n_replicas] (jg_pnc_reserve without its open-wave refusals), and
+// one doubling of R under jg_pnc_set_max_replicas' bound (false: at the bound).
+void pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas);
+bool pnc_auto_widen(jg_pnc* p);
 // orset.hip: merge n_runs sorted, duplicate-free runs (device SoA, run after run) into the store.
 void orset_merge_runs(jg_orset* s, uint32_t n_runs, const uint64_t* add_counts, const uint64_t* rem_counts, const unsigned long long* add_key,
                       const uint4* add_tag, const uint32_t* add_ord, const unsigned long long* rem_key, const uint4* rem_tag,

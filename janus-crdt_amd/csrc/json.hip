@@ -55,7 +55,7 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kMaxJsonReplicas = 256;  // per-vector duplicate masks are 4 x 64 bits
+constexpr uint32_t kMaxJsonReplicas = jg::kMaxTableReplicas;  // per-vector duplicate masks are 4 x 64 bits
 
 enum : uint32_t { kErrSyntax = 0, kErrFull = 1, kErrInternal = 2 };
 
@@ -815,12 +815,19 @@ Status read_status(jg_ctx* ctx, const unsigned long long* d) {
 // kErrInternal (a message pass A accepted that a later pass could not parse or resolve again) is the library's
 // own inconsistency, never a verdict on the message: it leaves *bad_msg unset, so a node wave does not take it for
 // the reference's cut (pnc_node_finish rethrows, wave_end aborts the wave) and no caller blames the payload.
+// kErrFull's error: the one failure the opt-in widening (jg_pnc_set_max_replicas) answers by running the call again
+// on a wider store.  Everyone else catches it as the jg::Error it is (JG_ESTATE, the same text as ever).
+struct RowFull : jg::Error {};
+
 [[noreturn]] void fail_msg(unsigned long long code, uint64_t* bad_msg, const char* what) {
     const uint64_t m = code >> 2;
     const uint32_t kind = (uint32_t)(code & 3);
     if (bad_msg && kind != kErrInternal) *bad_msg = m;
-    if (kind == kErrFull)
-        jg::fail(JG_ESTATE, "%s %llu: its key holds more replicas than the store's columns", what, (unsigned long long)m);
+    if (kind == kErrFull) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "%s %llu: its key holds more replicas than the store's columns", what, (unsigned long long)m);
+        throw RowFull{{JG_ESTATE, msg}};
+    }
     if (kind == kErrInternal) jg::fail(JG_EHIP, "%s %llu: internal replica-table inconsistency", what, (unsigned long long)m);
     jg::fail(JG_EINVAL, "%s %llu is not a PNCounterMsg in the accepted JSON form (JsonException)", what, (unsigned long long)m);
 }
@@ -1016,6 +1023,29 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
     }
 }
 
+// finish_wave for a store that may widen itself (jg_pnc_set_max_replicas; a fixed store takes the plain call and
+// its errors).  A wave that fails for row capacity has been rolled back whole — the columns it added and the fused
+// pass A's raises — so the store holds its contents from before the wave: widen it (the contents padded with
+// zeros), run pass A again over the same resident messages [0, n) at the new stride, and finish again; until the
+// wave is through or R stands at its bound, where the failure is the fixed store's (same code, same *bad_msg).
+// `cap` = the messages the wave's scratch was sized for.
+void finish_wave_elastic(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uint32_t* rows, uint64_t n, uint64_t cap,
+                         uint64_t* bad_msg) {
+    for (;;) {
+        try {
+            finish_wave(p, bytes, off, rows, n, wave_scratch(p, cap), bad_msg);
+            return;
+        } catch (const RowFull&) {
+            if (!jg::pnc_auto_widen(p)) throw;
+        }
+        if (bad_msg) *bad_msg = UINT64_MAX;
+        const WaveScratch w = wave_scratch(p, cap);
+        begin_status(p, w.status);
+        p->scan_hi = 0;
+        launch_scan(p, bytes, off, rows, 0, n, w);
+    }
+}
+
 // The whole device side of a wave already in device memory.
 void merge_wave_dev(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uint32_t* rows, uint64_t n, uint64_t* bad_msg) {
     ensure_table(p);
@@ -1024,7 +1054,7 @@ void merge_wave_dev(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const 
     p->scan_hi = 0;
     p->fuse = json_fuse();
     launch_scan(p, bytes, off, rows, 0, n, w);
-    finish_wave(p, bytes, off, rows, n, w, bad_msg);
+    finish_wave_elastic(p, bytes, off, rows, n, n, bad_msg);
 }
 
 void check_wave_host(const jg_pnc* p, uint64_t n, const uint32_t* key_idx, const uint64_t* off, const char* fn) {
@@ -1062,7 +1092,9 @@ int pnc_node_finish(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const 
     *bad = UINT64_MAX;
     if (n == 0) return JG_OK;
     try {
-        finish_wave(p, bytes, off, rows, n, wave_scratch(p, p->wn), bad);
+        // a store that widens itself (jg_pnc_set_max_replicas) runs the resident messages again instead of cutting
+        // the wave at a key that ran out of columns; the widening passes the node wave's hold on the store
+        finish_wave_elastic(p, bytes, off, rows, n, p->wn, bad);
         p->scan_hi = 0;  // committed: a later abort of the node wave (an OR-Set commit failing) must not undo it
         return JG_OK;
     } catch (const Error& e) {
@@ -1110,7 +1142,6 @@ int jg_pnc_intern(jg_pnc* p, uint64_t n, const uint32_t* key_idx, const jg_guid*
         jg_ctx* ctx = p->ctx;
         jg::ensure_device(ctx);
         ensure_table(p);
-        const Table t = table_of(p);
         char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch, 64 + n * (4 + 16 + 8 + 4 + 4) + 256));
         auto* status = reinterpret_cast<unsigned long long*>(s);
         auto* keys = reinterpret_cast<unsigned long long*>(s + 64);
@@ -1119,17 +1150,20 @@ int jg_pnc_intern(jg_pnc* p, uint64_t n, const uint32_t* key_idx, const jg_guid*
         auto* cols = rows + n;
         auto* saved = cols + n;
         const Status init{~0ull, 0, ~0ull, 0};
-        JG_HIP(hipMemcpyAsync(status, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(rows, key_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(g, replica, n * 16, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_make_keys, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, rows, n, keys);
         unsigned long long* sorted = sort_keys(ctx, keys, n, p->n_keys);
-        hipLaunchKernelGGL(k_intern, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, sorted, n, g, t, cols, saved, status);
-        JG_HIP(hipGetLastError());
-        const Status st = read_status(ctx, status);
-        if (st.resolve_bad != ~0ull) {
+        for (;;) {  // once, or again on a wider store while it may widen itself (jg_pnc_set_max_replicas)
+            const Table t = table_of(p);
+            JG_HIP(hipMemcpyAsync(status, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_intern, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, sorted, n, g, t, cols, saved, status);
+            JG_HIP(hipGetLastError());
+            const Status st = read_status(ctx, status);
+            if (st.resolve_bad == ~0ull) break;
             hipLaunchKernelGGL(k_rollback, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, sorted, n, t, saved);
             JG_HIP(hipStreamSynchronize(ctx->stream));
+            if (jg::pnc_auto_widen(p)) continue;  // rolled back: the same entries over the wider rows
             jg::fail(JG_ESTATE, "jg_pnc_intern: entry %llu: its key holds more replicas than the store's columns",
                      (unsigned long long)(st.resolve_bad >> 2));
         }
@@ -1294,7 +1328,7 @@ int jg_pnc_wave_commit(jg_pnc* p, uint64_t* bad_msg) {
         jg::ensure_device(p->ctx);
         p->wopen = false;
         if (p->wn == 0) return;
-        finish_wave(p, p->wbytes.as<uint8_t>(), p->woff.as<uint64_t>(), p->wrows.as<uint32_t>(), p->wn, wave_scratch(p, p->wn), bad_msg);
+        finish_wave_elastic(p, p->wbytes.as<uint8_t>(), p->woff.as<uint64_t>(), p->wrows.as<uint32_t>(), p->wn, p->wn, bad_msg);
     });
 }
 

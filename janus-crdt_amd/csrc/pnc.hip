@@ -12,6 +12,11 @@
 //   k_apply_ops      Increment/Decrement (PNCounters.cs:97-112): wrapping atomic adds.
 //   k_values         PNCounter.Get (PNCounters.cs:87-90): one wave per key, exact prefix sums in
 //                    column order to reproduce the checked LINQ Sum's OverflowException.
+//   k_restride       jg_pnc_reserve's widening: dst[k][0..R_old) = src[k][0..R_old), zero elsewhere (a row
+//                    the Dictionary<Guid,int> grows into, PNCounters.cs:131-144).  Reads the old bytes once,
+//                    writes the new bytes once: (old + new) bytes at HBM rate.
+#include <algorithm>
+#include <chrono>
 #include <cstdlib>
 
 #include "jg_internal.hpp"
@@ -277,6 +282,51 @@ __global__ __launch_bounds__(kBlock) void k_values(const typename Elem<EB>::T* _
     }
 }
 
+// Re-stride copy (jg_pnc_reserve): the destination is n_units units (16-B vectors where both row sizes are whole
+// vectors, else cells) in rows of `dw`; unit (row, col) takes the source's (row, col) where row < src_rows and
+// col < sw, zero elsewhere, so every destination unit is written exactly once and no memset runs ahead of the
+// copy.  One unit per lane over a flat grid, as k_merge_dense: measured on MI355X on the widen's P array (1M keys,
+// 64 -> 128 int64 columns, 1.6 GB moved; tools/tune_reserve.hip) at 0.259 ms = 6.2 TB/s against 0.297 ms for a
+// device copy of the old bytes plus a memset of the new ones; 2 / 4 / 8 units in flight per lane 0.265 / 0.289 /
+// 0.283 ms, a grid capped at 16 blocks per CU 0.292 ms (4 units per lane: 0.308), plain instead of non-temporal
+// accesses the same (0.257);
+// past kRestrideBlocks blocks the grid strides.  Stores are coalesced, loads contiguous inside a row.  Index
+// arithmetic: the block's first (row, col) comes from one 32-bit divide up front and moves by the grid's step
+// (step_rows, step_cols: divided on the host) with a compare; a lane's own unit lies at most kBlock / dw + 1 rows
+// further, found by a float reciprocal with a +-1 fix-up (exact: the quotient is at most 257 and dw < 2^30) — no
+// 64-bit divide per unit.  Touched once: non-temporal both ways, no LDS.
+template <class T> __device__ __forceinline__ T nt_ld(const T* p) { return __builtin_nontemporal_load(p); }
+template <> __device__ __forceinline__ uint4 nt_ld<uint4>(const uint4* p) { return nt_load(p); }
+template <class T> __device__ __forceinline__ void nt_st(T* p, T v) { __builtin_nontemporal_store(v, p); }
+template <> __device__ __forceinline__ void nt_st<uint4>(uint4* p, uint4 v) { nt_store(p, v); }
+
+constexpr uint64_t kRestrideBlocks = 1u << 16;  // x kBlock = 16.8M units a pass (268 MB of vectors)
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_restride(T* __restrict__ dst, const T* __restrict__ src, uint32_t sw, uint32_t dw, float rdw,
+                                                     uint64_t src_rows, uint64_t n_units, uint64_t step_rows, uint32_t step_cols) {
+    const uint32_t first = blockIdx.x * kBlock;  // < 2^24 (kRestrideBlocks)
+    uint64_t row0 = first / dw;
+    uint32_t col0 = first - (uint32_t)row0 * dw;
+    for (uint64_t base = first; base < n_units; base += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t i = base + threadIdx.x;
+        if (i < n_units) {
+            const uint32_t c = col0 + threadIdx.x;  // < dw + kBlock
+            uint32_t q = (uint32_t)((float)c * rdw);
+            uint32_t col = c - q * dw;
+            if ((int32_t)col < 0) --q, col += dw;
+            else if (col >= dw) ++q, col -= dw;
+            const uint64_t row = row0 + q;
+            T v{};
+            if (row < src_rows && col < sw) v = nt_ld(src + row * sw + col);
+            nt_st(dst + i, v);
+        }
+        row0 += step_rows;
+        col0 += step_cols;
+        if (col0 >= dw) col0 -= dw, ++row0;
+    }
+}
+
 unsigned grid_for(jg_ctx* ctx, uint64_t work_items, unsigned per_cu = 8) {
     uint64_t g = (work_items + kBlock - 1) / kBlock;
     const uint64_t cap = (uint64_t)ctx->num_cus * per_cu;
@@ -397,11 +447,112 @@ void launch_rows_copy(jg_ctx* ctx, uint32_t eb, void* dst, const void* src, cons
     JG_HIP(hipGetLastError());
 }
 
+template <class T>
+void launch_restride_t(jg_ctx* ctx, void* dst, const void* src, uint64_t sw, uint64_t dw, uint64_t src_rows, uint64_t dst_rows) {
+    const uint64_t n_units = dst_rows * dw;
+    const unsigned grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((n_units + kBlock - 1) / kBlock, 1), kRestrideBlocks);
+    const uint64_t step = (uint64_t)grid * kBlock;
+    hipLaunchKernelGGL(k_restride<T>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)dst, (const T*)src, (uint32_t)sw, (uint32_t)dw,
+                       1.0f / (float)dw, src_rows, n_units, step / dw, (uint32_t)(step % dw));
+    JG_HIP(hipGetLastError());
+}
+
+// [src_rows x sr] cells of `cell` bytes into [dst_rows x dr] (dr > sr), new cells zero: the vector path where both
+// row sizes are whole 16-B vectors (always so for the replica table's Guids), else cell by cell.
+void launch_restride(jg_ctx* ctx, uint32_t cell, void* dst, const void* src, uint32_t sr, uint32_t dr, uint64_t src_rows, uint64_t dst_rows) {
+    const uint64_t sb = (uint64_t)sr * cell, db = (uint64_t)dr * cell;
+    if (sb % 16 == 0 && db % 16 == 0) launch_restride_t<uint4>(ctx, dst, src, sb / 16, db / 16, src_rows, dst_rows);
+    else if (cell == 8) launch_restride_t<long long>(ctx, dst, src, sr, dr, src_rows, dst_rows);
+    else launch_restride_t<int>(ctx, dst, src, sr, dr, src_rows, dst_rows);
+}
+
+// The same rows under more keys (the stride stays): a device copy and the tail zeroed.
+void grow_rows(jg_ctx* ctx, void* dst, const void* src, size_t old_bytes, size_t new_bytes) {
+    if (old_bytes) JG_HIP(hipMemcpyAsync(dst, src, old_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (new_bytes > old_bytes) JG_HIP(hipMemsetAsync((char*)dst + old_bytes, 0, new_bytes - old_bytes, ctx->stream));
+}
+
+void swap_buf(jg::DevBuf& a, jg::DevBuf& b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+    std::swap(a.own, b.own);
+}
+
 }  // namespace
 
 void jg::pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t* d_keys, uint64_t n_rows) {
     Groups g;
     launch_merge_indexed(p->ctx, p->eb, p->P.p, p->N.p, BP, BN, d_keys, n_rows, p->R, groups_of(p, n_rows, g));
+}
+
+// The store grown in place to [n_keys x n_replicas] (never shrunk).  Every new buffer is allocated before anything
+// is copied and the store's own fields change only after both streams have drained, so a failure at any point
+// leaves the store as it was (the new buffers are freed on the way out).  Takes no heed of an open wave: the
+// public entry point refuses those, the automatic widening runs inside one (pnc_auto_widen).
+void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
+    const uint64_t ok = p->n_keys, nk = std::max(n_keys, ok);
+    const uint32_t orr = p->R, nr = std::max(n_replicas, orr), eb = p->eb;
+    if (nk == ok && nr == orr) return;
+    JG_REQUIRE(nk <= 0xFFFFFFFFull, JG_EINVAL, "jg_pnc_reserve: key_idx is 32-bit (%llu keys)", (unsigned long long)nk);
+    JG_REQUIRE(nr < 0x40000000u, JG_EINVAL, "jg_pnc_reserve: at most 2^30-1 replica columns");  // k_restride's index arithmetic
+    JG_REQUIRE(!p->cols.p || nr <= jg::kMaxTableReplicas, JG_EINVAL, "jg_pnc_reserve: the replica table holds at most %u replicas per key (%u asked)",
+               jg::kMaxTableReplicas, nr);
+    JG_REQUIRE(nk * nr <= (1ull << 44), JG_ENOMEM, "jg_pnc_reserve: %llu x %u cells exceed any device", (unsigned long long)nk, nr);
+    jg_ctx* ctx = p->ctx;
+    jg::ensure_device(ctx);
+    const bool table = p->cols.p != nullptr;
+    static const bool trace = std::getenv("JANUS_TRACE_RESERVE") != nullptr;  // the call's phases to stderr
+    const auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    jg::DevBuf nP, nN, nC, nNc;  // all of them first: an allocation failure leaves the store untouched
+    nP.alloc((size_t)nk * nr * eb);
+    nN.alloc((size_t)nk * nr * eb);
+    if (table) {
+        nC.alloc((size_t)nk * nr * 16);
+        nNc.alloc((size_t)nk * 4);
+    }
+    if (nr == orr) {
+        grow_rows(ctx, nP.p, p->P.p, (size_t)ok * orr * eb, nP.bytes);
+        grow_rows(ctx, nN.p, p->N.p, (size_t)ok * orr * eb, nN.bytes);
+        if (table) grow_rows(ctx, nC.p, p->cols.p, (size_t)ok * orr * 16, nC.bytes);
+    } else {
+        launch_restride(ctx, eb, nP.p, p->P.p, orr, nr, ok, nk);
+        launch_restride(ctx, eb, nN.p, p->N.p, orr, nr, ok, nk);
+        if (table) launch_restride(ctx, 16, nC.p, p->cols.p, orr, nr, ok, nk);  // new slots all-zero (json_wave.hpp row_cache)
+    }
+    if (table) grow_rows(ctx, nNc.p, p->ncols.p, (size_t)ok * 4, nNc.bytes);
+    const double t1 = now();
+    // the old buffers go: everything queued on them first (an async merge_batch on `stream`, the upload stream)
+    JG_HIP(hipStreamSynchronize(ctx->stream));
+    JG_HIP(hipStreamSynchronize(ctx->copy));
+    const double t2 = now();
+    swap_buf(p->P, nP);
+    swap_buf(p->N, nN);
+    if (table) swap_buf(p->cols, nC), swap_buf(p->ncols, nNc);
+    if (nk != ok) p->head.release();  // the grouped merge's heads follow n_keys: first use recreates them (groups_of)
+    p->n_keys = nk;
+    p->R = nr;
+    if (trace) {
+        nP.release(), nN.release(), nC.release(), nNc.release();  // the old buffers (freed here or on the way out)
+        std::fprintf(stderr, "reserve %llu x %u -> %llu x %u: allocate + queue %.3f ms, copies %.3f ms, free %.3f ms\n", (unsigned long long)ok, orr,
+                     (unsigned long long)nk, nr, t1 - t0, t2 - t1, now() - t2);
+    }
+}
+
+// One step of the opt-in widening after a call failed for row capacity (its roll-back has run): R doubles, up to
+// the caller's bound and the replica table's.  false = at the bound (or no room on the device): the call's own
+// failure stands.
+bool jg::pnc_auto_widen(jg_pnc* p) {
+    uint64_t cap = p->max_R;
+    if (p->cols.p) cap = std::min<uint64_t>(cap, jg::kMaxTableReplicas);
+    const uint64_t nr = std::min<uint64_t>(2ull * p->R, cap);
+    if (nr <= p->R) return false;
+    try {
+        pnc_grow(p, p->n_keys, (uint32_t)nr);
+    } catch (const jg::Error&) {
+        return false;
+    }
+    return true;
 }
 
 extern "C" {
@@ -439,6 +590,34 @@ int jg_pnc_destroy(jg_pnc* p) {
         jg::ensure_device(p->ctx);
         JG_HIP(hipStreamSynchronize(p->ctx->stream));
         delete p;
+    });
+}
+
+int jg_pnc_shape(jg_pnc* p, uint64_t* n_keys, uint32_t* n_replicas, uint32_t* elem_bytes) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
+        check_store(p, "jg_pnc_shape");
+        if (n_keys) *n_keys = p->n_keys;
+        if (n_replicas) *n_replicas = p->R;
+        if (elem_bytes) *elem_bytes = p->eb;
+    });
+}
+
+int jg_pnc_reserve(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
+        jg::require_writable(p, "jg_pnc_reserve");
+        check_store(p, "jg_pnc_reserve");
+        JG_REQUIRE(!p->wopen, JG_EINVAL, "jg_pnc_reserve: a wave (jg_pnc_wave_begin) is open on this store");
+        jg::pnc_grow(p, n_keys, n_replicas);
+    });
+}
+
+int jg_pnc_set_max_replicas(jg_pnc* p, uint32_t max_replicas) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
+        check_store(p, "jg_pnc_set_max_replicas");
+        p->max_R = max_replicas;
     });
 }
 

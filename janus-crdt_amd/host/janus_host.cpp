@@ -102,7 +102,11 @@ void GpuStableStore::CreateSafeCRDT(const Guid& uid, CrdtType type, const Guid& 
     if (uids_.count(uid)) return;
     KeyRef kr{type, 0};
     if (type == CrdtType::PNCounter) {
-        if (next_row_ >= max_keys_) throw EngineError(JG_ESTATE, "PNCounter store full");
+        if (next_row_ >= max_keys_) {
+            // an elastic store (SetElastic) doubles its keys up to the limit, as CreateNewKVPair just adds one
+            if (max_keys_ >= max_keys_limit_) throw EngineError(JG_ESTATE, "PNCounter store full");
+            Reserve((uint32_t)std::min<uint64_t>(std::max<uint64_t>(2ull * max_keys_, 1), max_keys_limit_), R_);
+        }
         kr.idx = next_row_++;
         reg_rows_.push_back(kr.idx);  // {self: 0} — the row is zero already; column 0 once flushed
         reg_guids_.push_back(jg_guid{stableReplicaGuid.lo, stableReplicaGuid.hi});
@@ -114,6 +118,26 @@ void GpuStableStore::CreateSafeCRDT(const Guid& uid, CrdtType type, const Guid& 
     reg_uid_.push_back(jg_guid{uid.lo, uid.hi});  // safeCRDTsIndexedByuid[uid] (SafeCRDTManager.cs:73, 98)
     reg_type_.push_back(type == CrdtType::PNCounter ? 0 : 1);
     reg_idx_.push_back(kr.idx);
+}
+
+void GpuStableStore::sync_shape() {
+    uint64_t nk = 0;
+    uint32_t r = 0;
+    check(jg_pnc_shape(pnc_, &nk, &r, nullptr));
+    max_keys_ = (uint32_t)nk;
+    R_ = r;
+}
+
+void GpuStableStore::Reserve(uint32_t max_keys, uint32_t replicas) {
+    const int rc = jg_pnc_reserve(pnc_, max_keys, replicas);
+    const std::string why = rc == JG_OK ? std::string() : last_error();
+    sync_shape();
+    if (rc != JG_OK) throw EngineError(rc, why);
+}
+
+void GpuStableStore::SetElastic(uint32_t max_keys_limit, uint32_t max_replicas) {
+    check(jg_pnc_set_max_replicas(pnc_, max_replicas));
+    max_keys_limit_ = max_keys_limit;
 }
 
 void GpuStableStore::flush_registrations() {

@@ -146,6 +146,17 @@ class GpuStableStore {
     // PNCounter's own replica Guid takes column 0 with value 0 (PNCounters.cs:73-81).
     void CreateSafeCRDT(const Guid& uid, CrdtType type, const Guid& stableReplicaGuid = Guid{});
 
+    // The PN-Counter store grown in place to at least max_keys x replicas (jg_pnc_reserve; never shrinks).
+    void Reserve(uint32_t max_keys, uint32_t replicas);
+    // An elastic store, as the reference's Dictionaries are (KeySpaceManager.cs:121-136, PNCounters.cs:131-144):
+    // CreateSafeCRDT doubles the key capacity up to max_keys_limit instead of throwing "PNCounter store full", and
+    // the library widens the replica columns up to max_replicas where a state would run out of them
+    // (jg_pnc_set_max_replicas).  The bounds are the caller's guard against a faulty peer.  Never called: fixed.
+    void SetElastic(uint32_t max_keys_limit, uint32_t max_replicas);
+    // The PN-Counter store's shape now (jg_pnc_shape), which the automatic widening may have changed.
+    uint32_t MaxKeys() { sync_shape(); return max_keys_; }
+    uint32_t Replicas() { sync_shape(); return R_; }
+
     // HandleAfterConsensusUpdates (SafeCRDTManager.cs:109-160): the committed wave flattened in commit
     // order into the jg_commit arrays (uid, syncMsgType, identity, payload pointer + length) and applied by
     // ONE jg_apply_committed: unknown uids, ManagerMsg_Create and Guid.Empty skipped (:133-136), every state
@@ -359,7 +370,9 @@ class GpuStableStore {
     jg_pnc* pnc_ = nullptr;
     jg_orset* orset_ = nullptr;
     jg_node* node_ = nullptr;
+    void sync_shape();  // max_keys_ and R_ from jg_pnc_shape
     uint32_t max_keys_, R_, eb_;
+    uint32_t max_keys_limit_ = 0;  // SetElastic: CreateSafeCRDT may grow the keys up to this (0: fixed)
     uint32_t next_row_ = 0, next_set_ = 0;
     std::vector<uint32_t> reg_rows_;  // CreateSafeCRDT registrations not yet sent: PNC stable replica Guids
     std::vector<jg_guid> reg_guids_;

@@ -45,6 +45,7 @@ EXPORTS = [
     "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
     "jg_keyspace_new_keys", "jg_keyspace_lookup",
+    "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -163,6 +164,9 @@ _SIGS = {
     "jg_keyspace_receive": ([_vp, _u64, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(C.c_uint8), C.POINTER(_u64)], C.c_int),
     "jg_keyspace_new_keys": ([_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
     "jg_keyspace_lookup": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
+    "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
+    "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
 }
 GUID_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])  # jg_guid
 
@@ -293,8 +297,37 @@ class PNCStore:
     def __init__(self, ctx: Context, n_keys: int, n_replicas: int, elem_bytes: int = 8):
         self.ctx, self.n_keys, self.R, self.eb = ctx, n_keys, n_replicas, elem_bytes
         self.dtype = _elem_dtype(elem_bytes)
+        self._elastic = False
         self._h = _vp()
         _check(load().jg_pnc_create(ctx.handle, n_keys, n_replicas, elem_bytes, C.byref(self._h)))
+
+    # ---- elastic shape (jg_pnc_reserve / jg_pnc_set_max_replicas) ----
+    def shape(self):
+        """(n_keys, n_replicas, elem_bytes) as the library holds them (jg_pnc_shape); refreshes n_keys and R."""
+        nk, r, eb = _u64(0), _u32(0), _u32(0)
+        _check(load().jg_pnc_shape(self._h, C.byref(nk), C.byref(r), C.byref(eb)))
+        self.n_keys, self.R = int(nk.value), int(r.value)
+        return self.n_keys, self.R, int(eb.value)
+
+    def reserve(self, n_keys: int = 0, n_replicas: int = 0) -> None:
+        """Grow the store in place to at least this shape (jg_pnc_reserve); never shrinks."""
+        try:
+            _check(load().jg_pnc_reserve(self._h, n_keys, n_replicas))
+        finally:
+            self.shape()
+
+    def set_max_replicas(self, max_replicas: int) -> None:
+        """Let a call that runs out of columns widen the store up to max_replicas (0 = fixed shape)."""
+        _check(load().jg_pnc_set_max_replicas(self._h, max_replicas))
+        self._elastic = max_replicas > 0
+
+    def _widened(self, rc, bad_msg=None) -> None:
+        # after a call that may have widened the store: n_keys / R size read_rows' and columns' buffers
+        try:
+            _check(rc, bad_msg)  # first: the next call clears the library's error text
+        finally:
+            if self._elastic:
+                self.shape()
 
     def _rows(self, P, N):
         P, N = _arr(P, self.dtype), _arr(N, self.dtype)
@@ -308,6 +341,8 @@ class PNCStore:
         _check(load().jg_pnc_write_rows(self._h, _ptr(k), n, _ptr(P), _ptr(N)))
 
     def read_rows(self, key_idx=None, n: int | None = None):
+        if self._elastic:  # a node wave (Node.apply_*) may have widened the store since
+            self.shape()
         k = None if key_idx is None else _arr(key_idx, np.uint32)
         n = (self.n_keys if n is None else n) if k is None else k.size
         P = np.empty((n, self.R), self.dtype)
@@ -349,11 +384,13 @@ class PNCStore:
         g = np.empty(k.size, GUID_DTYPE)
         g["lo"], g["hi"] = lo, hi
         out = np.empty(k.size, np.uint32)
-        _check(load().jg_pnc_intern(self._h, k.size, _ptr(k), _ptr(g), _ptr(out)))
+        self._widened(load().jg_pnc_intern(self._h, k.size, _ptr(k), _ptr(g), _ptr(out)))
         return out
 
     def columns(self, key_idx):
         """(guids [n x R] of GUID_DTYPE, ncols [n])."""
+        if self._elastic:
+            self.shape()
         k = _arr(key_idx, np.uint32)
         g = np.zeros((k.size, self.R), GUID_DTYPE)
         n = np.empty(k.size, np.uint32)
@@ -369,7 +406,7 @@ class PNCStore:
         bad = _u64(0)
         rc = load().jg_pnc_merge_json(self._h, k.size, _ptr(k), _ptr(off), _ptr(data) if data.size else _ptr(np.zeros(16, np.uint8)),
                                       C.byref(bad))
-        _check(rc, bad.value)
+        self._widened(rc, bad.value)
 
     # streamed wave: begin, append chunks (their buffers are kept alive here until commit/abort)
     def wave_begin(self, cap_msgs: int = 0, cap_bytes: int = 0) -> None:
@@ -387,7 +424,7 @@ class PNCStore:
         bad = _u64(0)
         rc = load().jg_pnc_wave_commit(self._h, C.byref(bad))
         self._chunks = []
-        _check(rc, bad.value)
+        self._widened(rc, bad.value)
 
     def wave_abort(self) -> None:
         _check(load().jg_pnc_wave_abort(self._h))
@@ -450,7 +487,7 @@ class PNCStore:
     def merge_wave(self, wave: "Wave") -> None:
         bad = _u64(0)
         rc = load().jg_pnc_merge_wave(self._h, wave._h, C.byref(bad))
-        _check(rc, bad.value)
+        self._widened(rc, bad.value)
 
     def close(self) -> None:
         if self._h:
