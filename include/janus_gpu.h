@@ -643,9 +643,12 @@ int jg_keyspace_create_keys(jg_keyspace* ks, uint64_t n, const uint64_t* off, co
  * message (jg_tpset_merge_json's contract per message, mode included; each message is one merge on the device, so
  * many small states in one call cost one round of launches each).  OnNext takes LookupAll().Except(LastKeySpaceSet):
  * an entry is SEEN by the OnNext of the message that added it unless that message or an earlier one put it in
- * removeSet; a removal by a later message does not unsee it.  For each seen entry, in ordinal order: key = the
- * bytes before the first NUL, guid = the segment between the first and the second NUL (Split("\0")[1]) in "D" form
- * of either case; a key the dictionary lacks is added with that guid (the first entry wins) and journalled.
+ * removeSet; a removal by a later message does not unsee it.  For each seen entry, in ordinal order and in the
+ * reference's order of evaluation (:163-166): key = the bytes before the first NUL (the whole entry if it has none);
+ * if the dictionary holds that key - from jg_keyspace_create_keys, an earlier message or an earlier entry of the same
+ * OnNext - nothing happens, whatever the rest of the entry looks like; else guid = the segment between the first and
+ * the second NUL (Split("\0")[1]) in "D" form of either case, and the key is added with that guid (the first entry
+ * wins) and journalled.
  * A message Decode / Merge rejects stops the call as in jg_tpset_merge_json (JG_EINVAL, *bad_msg, *partial; its
  * OnNext does not run: entries a partial merge added are seen by the next message's OnNext).  *n_new = journal
  * records this call appended.  JG_ESTATE from the dictionary or the journal (neither can fill before the set does)
@@ -655,13 +658,16 @@ int jg_keyspace_create_keys(jg_keyspace* ks, uint64_t n, const uint64_t* off, co
  * (IndexOutOfRangeException), with a guid segment Guid.Parse rejects (FormatException) or on the null element (NRE),
  * before LastKeySpaceSet advances, and so wedges on that entry at every later message; Guid.Parse also accepts forms
  * other than "D", which an honest node never writes.  Here such an entry is journalled with a status, not added to
- * the dictionary, and processing goes on; only the "D" form is a guid. */
+ * the dictionary, and processing goes on; only the "D" form is a guid.  The departure covers only entries on which the
+ * reference throws: a NUL-less or bad-guid entry of a key the dictionary holds is skipped there and here alike; one of
+ * an unknown key adds nothing, so a later well-formed entry of that key still wins; the null element is dereferenced
+ * before any lookup and is journalled (status 3) whatever the dictionary holds. */
 int jg_keyspace_receive(jg_keyspace* ks, uint64_t n, const uint64_t* off, const uint8_t* bytes, uint32_t mode, uint64_t* bad_msg, uint8_t* partial,
                         uint64_t* n_new);
 /* The journal of OnNext's outcomes since record `from`, in the style of jg_orset_names_since: records [from, *to)
  * with *to = the journal's length now; record i - from = bytes[off[i], off[i+1]), guid[i], status[i]: 0 = key added
  * (bytes = the key); 1 = the entry has no NUL; 2 = its guid segment is not in "D" form; 3 = the null element (1-3:
- * bytes = the raw entry, guid zero, nothing added).  off / bytes / guid / status all NULL = size query (*to,
+ * bytes = the raw entry, guid zero, nothing added; 1 and 2 only for a key the dictionary lacked at that entry).  off / bytes / guid / status all NULL = size query (*to,
  * *n_bytes); else *n_bytes holds bytes' capacity on entry (JG_ESTATE if short) and off has *to - from + 1 entries. */
 int jg_keyspace_new_keys(jg_keyspace* ks, uint64_t from, uint64_t* to, uint64_t* n_bytes, uint64_t* off, uint8_t* bytes, jg_guid* guid, uint8_t* status);
 /* keySpaces[key] (GetKeySpace, KeySpaceManager.cs:99-110): found[i], guid[i] (zero when absent). */

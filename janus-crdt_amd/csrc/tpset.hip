@@ -1479,8 +1479,8 @@ struct Dict {
     uint32_t *sid, *klen;
     ull *glo, *ghi, *key;
 };
-struct Items {  // one dictionary candidate per item, in order
-    uint32_t *sid, *klen, *slot, *prep, *pmin;
+struct Items {  // one dictionary candidate per item, in order; klen = the key's bytes, rlen = the bytes its journal record copies
+    uint32_t *sid, *klen, *rlen, *slot, *prep, *pmin;
     ull *glo, *ghi, *key;
     uint8_t *status, *valid;
     uint64_t pmask, n;
@@ -1501,14 +1501,16 @@ __device__ uint32_t dict_find(const Store& S, const Dict& D, ull key, const uint
 }
 
 // OnNext's body per new entry (KeySpaceManager.cs:160-172), entry = add[from + i]: seen iff not in removeSet; key =
-// the bytes before the first NUL, guid = the segment up to the second NUL in "D" form.  status as jg_keyspace_new_keys.
+// the bytes before the first NUL (the whole entry if it has none), guid = the segment up to the second NUL in "D" form.
+// status is what jg_keyspace_new_keys reports if the key turns out unknown (k_ks_find / k_ks_win decide that); a
+// malformed entry carries its key's hash and length as well, since ContainsKey (:164) comes before Guid.Parse (:166).
 __global__ void k_ks_parse(Store S, uint64_t from, Items I) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= I.n) return;
     const uint32_t id = S.add[from + i];
     I.sid[i] = id, I.slot[i] = kNone, I.glo[i] = I.ghi[i] = 0, I.key[i] = 0;
     if (id == kNullId) {
-        I.valid[i] = S.nulls[1] == kNone, I.status[i] = 3, I.klen[i] = 0;
+        I.valid[i] = S.nulls[1] == kNone, I.status[i] = 3, I.klen[i] = I.rlen[i] = 0;
         return;
     }
     I.valid[i] = S.srem[id] == kNone;
@@ -1516,17 +1518,18 @@ __global__ void k_ks_parse(Store S, uint64_t from, Items I) {
     const uint32_t len = S.slen[id];
     uint32_t p1 = 0;
     while (p1 < len && s[p1]) ++p1;
+    I.klen[i] = p1, I.rlen[i] = len, I.key[i] = key_hash(s, p1, S.salt);
     if (p1 == len) {
-        I.status[i] = 1, I.klen[i] = len;
+        I.status[i] = 1;
         return;
     }
     jgw::GuidSink g;
     for (uint32_t p = p1 + 1; p < len && s[p]; ++p) g.put(s[p]);
     if (!g.ok()) {
-        I.status[i] = 2, I.klen[i] = len;
+        I.status[i] = 2;
         return;
     }
-    I.status[i] = 0, I.klen[i] = p1, I.glo[i] = g.lo(), I.ghi[i] = g.hi, I.key[i] = key_hash(s, p1, S.salt);
+    I.status[i] = 0, I.rlen[i] = p1, I.glo[i] = g.lo(), I.ghi[i] = g.hi;
 }
 
 // CreateNewKVPair's TryAdd (:130): item i = key i of the batch, found as the prefix of its entry in the set
@@ -1537,12 +1540,12 @@ __global__ void k_ks_local(Store S, const uint8_t* __restrict__ ent, const ull* 
     const uint8_t* e = ent + eoff[i];
     const uint32_t len = (uint32_t)(eoff[i + 1] - eoff[i]);
     I.sid[i] = store_find(S, key_hash(e, len, S.salt), e, len);  // the Add before this launch put it there
-    I.klen[i] = klen[i], I.slot[i] = kNone, I.glo[i] = guid[i].lo, I.ghi[i] = guid[i].hi;
+    I.klen[i] = I.rlen[i] = klen[i], I.slot[i] = kNone, I.glo[i] = guid[i].lo, I.ghi[i] = guid[i].hi;
     I.key[i] = key_hash(e, klen[i], S.salt);
     I.status[i] = 0, I.valid[i] = 1;
 }
 
-// first wins: among the items whose key the dictionary lacks, the smallest index per distinct key
+// first wins: among the well-formed items whose key the dictionary lacks, the smallest index per distinct key
 __global__ void k_ks_find(Store S, Dict D, Items I) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= I.n || !I.valid[i] || I.status[i]) return;
@@ -1563,13 +1566,31 @@ __global__ void k_ks_find(Store S, Dict D, Items I) {
         }
     }
 }
-// added = the item puts its key into the dictionary; jrn = it is journalled (an added key, or a malformed entry)
-__global__ void k_ks_win(Items I, uint32_t* __restrict__ added, uint32_t* __restrict__ jrn) {
+// added = the item puts its key into the dictionary; jrn = it is journalled: an added key, the null element, or a
+// malformed entry whose key is unknown when its turn comes, i.e. neither in the dictionary nor added by a well-formed
+// item before it (the minima stand: k_ks_find has ended, the call-wide table is only read here)
+__global__ void k_ks_win(Store S, Dict D, Items I, uint32_t* __restrict__ added, uint32_t* __restrict__ jrn) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= I.n) return;
     const bool a = I.slot[i] != kNone && I.pmin[I.slot[i]] == i;
     added[i] = a;
-    jrn[i] = I.valid[i] && (a || I.status[i] != 0);
+    bool j = a;
+    if (I.valid[i] && I.status[i] == 3) j = true;
+    else if (I.valid[i] && I.status[i] != 0) {
+        const uint8_t* k = S.pool + S.soff[I.sid[i]];
+        const uint32_t klen = I.klen[i];
+        j = dict_find(S, D, I.key[i], k, klen) == kNone;
+        for (uint64_t slot = I.key[i] & I.pmask; j; slot = (slot + 1) & I.pmask) {
+            const uint32_t r = I.prep[slot];
+            if (r == 0) break;
+            const uint32_t o = r - 1;
+            if (I.key[o] == I.key[i] && I.klen[o] == klen && same_bytes(S.pool + S.soff[I.sid[o]], k, klen)) {
+                j = I.pmin[slot] > i;
+                break;
+            }
+        }
+    }
+    jrn[i] = j;
 }
 __global__ void k_ks_commit(Dict D, Items I, const uint32_t* __restrict__ added, const ull* __restrict__ oa, uint64_t n_keys, const uint32_t* __restrict__ jrn,
                             const ull* __restrict__ oj, uint64_t jn, uint32_t* __restrict__ jsid, uint32_t* __restrict__ jlen, ull* __restrict__ jglo,
@@ -1584,7 +1605,7 @@ __global__ void k_ks_commit(Dict D, Items I, const uint32_t* __restrict__ added,
     }
     if (jsid && jrn[i]) {
         const ull j = jn + oj[i];
-        jsid[j] = I.sid[i], jlen[j] = I.klen[i], jglo[j] = I.glo[i], jghi[j] = I.ghi[i], jstatus[j] = I.status[i];
+        jsid[j] = I.sid[i], jlen[j] = I.rlen[i], jglo[j] = I.glo[i], jghi[j] = I.ghi[i], jstatus[j] = I.status[i];
     }
 }
 
@@ -1634,7 +1655,7 @@ void items_layout(Carve& cv, uint64_t n, ItemBufs& B) {
     uint64_t slots = 64;
     while (slots < 2 * n) slots <<= 1;
     Items& I = B.I;
-    I.sid = cv.take<uint32_t>(n), I.klen = cv.take<uint32_t>(n), I.slot = cv.take<uint32_t>(n), I.prep = cv.take<uint32_t>(slots), I.pmin = cv.take<uint32_t>(slots);
+    I.sid = cv.take<uint32_t>(n), I.klen = cv.take<uint32_t>(n), I.rlen = cv.take<uint32_t>(n), I.slot = cv.take<uint32_t>(n), I.prep = cv.take<uint32_t>(slots), I.pmin = cv.take<uint32_t>(slots);
     I.glo = cv.take<ull>(n), I.ghi = cv.take<ull>(n), I.key = cv.take<ull>(n), I.status = cv.take<uint8_t>(n), I.valid = cv.take<uint8_t>(n);
     I.pmask = slots - 1, I.n = n;
     B.added = cv.take<uint32_t>(n), B.jrn = cv.take<uint32_t>(n), B.oa = cv.take<ull>(n + 1), B.oj = cv.take<ull>(n + 1);
@@ -1649,7 +1670,7 @@ uint64_t dict_insert(jg_keyspace* ks, ItemBufs& B, bool journal, uint8_t* added_
     JG_HIP(hipMemsetAsync(B.I.prep, 0, slots * 4, st));
     JG_HIP(hipMemsetAsync(B.I.pmin, 0xFF, slots * 4, st));
     hipLaunchKernelGGL(k_ks_find, dim3(g), dim3(kBlock), 0, st, s->view(), ks->dict(), B.I);
-    hipLaunchKernelGGL(k_ks_win, dim3(g), dim3(kBlock), 0, st, B.I, B.added, B.jrn);
+    hipLaunchKernelGGL(k_ks_win, dim3(g), dim3(kBlock), 0, st, s->view(), ks->dict(), B.I, B.added, B.jrn);
     excl_scan(s, B.added, B.oa, n);
     excl_scan(s, B.jrn, B.oj, n);
     JG_HIP(hipGetLastError());

@@ -149,10 +149,12 @@ inline int MergeJson(TPSet& set, std::string_view msg) {
 }
 
 // KeySpaceManager: the key-space CRDT, keySpaces (:30) and LastKeySpaceSet (:35).  Receive = the CRDT's
-// ApplySynchronizedUpdate followed by OnNext (:151-178).  Stated departure from the reference, which throws out of
-// OnNext (and so wedges) there: an entry without a NUL (status 1), with a guid segment not in "D" form (2), or the null
-// element (3) is journalled with its raw bytes, not added, and processing goes on.  tests/tpset_ref.py KeySpaceRef is
-// the same in Python.
+// ApplySynchronizedUpdate followed by OnNext (:151-178), in the reference's order: the null element first (it is
+// dereferenced before any lookup), then ContainsKey of the bytes before the first NUL (the whole entry if it has none):
+// an entry of a key the dictionary holds is skipped whatever the rest of it looks like.  Stated departure from the
+// reference, which throws out of OnNext (and so wedges) there: an entry of an unknown key without a NUL (status 1) or
+// with a guid segment not in "D" form (2), and the null element (3), is journalled with its raw bytes, not added, and
+// processing goes on.  tests/tpset_ref.py KeySpaceRef is the same in Python.
 class KeySpace {
   public:
     struct Record {
@@ -179,6 +181,8 @@ class KeySpace {
                 continue;
             }
             const size_t p1 = e->find('\0');
+            const std::string key = e->substr(0, p1);
+            if (keys_.count(key) != 0) continue;  // :164 ContainsKey first: Split(...)[1] and Guid.Parse never run
             if (p1 == std::string::npos) {
                 journal_.push_back({*e, {}, 1});
                 continue;
@@ -189,8 +193,8 @@ class KeySpace {
                 journal_.push_back({*e, {}, 2});
                 continue;
             }
-            const std::string key = e->substr(0, p1);
-            if (keys_.emplace(key, g).second) journal_.push_back({key, g, 0});
+            keys_.emplace(key, g);
+            journal_.push_back({key, g, 0});
         }
         last_.clear();
         last_null_ = false;

@@ -1,10 +1,12 @@
 """GPU: KeySpaceManager's state on the device (jg_keyspace_*) against its restatement (tests/tpset_ref.py KeySpaceRef),
-whose OnNext runs message by message with the documented departure for malformed entries."""
+whose OnNext runs message by message, in the reference's order (ContainsKey before Guid.Parse), with the documented
+departure for malformed entries of unknown keys."""
 import numpy as np
 import pytest
 
 import janus_gpu as jg
 import tpset_ref as R
+from test_tpset import ORDER_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -94,7 +96,7 @@ def test_rejected_and_partial_messages(ctx):
     assert [r[0] for r in ref.journal] == [b"a", b"b", b"c"]
 
 
-def test_journal_paging_and_random_parity(ctx):
+def journal_paging_and_random_parity(ctx):
     rng = np.random.default_rng(9)
     keys = [b"key%03d" % i for i in range(60)] + [b"", "ключ€".encode()]
     ref = R.KeySpaceRef()
@@ -123,6 +125,20 @@ def test_journal_paging_and_random_parity(ctx):
             assert (page, to) == (ref.journal[f:], len(ref.journal))
         with pytest.raises(jg.JanusError):
             ks.new_keys(len(ref.journal) + 1)
+
+
+def test_journal_paging_and_random_parity(ctx):
+    journal_paging_and_random_parity(ctx)
+
+
+@pytest.mark.parametrize("name", list(ORDER_CASES))
+def test_known_key_is_skipped_before_its_guid_is_parsed(ctx, name):
+    """KeySpaceManager.cs:163-166: ContainsKey comes before Split(...)[1] and Guid.Parse.  The cases and their
+    journals, worked out by hand, are test_tpset.ORDER_CASES; the known key comes from create_keys, from an earlier
+    call, from an earlier message of the call and from an earlier entry of the message."""
+    steps, journal, keys = ORDER_CASES[name]
+    ref = both(ctx, steps, probe=(b"nokey", b"", b"k", b"u", b"w", b"r", b"new"))
+    assert ref.journal == journal and ref.keys == keys
 
 
 def test_kat_keyspace_binary():

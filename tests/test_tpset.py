@@ -153,7 +153,8 @@ def test_cpp_restatement_agrees_byte_for_byte():
 
 
 def test_cpp_key_space_restatement_agrees():
-    """host/tpset_ref.hpp's KeySpace (CreateNewKVPair, Receive = Merge + OnNext with the documented departure) and
+    """host/tpset_ref.hpp's KeySpace (CreateNewKVPair, Receive = Merge + OnNext in the reference's order, ContainsKey
+    before Guid.Parse, with the documented departure for malformed entries of unknown keys) and
     tests/tpset_ref.py's KeySpaceRef give the same verdicts, TryAdd results, journals and sets on random histories with
     repeated keys, removals, upper-case guids, malformed entries, the null element and rejected messages."""
     import subprocess
@@ -195,3 +196,81 @@ def test_cpp_key_space_restatement_agrees():
     out = subprocess.run([str(exe)], input="\n".join(script) + "\n", capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr
     assert out.stdout.split("\n")[:-1] == expect
+
+
+# ---- OnNext's order (KeySpaceManager.cs:160-172): ContainsKey(item.Split("\0")[0]) comes before Split(...)[1] and
+# Guid.Parse, so an entry of a key the dictionary holds is skipped whatever the rest of it looks like.  Each case is
+# (steps in the form test_keyspace_gpu.both() takes, the journal, the dictionary), the last two worked out by hand from
+# those lines (with the stated departure: where the reference throws, a record with status 1 / 2 / 3 and no add).
+_A, _B, _C, _D = (0x0123456789ABCDEF, 0x1122334455667788), (2, 3), (0xFFFFFFFFFFFFFFFF, 0), (0, 0)
+_DA, _DB, _DC = b"89abcdef-4567-0123-8877-665544332211", b"00000002-0000-0000-0300-000000000000", b"ffffffff-ffff-ffff-0000-000000000000"
+_OK = (None, False)
+
+
+def _m(add, rem=()):
+    return R.encode_msg(list(add), list(rem))
+
+
+ORDER_CASES = {
+    # both malformed entries are of known keys, and new\0zz comes after new was added: one record where status-first gives four
+    "four_entries_one_record": (
+        [("create", [(b"mine", _A), (b"nonul", _B)]),
+         ("receive", [_m([b"mine\0not-a-guid", b"nonul", b"new\0" + _DC, b"new\0zz"])], _OK)],
+        [(b"new", _C, 0)], {b"mine": _A, b"nonul": _B, b"new": _C}),
+    "known_from_create_keys": (
+        [("create", [(b"k", _A)]),
+         ("receive", [_m([b"k", b"k\0", b"k\0{" + _DB + b"}", b"k\0" + _DB])], _OK)],
+        [], {b"k": _A}),
+    "known_from_an_earlier_call": (
+        [("receive", [_m([b"k\0" + _DA])], _OK),
+         ("receive", [_m([b"k", b"k\0zz"]), _m([b"k\0" + _DB[:-1]])], _OK)],
+        [(b"k", _A, 0)], {b"k": _A}),
+    "known_from_an_earlier_message_of_the_call": (
+        [("receive", [_m([b"k\0" + _DA]), _m([b"k", b"k\0zz"])], _OK)],
+        [(b"k", _A, 0)], {b"k": _A}),
+    "known_from_an_earlier_entry_of_the_message": (
+        [("receive", [_m([b"k\0" + _DA.upper(), b"k", b"k\0zz", b"k\0" + _DB])], _OK)],
+        [(b"k", _A, 0)], {b"k": _A}),
+    # a malformed entry adds nothing, so the key is still unknown when its good entry comes
+    "malformed_then_good": (
+        [("receive", [_m([b"u\0zz", b"u\0" + _DA])], _OK)],
+        [(b"u\0zz", (0, 0), 2), (b"u", _A, 0)], {b"u": _A}),
+    "good_then_malformed": (
+        [("receive", [_m([b"u\0" + _DA, b"u\0zz"])], _OK)],
+        [(b"u", _A, 0)], {b"u": _A}),
+    "no_nul_twice_then_good_then_more": (
+        [("receive", [_m([b"w", b"w\0yy", b"w\0" + _DB, b"w\0xx"]), _m([b"w\0ww"])], _OK)],
+        [(b"w", (0, 0), 1), (b"w\0yy", (0, 0), 2), (b"w", _B, 0)], {b"w": _B}),
+    # an entry its own message removes is never seen: it makes nothing known
+    "a_removed_good_entry_adds_nothing": (
+        [("receive", [_m([b"r\0" + _DA, b"r\0zz"], [b"r\0" + _DA])], _OK)],
+        [(b"r\0zz", (0, 0), 2)], {}),
+    # the null element is dereferenced (item.Split) before any lookup: status 3 whatever the dictionary holds
+    "null_with_the_empty_key_unknown": (
+        [("receive", [_m([None, b""])], _OK)],
+        [(b"", (0, 0), 3), (b"", (0, 0), 1)], {}),
+    "null_with_the_empty_key_known": (
+        [("create", [(b"", _A)]),
+         ("receive", [_m([None, b"", b"\0zz"])], _OK)],
+        [(b"", (0, 0), 3)], {b"": _A}),
+    # the all-zero guid is a valid "D" form
+    "zero_guid_then_malformed": (
+        [("receive", [_m([b"z\0" + b"00000000-0000-0000-0000-000000000000", b"z"])], _OK)],
+        [(b"z", _D, 0)], {b"z": _D}),
+}
+
+
+def test_guid_literals():
+    assert (R.guid_d(_A), R.guid_d(_B), R.guid_d(_C)) == (_DA, _DB, _DC)
+
+
+def test_on_next_looks_the_key_up_before_it_parses_the_guid():
+    for name, (steps, journal, keys) in ORDER_CASES.items():
+        ref = R.KeySpaceRef()
+        for st in steps:
+            if st[0] == "create":
+                ref.create_keys(st[1])
+            else:
+                assert ref.receive(st[1]) == st[2], name
+        assert ref.journal == journal, name
+        assert ref.keys == keys, name

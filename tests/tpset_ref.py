@@ -13,13 +13,20 @@ removeSet is missing or null applies its addSet and stops the call (`partial`).
 """
 from __future__ import annotations
 
+import re
+
 MAX_DEPTH = 64
 _TWO = {0x5C: b"\\\\", 0x08: b"\\b", 0x09: b"\\t", 0x0A: b"\\n", 0x0C: b"\\f", 0x0D: b"\\r"}
 _U16 = set(b"\"&'+<>`") | {0x7F} | set(range(0x20))
+_ASCII = {c: _TWO.get(c) or b"\\u%04X" % c for c in set(_TWO) | _U16}
+_RUN = re.compile(rb'[^"\\\x00-\x1f\x80-\xff]*').match
+_ASCII_SUB = re.compile(b"[" + b"".join(b"\\x%02x" % c for c in sorted(_ASCII)) + b"]").sub
 
 
 def escape(s: bytes) -> bytes:
     """JavaScriptEncoder.Default over well-formed UTF-8 (oracle/json.hpp EscapeTo)."""
+    if s.isascii():  # the same two tables in one pass: what keeps a large state's encoding quick
+        return _ASCII_SUB(lambda m: _ASCII[m.group()[0]], s)
     o = bytearray()
     for ch in s.decode("utf-8"):
         cp = ord(ch)
@@ -93,6 +100,9 @@ class _Reader:
         self.expect(b'"')
         s, o = self.s, bytearray()
         while True:
+            run = _RUN(s, self.p).end()  # ASCII that stands for itself, in one step
+            o += s[self.p:run]
+            self.p = run
             if self.p >= len(s):
                 self.fail("unterminated string")
             c = s[self.p]
@@ -174,7 +184,6 @@ class _Reader:
             if self.s[self.p:self.p + len(lit)] == lit:
                 self.p += len(lit)
                 return
-        import re
         m = re.compile(rb"-?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)?").match(self.s, self.p)
         if not m:
             self.fail("not a value")
@@ -317,9 +326,12 @@ def parse_guid_d(s: bytes):
 
 class KeySpaceRef:
     """The key-space CRDT, keySpaces and LastKeySpaceSet, with OnNext (:151-178) run after every merged message.
-    Stated departure from the reference, which throws out of OnNext (and so wedges) on such entries: an entry without
-    a NUL (status 1), with a guid segment not in "D" form (2) or the null element (3) is journalled with its raw
-    bytes, not added, and processing goes on."""
+    In the reference's order: the null element first (it is dereferenced before any lookup), then ContainsKey of the
+    bytes before the first NUL (the whole entry if it has none) - an entry of a key the dictionary holds is skipped
+    whatever the rest of it looks like - and only then Split(...)[1] and Guid.Parse.
+    Stated departure from the reference, which throws out of OnNext (and so wedges) on such entries: an entry of an
+    unknown key without a NUL (status 1) or with a guid segment not in "D" form (2), and the null element (3), is
+    journalled with its raw bytes, not added, and processing goes on."""
 
     def __init__(self):
         self.set = TPSetRef()
@@ -344,13 +356,15 @@ class KeySpaceRef:
                 self.journal.append((b"", (0, 0), 3))
                 continue
             parts = x.split(b"\0")
+            if parts[0] in self.keys:  # :164 ContainsKey comes first: Split(...)[1] and Guid.Parse never run
+                continue
             if len(parts) < 2:
                 self.journal.append((x, (0, 0), 1))
                 continue
             guid = parse_guid_d(parts[1])
             if guid is None:
                 self.journal.append((x, (0, 0), 2))
-            elif parts[0] not in self.keys:
+            else:
                 self.keys[parts[0]] = guid
                 self.journal.append((parts[0], guid, 0))
         self.last = set(now)
