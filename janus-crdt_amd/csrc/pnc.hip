@@ -4,9 +4,11 @@
 // reference's `int`, int64 = the BASELINE variant).  Row = interned key, column = interned replica.
 //
 // Kernels and their roofline (HBM):
-//   k_merge_dense    A = max(A, B) over identity rows.  Reads A.P A.N B.P B.N, writes A.P A.N:
-//                    6 x elem_bytes per cell (48 B at int64).  One 16-B vector per array per lane,
-//                    non-temporal.  This is PNCounter.Merge (PNCounters.cs:131-144).
+//   k_merge_dense    A = max(A, B) over identity rows.  Reads A.P A.N B.P B.N: 4 x elem_bytes per cell
+//                    (32 B at int64), and writes back only the 128-B lines of A.P / A.N that a cell of B
+//                    raised: up to 2 x elem_bytes more (48 B per cell when every line changes, 32 B for a
+//                    re-delivered batch).  One 16-B vector per array per lane, non-temporal.  This is
+//                    PNCounter.Merge (PNCounters.cs:131-144).
 //   k_merge_indexed  scatter-max of received rows into their keys (atomicMax: rows may repeat a
 //                    key inside one committed batch, SafeCRDTManager.cs:122-146).
 //   k_apply_ops      Increment/Decrement (PNCounters.cs:97-112): wrapping atomic adds.
@@ -52,28 +54,50 @@ template <int EB> struct Elem;
 template <> struct Elem<4> { using T = int; };
 template <> struct Elem<8> { using T = long long; };
 
+// True where the two vectors differ in any bit.
+__device__ __forceinline__ bool differs(uint4 a, uint4 b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0; }
+
+// Store elision (merge kernels): max is idempotent and most merges are no-ops for most cells (a replica advances
+// its own column only, every message is a full state, anti-entropy re-delivers merged states), so a vector of A
+// is stored only if its aligned group of kElideLanes lanes holds a lane whose maximum differs from what it loaded:
+// 8 lanes x 16 B = one 128-B line where the lanes' vectors are consecutive and the group's first is line-aligned
+// (k_merge_dense always; k_merge_grouped where the row is a multiple of 128 B), so a line is written whole or
+// not at all.  Granularity measured against per-lane (16 B) and per-wave (1 KB) elision over 0 - 100 % changed
+// cells (tools/tune_pnc.hip, profiles/r07/tune_pnc_elide.txt).  Correctness rests on neither grouping nor
+// alignment: a lane that stores writes the maximum, a lane that skips held an unchanged value.  `mask` is the
+// wave's ballot of changed lanes (inactive lanes read as unchanged).
+constexpr uint32_t kElideLanes = 8;
+__device__ __forceinline__ bool group_changed(unsigned long long mask, uint32_t lane) {
+    return ((mask >> (lane & (64 - kElideLanes))) & ((1u << kElideLanes) - 1)) != 0;
+}
+
 // Dense merge: nv 16-byte vectors per array, one vector of each array per lane, plus `tail` trailing
 // cells (< 16 B) done by block 0.  Measured on MI355X against grid-stride / multi-vector-per-lane /
 // block-chunk variants (tools/tune_pnc.hip, profiles/r01/tune_pnc_*.txt): a flat grid with one
-// vector per lane and non-temporal loads/stores (every byte is touched once) was fastest.
+// vector per lane and non-temporal loads/stores (every byte is touched once) was fastest.  P and N are
+// elided separately (a batch that only raises P leaves N unwritten); the bounds test is a predicate, not a
+// branch around the ballots, so every lane of a wave that loaded data votes (lanes past nv vote unchanged).
 template <int EB>
 __global__ __launch_bounds__(kBlock) void k_merge_dense(uint4* __restrict__ AP, uint4* __restrict__ AN,
                                                         const uint4* __restrict__ BP, const uint4* __restrict__ BN,
                                                         uint64_t nv, uint32_t tail) {
     using T = typename Elem<EB>::T;
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < nv) {
-        const uint4 ap = nt_load(AP + i), bp = nt_load(BP + i), an = nt_load(AN + i), bn = nt_load(BN + i);
-        nt_store(AP + i, vmax<EB>(ap, bp));
-        nt_store(AN + i, vmax<EB>(an, bn));
-    }
+    const bool in = i < nv;
+    uint4 ap{}, bp{}, an{}, bn{};
+    if (in) ap = nt_load(AP + i), bp = nt_load(BP + i), an = nt_load(AN + i), bn = nt_load(BN + i);
+    const uint4 mp = vmax<EB>(ap, bp), mn = vmax<EB>(an, bn);
+    const unsigned long long cp = __ballot(in && differs(mp, ap)), cn = __ballot(in && differs(mn, an));
+    const uint32_t lane = threadIdx.x & 63;
+    if (in && group_changed(cp, lane)) nt_store(AP + i, mp);
+    if (in && group_changed(cn, lane)) nt_store(AN + i, mn);
     if (blockIdx.x == 0 && threadIdx.x < tail) {
         T* ap = reinterpret_cast<T*>(AP + nv) + threadIdx.x;
         T* an = reinterpret_cast<T*>(AN + nv) + threadIdx.x;
         const T bp = reinterpret_cast<const T*>(BP + nv)[threadIdx.x];
         const T bn = reinterpret_cast<const T*>(BN + nv)[threadIdx.x];
-        *ap = *ap > bp ? *ap : bp;
-        *an = *an > bn ? *an : bn;
+        if (bp > *ap) *ap = bp;
+        if (bn > *an) *an = bn;
     }
 }
 
@@ -121,7 +145,8 @@ __global__ __launch_bounds__(kBlock) void k_merge_indexed_rows(typename Elem<EB>
 // key's rows into a list: next[m] = the key's previous head, head[key] = gen << 32 | m (one atomicExch per
 // row).  Pass 2 (k_merge_grouped): the head row of every key loads its A row once, max-folds every B row of
 // the key in registers — each B row's load issued together with its next[] link, so a key held k times
-// costs k - 1 dependent hops — and stores A once; the other rows of the key do nothing.  Heads carry the
+// costs k - 1 dependent hops — and stores the 128-B lines of A that the fold raised, once (store elision, above:
+// a key whose rows are all at or below A writes nothing); the other rows of the key do nothing.  Heads carry the
 // batch's generation: a head left by an earlier batch reads as empty, so nothing resets them (the list
 // head's `head[key] = kNil` store was one more random write per distinct key: 0.578 -> 0.566 ms per 1M rows,
 // tools/tune_grouped.hip).  Atomics ran at ~1.3 TB/s of added bytes on MI355X against ~6 TB/s for plain
@@ -164,18 +189,18 @@ __global__ __launch_bounds__(kBlock) void k_merge_grouped(typename Elem<EB>::T* 
             const uint32_t w = isP ? v : v - nv;
             const auto* B = isP ? BP : BN;
             auto* A = isP ? AP : AN;
-            uint4 a[U], b[U];
+            uint4 a[U], a0[U], b[U];  // a0: the A vector as loaded (store elision)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (lead[u]) {
                     b[u] = nt_load(reinterpret_cast<const uint4*>(B + (m0 + u) * R) + w);
-                    a[u] = *(reinterpret_cast<const uint4*>(A + key[u] * R) + w);
+                    a0[u] = *(reinterpret_cast<const uint4*>(A + key[u] * R) + w);
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (!lead[u]) continue;
-                a[u] = vmax<EB>(a[u], b[u]);
+                a[u] = vmax<EB>(a0[u], b[u]);
                 uint64_t hops = 0;  // a list holds at most n_rows - 1 more rows: a bound every walk reaches
                 for (uint32_t cur = next[m0 + u]; cur != kNil && ++hops < n_rows;) {  // the key's other rows
                     const uint4 bb = nt_load(reinterpret_cast<const uint4*>(B + (uint64_t)cur * R) + w);
@@ -183,7 +208,9 @@ __global__ __launch_bounds__(kBlock) void k_merge_grouped(typename Elem<EB>::T* 
                     a[u] = vmax<EB>(a[u], bb);
                     cur = nx;
                 }
-                *(reinterpret_cast<uint4*>(A + key[u] * R) + w) = a[u];
+                // lead[u] and the list walk are wave-uniform: the ballot is taken by the lanes of this trip of the
+                // v loop (the last trip's idle lanes vote unchanged)
+                if (group_changed(__ballot(differs(a[u], a0[u])), lane)) *(reinterpret_cast<uint4*>(A + key[u] * R) + w) = a[u];
             }
         }
     }

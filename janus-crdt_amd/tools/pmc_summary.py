@@ -24,7 +24,8 @@ from pathlib import Path
 # bench.py "exchange" at N = 1: 1M rows with keys uniform over 2M -> expected distinct keys
 _EXCH_DISTINCT = round(2_000_000 * (1 - (1 - 1 / 2_000_000) ** 1_000_000))
 ALGO = {  # algorithmic bytes per launch of the bench.py workloads
-    "pnc_merge_dense": 10_000_000 * 64 * 8 * 2 * 3,           # P and N: read local + received, write local
+    # P and N: read local + received, write local (every line raised: the first launch; a re-merged batch writes none)
+    "pnc_merge_dense": 10_000_000 * 64 * 8 * 2 * 3,
     "orset_union_add": (100_000_000 * 2 + 150_000_000) * 28,  # read both sides, write the union (28 B records)
     "orset_union_rem": (20_000_000 * 2 + 30_000_000) * 28,
     # bench.py "exchange": 1M rows x (4 B key + 2 x 64 x 8 B) per rank
@@ -71,6 +72,17 @@ def json_scan_split(path, counter):
         elif cur is not None and ("k_resolve_rows" in n or "k_apply_emit" in n):
             cur[1] = True
     return out
+
+
+def dense_split(path, counter, kernel="k_merge_dense<8>"):
+    """The dense merge's counter values (bytes) in dispatch order, the first launch apart from the rest: the bench
+    re-merges one batch, so only the first launch after the synthesis raises cells (and writes their lines back);
+    every later one finds nothing to raise and, with store elision, writes nothing."""
+    with open(path) as f:
+        rows = sorted((r for r in csv.DictReader(f) if r["Counter_Name"] == counter and kernel in r["Kernel_Name"]),
+                      key=lambda r: int(r["Dispatch_Id"]))
+    v = [float(r["Counter_Value"]) * 1024 for r in rows]
+    return {"first": v[:1], "steady": v[1:]}
 
 
 def durations(trace_dir):
@@ -167,6 +179,17 @@ def main():
             res[key] = v
             if key in ALGO:
                 res[key + "_algorithmic"] = ALGO[key]
+    # the dense merge's steady launches (the batch already merged: reads only) apart from the first one after the
+    # synthesis (practically every line written back); pnc_merge_dense is the steady figure, what the bench times
+    ds = {c: dense_split(d / f"pmc_{c}" / "run_counter_collection.csv", c) for c in ("FETCH_SIZE", "WRITE_SIZE")}
+    if ds["FETCH_SIZE"]["steady"] and ds["WRITE_SIZE"]["steady"]:
+        f, w = statistics.median(ds["FETCH_SIZE"]["steady"]), statistics.median(ds["WRITE_SIZE"]["steady"])
+        res["pnc_merge_dense"] = 2 * f + w
+        res["pnc_merge_dense_steady"] = {"fetch_size_bytes": f, "write_size_bytes": w, "read_bytes": 2 * f,
+                                         "launches": [len(ds["FETCH_SIZE"]["steady"]), len(ds["WRITE_SIZE"]["steady"])]}
+        f1, w1 = ds["FETCH_SIZE"]["first"][0], ds["WRITE_SIZE"]["first"][0]
+        res["pnc_merge_dense_first_launch"] = 2 * f1 + w1
+        res["pnc_merge_dense_first"] = {"fetch_size_bytes": f1, "write_size_bytes": w1, "read_bytes": 2 * f1}
     # the json leg's steady-state waves (every replica known: pass A applies the cells itself, nothing follows it)
     # apart from its cold ones (first sight of the replicas: k_resolve_rows + k_apply_emit follow the scan)
     if (d / "pmc_json_FETCH_SIZE").exists():
