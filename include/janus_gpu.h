@@ -335,6 +335,42 @@ int jg_orset_names_since(jg_orset* s, uint64_t from, uint64_t* to, uint64_t* n_b
 int jg_orset_merge_json(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* off, const uint8_t* bytes, uint64_t* bad_msg);
 
 /* ---------------------------------------------------------------------------------------------
+ * The OR-Set by element name (csrc/orset_names.hip).  ORSet<string>'s members take strings
+ * (ORSet.cs:134-237); these calls resolve and intern them in the store's own element table, the one
+ * wave commits and jg_orset_names_sync fill, so a caller needs no string <-> id dictionaries.
+ * Name arrays as jg_tpset_*: name i = bytes[off[i], off[i+1]) with off[0] = 0, is_null[i] = 1 for the
+ * C# null element (its length is ignored).  Names are the element's UTF-8 bytes, unescaped, compared byte
+ * for byte, shorter than 2^31; "" is an ordinary element, distinct from null.  A set id the table has never
+ * seen is an empty set.  Locking and refusals as the id-taking counterparts.
+ * --------------------------------------------------------------------------------------------- */
+/* name -> live element id of set[i]: JG_NULL_ELEM for null, JG_NULL_ELEM - 1 ("never allocated", the id no
+ * record carries) when the set's live table lacks it.  Read-only.  (Replaces the caller's per-set
+ * Dictionary<string, id>; in the reference the strings are the keys of addSet / removeSet, ORSet.cs:83-88.) */
+int jg_orset_resolve_names(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* off, const uint8_t* bytes,
+                           const uint8_t* is_null, uint32_t* elem);
+/* ORSet.Contains(item) (ORSet.cs:234-237) by string. */
+int jg_orset_contains_names(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* off, const uint8_t* bytes,
+                            const uint8_t* is_null, uint8_t* out);
+/* ORSet.LookupAll() (ORSet.cs:204-227) as strings, in jg_orset_lookup_all's order: members of set[i] are entries
+ * [off[i], off[i+1]); entry k = bytes[name_off[k], name_off[k+1]), is_null[k] = 1 for the null element (zero length);
+ * elems (optional) = the ids.  off and *n_bytes always filled; name_off/bytes/is_null NULL = size query; JG_ESTATE
+ * with nothing written if cap_elems / cap_bytes are short, or if a member's id has no name in the table. */
+int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint64_t* off, uint64_t* n_bytes,
+                              uint64_t* name_off, uint8_t* bytes, uint8_t* is_null, uint32_t* elems,
+                              uint64_t cap_elems, uint64_t cap_bytes);
+/* ORSet.Add / Remove / Clear by string (ORSet.cs:134-198), op ids and results as jg_orset_apply_ops; the name of a
+ * Clear is ignored.  Per set, in op order: an Add takes its name's live id or interns it with the set's next id
+ * (ids only grow, also across Clear; several Adds of one new name share the id issued at the first); a Remove takes
+ * the id if the name is live at that point, else JG_NULL_ELEM - 1 (result 0, nothing interned); a Clear drops the
+ * set's live names.  The new names join the names log (jg_orset_names_since) in the order of their first Add;
+ * jg_orset_wave_names is not affected.  elem_out (optional): the id each op addressed (0 for a Clear).
+ * add_lim / rem_lim (both or neither): as jg_orset_apply_ops_ords.  All or nothing: JG_EINVAL for an op id other than
+ * 1..3, NULL arguments, bad offsets or an open wave, JG_ESTATE for a set out of element ids. */
+int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint8_t* op, const uint64_t* off,
+                             const uint8_t* bytes, const uint8_t* is_null, const uint64_t* tag_lo, const uint64_t* tag_hi,
+                             uint8_t* result, uint32_t* elem_out, uint64_t* add_lim, uint64_t* rem_lim);
+
+/* ---------------------------------------------------------------------------------------------
  * The committed-wave apply loop (csrc/node.hip) — SafeCRDTManager.HandleAfterConsensusUpdates
  * (BFT-CRDT/CRDTManagers/SafeCRDTManager.cs:109-160) as ONE call per committed wave (SURVEY.md §8b B2's
  * jg_apply_batch).  Inside the library: the walk in commit order, the skip of creation and key-space

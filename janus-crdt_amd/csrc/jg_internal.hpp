@@ -288,6 +288,14 @@ OrsetGathered orset_gather_sets(jg_orset* s, uint64_t n, const uint32_t* d_sets,
 void orset_settle_pending(jg_orset* s, size_t at);
 // orset.hip: room in the store's union targets for that many more records (no sync; skipped while counts are pending).
 void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in);
+// orset.hip, for orset_names.hip: jg_orset_contains' kernel over n device queries (set << 32 | id); jg_orset_lookup_all's
+// passes over n device set ids (d_out NULL: member counts into d_cnt_off, else members at the offsets there), both
+// queued on the context's stream; and the record side of jg_orset_apply_ops(_ords) over host ids (add_lim / rem_lim
+// both or neither), synchronous.
+void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out);
+void orset_lookup_all_device(jg_orset* s, const uint32_t* d_set, uint64_t n, uint64_t* d_cnt_off, uint32_t* d_out);
+void orset_apply_ops_ids(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
+                         const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim, uint64_t* rem_lim);
 
 // Node waves (node.hip): one upload of every kind's messages; rows / mset = the message's row / set id
 // or kSkipIdx.  json.hip (PN-Counter):

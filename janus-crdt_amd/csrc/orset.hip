@@ -1010,6 +1010,24 @@ void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in) {
     // device idle while the host queued the union (merge launches 237 us instead of 22 in a growing wave)
     (void)jg::scratch(s->ctx, s->ctx->scratch3, union_ws_bytes(s->add.n + add_in) + union_ws_bytes(s->rem.n + rem_in));
 }
+
+// The by-name entry points (orset_names.hip) resolve names on the device and hand device arrays to the kernels of
+// jg_orset_contains / jg_orset_lookup_all (queued on the context's stream, counts folded by the caller), and host
+// ids to the record side of jg_orset_apply_ops(_ords).
+void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out) {
+    hipLaunchKernelGGL(k_contains, dim3(grid_for(s->ctx, n, 16)), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_q, n, d_out);
+    JG_HIP(hipGetLastError());
+}
+void orset_lookup_all_device(jg_orset* s, const uint32_t* d_set, uint64_t n, uint64_t* d_cnt_off, uint32_t* d_out) {
+    const unsigned g = grid_for(s->ctx, n, 16);
+    if (d_out) hipLaunchKernelGGL(k_lookup_all<1>, dim3(g), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_set, n, d_cnt_off, d_out);
+    else hipLaunchKernelGGL(k_lookup_all<0>, dim3(g), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_set, n, d_cnt_off, d_out);
+    JG_HIP(hipGetLastError());
+}
+void orset_apply_ops_ids(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
+                         const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim, uint64_t* rem_lim) {
+    apply_ops(s, n_ops, set, elem, op, tag_lo, tag_hi, result, add_lim, rem_lim);
+}
 }  // namespace jg
 
 extern "C" {

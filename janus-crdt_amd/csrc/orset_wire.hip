@@ -42,9 +42,12 @@
 #include <vector>
 
 #include "jg_internal.hpp"
+#include "orset_names.hpp"
 #include "wire_cursor.hpp"
 
 namespace {
+
+using namespace jgn;  // the element table's layout and probes (orset_names.hpp)
 
 using jgw::Cursor;
 using jgw::hexv;
@@ -56,25 +59,10 @@ constexpr int kBlock = 256;
 constexpr unsigned long long kNone = ~0ull;
 constexpr unsigned long long kKindState = 1, kKindInval = 2;  // error word = position << 2 | kind
 constexpr uint32_t kDead = 0xFFFFFFFFu;                        // id of an entry at or beyond the limit
-constexpr uint32_t kNoName = 0xFFFFFFFFu;
 
 struct Tag16 { unsigned long long lo, hi; };
 
 unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3ull;
-// (set, string) key of an element name: the string's FNV-1a mixed with its set and the store's random salt
-// (drawn at the store's first wave), so a peer cannot aim names at one value of the sort's low 32 bits
-__device__ __forceinline__ uint64_t name_key(uint32_t set, uint64_t fnv, uint64_t salt) {
-    return mix64(fnv ^ mix64((uint64_t)set + salt));
-}
 
 // ---- string sinks: read_string feeds each unescaped UTF-8 byte to put(), esc() at a backslash -------
 __constant__ char kProp[4][16] = {"addSet", "removeSet", "nullAddGuid", "nullRemoveGuid"};
@@ -519,12 +507,6 @@ __global__ __launch_bounds__(kBlock) void k_ow_compact(const uint64_t* __restric
     }
 }
 
-__device__ __forceinline__ bool same_bytes(const uint8_t* a, const uint8_t* b, uint32_t n) {
-    for (uint32_t i = 0; i < n; ++i)
-        if (a[i] != b[i]) return false;
-    return true;
-}
-
 __device__ __forceinline__ bool same_name(const Entries& E, const uint32_t* mset, const uint8_t* bytes, uint32_t a, uint32_t b) {
     const uint32_t la = E.meta[a] & 0x7FFFFFFFu, lb = E.meta[b] & 0x7FFFFFFFu;
     if (la != lb || E.set[a] != E.set[b] || E.pfx[a] != E.pfx[b]) return false;
@@ -596,58 +578,7 @@ __global__ void k_ow_first_bad(const unsigned long long* __restrict__ err, uint6
     if (m < n && err[m] != kNone) atomicMin(status, (unsigned long long)m);
 }
 
-// ---- element table ----------------------------------------------------------------------------------
-struct Names {
-    unsigned long long* tab;
-    uint64_t mask;
-    uint32_t *set, *id, *gen, *len;
-    unsigned long long *off, *key;
-    uint8_t* pool;
-    uint32_t* set_gen;
-    uint32_t* next_id;
-    // (set, id) -> name index, for the encoder (jg_orset_encode_json): every name ever issued, dead ones too
-    unsigned long long* ikey;  // (set << 32 | id) + 1; 0 = empty
-    uint32_t* ival;            // the name's index g
-    uint64_t imask;
-};
-
-__device__ __forceinline__ void tab_insert(const Names& N, uint64_t key, uint32_t g) {
-    const unsigned long long word = (key >> 32) << 32 | (unsigned long long)(g + 1);
-    for (uint64_t s = key & N.mask;; s = (s + 1) & N.mask)
-        if (atomicCAS(N.tab + s, 0ull, word) == 0ull) return;
-}
-
-__device__ __forceinline__ void itab_insert(const Names& N, uint32_t set, uint32_t id, uint32_t g) {
-    const unsigned long long k = ((unsigned long long)set << 32 | id) + 1;
-    for (uint64_t s = mix64(k) & N.imask;; s = (s + 1) & N.imask)
-        if (atomicCAS(N.ikey + s, 0ull, k) == 0ull) {
-            N.ival[s] = g;
-            return;
-        }
-}
-
-// The name index of (set, id), or kNoName (a kernel after the inserting ones: no race).
-__device__ __forceinline__ uint32_t itab_find(const Names& N, uint32_t set, uint32_t id) {
-    const unsigned long long k = ((unsigned long long)set << 32 | id) + 1;
-    for (uint64_t s = mix64(k) & N.imask;; s = (s + 1) & N.imask) {
-        const unsigned long long w = N.ikey[s];
-        if (w == k) return N.ival[s];
-        if (w == 0) return kNoName;
-    }
-}
-
-__device__ __forceinline__ uint32_t tab_find(const Names& N, uint64_t key, uint32_t set, const uint8_t* name, uint32_t len) {
-    const uint32_t tag = (uint32_t)(key >> 32), gen = N.set_gen[set];
-    for (uint64_t s = key & N.mask;; s = (s + 1) & N.mask) {
-        const unsigned long long w = N.tab[s];
-        if (w == 0) return kNoName;
-        if ((uint32_t)(w >> 32) != tag) continue;
-        const uint32_t g = (uint32_t)w - 1;
-        if (N.set[g] != set || N.gen[g] != gen || N.len[g] != len || !same_bytes(N.pool + N.off[g], name, len)) continue;
-        return N.id[g];
-    }
-}
-
+// ---- element table (layout and probes: orset_names.hpp) -----------------------------------------------
 __global__ void k_names_rebuild(Names N, uint64_t n_names) {
     const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (g < n_names && N.gen[g] == N.set_gen[N.set[g]]) tab_insert(N, N.key[g], (uint32_t)g);
@@ -2586,6 +2517,22 @@ void orset_node_no_names(jg_orset* s) {
     if (!s->wire) return;
     s->wire->g0 = s->wire->g1 = s->wire->n_names;
     s->wire->p0 = s->wire->p1 = s->wire->pool_used;
+}
+
+// The by-name entry points (orset_names.hip) work on the table through these three.
+NamesRef orset_names_ref(jg_orset* s, uint64_t n_sets, uint64_t incoming, uint64_t pool_bytes) {
+    jg_orset_wire* w = wire_of(s);
+    ensure_sets(s->ctx, w, n_sets);
+    if (incoming || pool_bytes || !w->tab_cap || !w->itab_cap) ensure_names(s->ctx, w, incoming, pool_bytes);
+    return NamesRef{names_of(w), w->kmask, w->salt, w->n_names, w->pool_used, w->set_cap, w->open};
+}
+
+void orset_names_appended(jg_orset* s, uint64_t n, uint64_t nb, uint64_t id_bound) {
+    jg_orset_wire* w = s->wire;
+    w->n_names += n;
+    w->pool_used += nb;
+    w->id_bound = std::max(w->id_bound, id_bound);
+    w->mark();
 }
 
 void orset_wire_free(jg_orset_wire* w) {

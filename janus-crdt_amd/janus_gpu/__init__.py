@@ -35,6 +35,7 @@ EXPORTS = [
     "jg_rows_route", "jg_pnc_merge_device", "jg_orset_route", "jg_orset_merge_device", "jg_orset_read_sets",
     "jg_orset_names_sync", "jg_orset_wave_begin", "jg_orset_wave_append", "jg_orset_wave_check", "jg_orset_wave_commit",
     "jg_orset_wave_abort", "jg_orset_wave_names", "jg_orset_names_since", "jg_orset_merge_json",
+    "jg_orset_resolve_names", "jg_orset_contains_names", "jg_orset_lookup_all_names", "jg_orset_apply_ops_names",
     "jg_update_digests", "jg_wave_update_digests", "jg_waves_update_digests", "jg_wave_sha256", "jg_sha256_batch", "jg_update_digests_of",
     "jg_node_create", "jg_node_destroy", "jg_node_register", "jg_node_set_shard", "jg_shard_of", "jg_node_last_stats",
     "jg_tracker_create", "jg_tracker_destroy", "jg_tracker_add", "jg_tracker_size", "jg_tracker_contains",
@@ -123,6 +124,10 @@ _SIGS = {
     "jg_orset_wave_names": ([_vp, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
     "jg_orset_names_since": ([_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
     "jg_orset_merge_json": ([_vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)], C.c_int),
+    "jg_orset_resolve_names": ([_vp, _u64, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_orset_contains_names": ([_vp, _u64, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_orset_lookup_all_names": ([_vp, _u64, _vp, _vp, C.POINTER(_u64), _vp, _vp, _vp, _vp, _u64, _u64], C.c_int),
+    "jg_orset_apply_ops_names": ([_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_node_create": ([_vp, _vp, C.POINTER(_vp)], C.c_int),
     "jg_node_destroy": ([_vp], C.c_int),
     "jg_node_register": ([_vp, _u64, _vp, _vp, _vp], C.c_int),
@@ -752,6 +757,51 @@ class ORSetStore:
         out = np.empty(max(1, int(off[-1])), np.uint32)
         _check(load().jg_orset_lookup_all(self._h, s.size, _ptr(s), _ptr(off), _ptr(out), out.size))
         return [out[int(off[i]):int(off[i + 1])] for i in range(s.size)]
+
+    # ---- by element name (jg_orset_*_names, csrc/orset_names.hip): names are bytes (UTF-8), None = the null element ----
+    def resolve_names(self, set_ids, names) -> np.ndarray:
+        """jg_orset_resolve_names: each name's live elem id in its set (NULL_ELEM for None, NULL_ELEM - 1 if the set lacks it)."""
+        s = _arr(set_ids, np.uint32)
+        off, data, is_null = _pack_strings(names)
+        out = np.empty(s.size, np.uint32)
+        _check(load().jg_orset_resolve_names(self._h, s.size, _ptr(s), _ptr(off), _ptr(data), _ptr(is_null), _ptr(out)))
+        return out
+
+    def contains_names(self, set_ids, names) -> np.ndarray:
+        """ORSet.Contains by string (jg_orset_contains_names)."""
+        s = _arr(set_ids, np.uint32)
+        off, data, is_null = _pack_strings(names)
+        out = np.empty(s.size, np.uint8)
+        _check(load().jg_orset_contains_names(self._h, s.size, _ptr(s), _ptr(off), _ptr(data), _ptr(is_null), _ptr(out)))
+        return out
+
+    def lookup_all_names(self, set_ids, with_ids: bool = False):
+        """ORSet.LookupAll of each set as strings (jg_orset_lookup_all_names): list of [bytes | None] in the reference's
+        order (with_ids: also the list of uint32 id arrays)."""
+        s = _arr(set_ids, np.uint32)
+        off, nb = np.zeros(s.size + 1, np.uint64), _u64()
+        _check(load().jg_orset_lookup_all_names(self._h, s.size, _ptr(s), _ptr(off), C.byref(nb), None, None, None, None, 0, 0))
+        total = int(off[-1])
+        noff, data = np.zeros(total + 1, np.uint64), np.empty(max(1, nb.value), np.uint8)
+        isn, ids = np.zeros(max(1, total), np.uint8), np.empty(max(1, total), np.uint32)
+        _check(load().jg_orset_lookup_all_names(self._h, s.size, _ptr(s), _ptr(off), C.byref(nb), _ptr(noff), _ptr(data), _ptr(isn), _ptr(ids),
+                                                total, nb.value))
+        raw = data.tobytes()
+        flat = [None if isn[k] else raw[int(noff[k]):int(noff[k + 1])] for k in range(total)]
+        names = [flat[int(off[i]):int(off[i + 1])] for i in range(s.size)]
+        return (names, [ids[int(off[i]):int(off[i + 1])] for i in range(s.size)]) if with_ids else names
+
+    def apply_ops_names(self, set_ids, names, ops, tag_lo, tag_hi, ords: bool = False):
+        """ORSet.Add/Remove/Clear by string, in order (jg_orset_apply_ops_names): (results, the id each op addressed), with
+        ords=True also (add_lim, rem_lim) as apply_ops_ords."""
+        s, o = _arr(set_ids, np.uint32), _arr(ops, np.uint8)
+        lo, hi = _arr(tag_lo, np.uint64), _arr(tag_hi, np.uint64)
+        off, data, is_null = _pack_strings(names)
+        out, ids = np.empty(s.size, np.uint8), np.empty(s.size, np.uint32)
+        al, rl = (np.zeros(s.size, np.uint64), np.zeros(s.size, np.uint64)) if ords else (None, None)
+        _check(load().jg_orset_apply_ops_names(self._h, s.size, _ptr(s), _ptr(o), _ptr(off), _ptr(data), _ptr(is_null), _ptr(lo), _ptr(hi),
+                                               _ptr(out), _ptr(ids), _ptr(al), _ptr(rl)))
+        return (out, ids, al, rl) if ords else (out, ids)
 
     def route(self, world: int, d_add_key: int, d_add_tag: int, d_add_ord: int, cap_add: int, d_rem_key: int, d_rem_tag: int,
               d_rem_ord: int, cap_rem: int):
