@@ -710,6 +710,51 @@ int jg_keyspace_new_keys(jg_keyspace* ks, uint64_t from, uint64_t* to, uint64_t*
 int jg_keyspace_lookup(jg_keyspace* ks, uint64_t n, const uint64_t* off, const uint8_t* key_bytes, jg_guid* guid, uint8_t* found);
 
 /* ---------------------------------------------------------------------------------------------
+ * Client reads by key name (csrc/query.hip) — additive to ABI v10.
+ * PNCounterCommand / ORSetCommand "gp" / "gs" for a batch (CRDTCommands/PNCounterCommand.cs:27-41,
+ * ORSetCommand.cs:28-42): KeySpaceManager.GetKVPair (KeySpaceManager.cs:138-142) ->
+ * SafeCRDT.QueryStable / QueryProspective (SafeCRDT.cs:64-78) -> PNCounterWrapper.Query = PNCounter.Get
+ * (PNCounters.cs:87-90) or ORSetWrapper.Query = ORSet.Contains(args[0]) (ORSetWrapper.cs:24-28).
+ * One call chains the three resident tables on the device: the key space's dictionary (key -> Guid), the node's uid
+ * table (Guid -> type, row | set id; pending jg_node_register entries are uploaded first) and, for an OR-Set read,
+ * the store's element table (set, string -> element id); then jg_pnc_values' and jg_orset_contains' kernels answer.
+ *
+ * Query i reads key key_bytes[key_off[i], key_off[i+1]) (off[0] = 0 as elsewhere) on `node`, which is either copy of
+ * the keyspace: the stable copy answers "gs", the prospective copy "gp" (a mixed batch is two calls).  elem_flag[i]:
+ * 0 = no argument, 1 = the string elem_bytes[elem_off[i], elem_off[i+1]), 2 = the C# null element.  The three elem_*
+ * pointers are all NULL (no query carries an argument) or all given.
+ * Outputs: value[i] (Get's value, or Contains' 0 / 1; 0 for a status other than JG_Q_OK), status[i], kind[i] (optional: 0 PNCounter,
+ * 1 ORSet, 255 unresolved), guid[i] (optional: keySpaces[key], zero when the dictionary lacks the key).
+ *   Type.      The key's CRDT decides what is read, not the command (SafeCRDTManager hands back whichever SafeCRDT
+ *              the key names): a PN-Counter key ignores any argument (PNCounterWrapper.Query never reads args).
+ *   Argument.  An OR-Set key with flag 0 is JG_Q_NO_ARG (ORSetWrapper.Query dereferences args[0]); with flag 1 or 2
+ *              the answer is Contains by string exactly as jg_orset_contains_names gives it: "", a name never seen,
+ *              a set id without records and a name dropped by Clear are all absent.
+ *   Overflow.  value and the overflow rule are jg_pnc_values' for the key's row: JG_Q_OVERFLOW with value 0 when a
+ *              prefix of either checked Sum leaves the element type's range.
+ *   Keys.      Compared byte for byte with the dictionary; a key holding a NUL byte is never in it (JG_Q_NO_KEY).
+ *   JG_Q_NO_CRDT: the dictionary holds the key but `node` has nothing registered under its Guid (the reference's
+ *              "Key not found" answer).
+ * DEPARTURE (stated, parity-unpinned): the reference resolves safeCRDTs by key STRING (SafeCRDTManager.cs:29,72);
+ * here keySpaces[key] gives a Guid and the node's uid table is asked for it.  The two differ only after a second local
+ * CreateNewKVPair of a key the dictionary already holds: the reference rebinds safeCRDTs[key] to the new Guid's CRDT
+ * while TryAdd (KeySpaceManager.cs:130) keeps the old Guid in keySpaces; this call keeps reading the old Guid's CRDT.
+ * JG_EINVAL with every output untouched: NULL node, ks, value or status with n > 0; offsets that decrease (or
+ * off[0] != 0); an elem_flag other than 0, 1, 2; only some of the elem_* pointers; a key space and a node of different
+ * contexts.  n == 0 returns JG_OK.  The call holds the context's lock like jg_pnc_values and
+ * jg_orset_contains_names, is not refused while a wave holds the stores (it then reads what the wave has applied so
+ * far) unless a streamed wave of `node` itself is open with registrations pending, and changes no store or table. */
+#define JG_Q_OK        0  /* value[i] valid */
+#define JG_Q_NO_KEY    1  /* keySpaces[key] throws KeyNotFoundException (:140)                          */
+#define JG_Q_NO_CRDT   2  /* the dictionary holds the key, the node has no CRDT under its guid: "Key not found" */
+#define JG_Q_OVERFLOW  3  /* Get's checked Sum throws OverflowException                                  */
+#define JG_Q_NO_ARG    4  /* an OR-Set key read without an element: ORSetWrapper.Query dereferences args */
+int jg_node_query_keys(jg_node* node, jg_keyspace* ks, uint64_t n,
+                       const uint64_t* key_off, const uint8_t* key_bytes,
+                       const uint64_t* elem_off, const uint8_t* elem_bytes, const uint8_t* elem_flag,
+                       int64_t* value, uint8_t* status, uint8_t* kind, jg_guid* guid);
+
+/* ---------------------------------------------------------------------------------------------
  * Synthetic workloads (bench / size-independent parity): device-side counter-based generators,
  * defined in DESIGN.md §Synthetic inputs and mirrored on the host by the test oracle.
  * ------------------------------------------------------------------------------------------- */

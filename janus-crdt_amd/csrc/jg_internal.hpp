@@ -260,6 +260,10 @@ void pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t
 // one doubling of R under jg_pnc_set_max_replicas' bound (false: at the bound).
 void pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas);
 bool pnc_auto_widen(jg_pnc* p);
+// pnc.hip: jg_pnc_values' kernel over n device rows (d_keys NULL: rows 0..n), queued on the store's stream.  d_at /
+// d_count (query.hip): answer q into slot d_at[q], for the first *d_count rows only; an overflow is written as of_code.
+void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long* d_out, uint8_t* d_ovf, const uint32_t* d_at,
+                       const unsigned long long* d_count, uint8_t of_code);
 // orset.hip: merge n_runs sorted, duplicate-free runs (device SoA, run after run) into the store.
 void orset_merge_runs(jg_orset* s, uint32_t n_runs, const uint64_t* add_counts, const uint64_t* rem_counts, const unsigned long long* add_key,
                       const uint4* add_tag, const uint32_t* add_ord, const unsigned long long* rem_key, const uint4* rem_tag,
@@ -292,7 +296,9 @@ void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in);
 // passes over n device set ids (d_out NULL: member counts into d_cnt_off, else members at the offsets there), both
 // queued on the context's stream; and the record side of jg_orset_apply_ops(_ords) over host ids (add_lim / rem_lim
 // both or neither), synchronous.
-void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out);
+// d_at / d_count / d_out64 (query.hip): answer i into slot d_at[i] of d_out64, for the first *d_count queries only.
+void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out, const uint32_t* d_at = nullptr,
+                           const unsigned long long* d_count = nullptr, long long* d_out64 = nullptr);
 void orset_lookup_all_device(jg_orset* s, const uint32_t* d_set, uint64_t n, uint64_t* d_cnt_off, uint32_t* d_out);
 void orset_apply_ops_ids(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
                          const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim, uint64_t* rem_lim);

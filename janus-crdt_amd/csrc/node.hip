@@ -36,13 +36,12 @@
 
 #include "host_pool.hpp"
 #include "jg_internal.hpp"
+#include "uid_table.hpp"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr unsigned long long kTomb = ~0ull;
-constexpr uint32_t kOrSetBit = 0x80000000u;
 
 unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
 uint64_t pow2_at_least(uint64_t x, uint64_t lo = 1024) {
@@ -51,12 +50,10 @@ uint64_t pow2_at_least(uint64_t x, uint64_t lo = 1024) {
     return p;
 }
 
-struct UidSlot {
-    unsigned long long lo, hi;
-    uint32_t val, pad0;
-    unsigned long long pad1;
-};
-static_assert(sizeof(UidSlot) == 32, "one uid slot = half a 64-B line");
+using jg::DevUids;
+using jg::kNoSlot;
+using jg::kOrSetBit;
+using jg::UidSlot;  // uid_table.hpp: the table's layout and probe, shared with query.hip
 struct TrackSlot { unsigned long long key, origin; };
 struct Guid16 { unsigned long long lo, hi; };
 
@@ -70,7 +67,6 @@ __host__ __device__ __forceinline__ uint64_t seq_hash(uint64_t x) {
     return x ^ (x >> 33);
 }
 
-struct DevUids { const UidSlot* tab; uint64_t mask; };
 struct DevTrack { TrackSlot* tab; uint32_t* claim; uint64_t mask; };
 
 __global__ void k_uid_scatter(UidSlot* __restrict__ tab, const uint32_t* __restrict__ at, const UidSlot* __restrict__ v, uint64_t n) {
@@ -187,12 +183,7 @@ __global__ __launch_bounds__(kBlock) void k_classify(const Guid16* __restrict__ 
     uint32_t r = jg::kSkipIdx, s = jg::kSkipIdx, ts = kNoSlot;
     const Guid16 g = uid[i];
     if (type[i] != 0 && (g.lo | g.hi) != 0) {  // CRDTMsg of a key (not ManagerMsg_Create, not the key space)
-        uint32_t v = kNoSlot;
-        for (uint64_t q = uid_hash(g.lo, g.hi) & u.mask;; q = (q + 1) & u.mask) {
-            const UidSlot e = u.tab[q];
-            if ((e.lo | e.hi) == 0) break;
-            if (e.lo == g.lo && e.hi == g.hi) { v = e.val; break; }
-        }
+        const uint32_t v = jg::uid_find(u, g.lo, g.hi);
         if (v == kNoSlot) {
             atomicMin(status, (unsigned long long)i);  // TryGetValue false: skipped (:136); KeyNotFound in RM:329
         } else {
@@ -1035,6 +1026,16 @@ void apply_wave(jg_node* nd, jg_tracker* tr, const jg_commit* w, bool block_mode
     wave_end(nd, r, completed, n_completed, stopped_at);
 }
 }  // namespace
+
+namespace jg {
+jg_ctx* node_ctx(const jg_node* nd) { return nd->ctx; }
+NodeRef node_query_ref(jg_node* nd, const char* fn) {
+    JG_REQUIRE(!nd->run.active || (!nd->upload_all && nd->dirty.empty()), JG_EINVAL,
+               "%s: a streamed wave of the node is open and registrations are pending", fn);
+    nd->sync_table();
+    return NodeRef{nd->ctx, nd->pnc, nd->orset, DevUids{nd->dtab.as<UidSlot>(), nd->htab.size() - 1}};
+}
+}  // namespace jg
 
 extern "C" {
 

@@ -150,7 +150,12 @@ __device__ __forceinline__ uint64_t upper_key(const View& v, unsigned long long 
     return lo;
 }
 
-__global__ __launch_bounds__(kOB) void k_contains(View a, View r, const unsigned long long* __restrict__ q, uint64_t nq, uint8_t* __restrict__ out) {
+// at / count / out64 serve the reads by key name (query.hip): answer i goes to slot at[i] (NULL: i) of out64 (NULL:
+// of out), and only the first *count queries of the list are answered (NULL: all nq; the launch before appended them).
+__global__ __launch_bounds__(kOB) void k_contains(View a, View r, const unsigned long long* __restrict__ q, uint64_t nq, uint8_t* __restrict__ out,
+                                                  const uint32_t* __restrict__ at, const unsigned long long* __restrict__ count,
+                                                  long long* __restrict__ out64) {
+    if (count && *count < nq) nq = *count;
     for (uint64_t i = (uint64_t)blockIdx.x * kOB + threadIdx.x; i < nq; i += (uint64_t)gridDim.x * kOB) {
         const unsigned long long key = q[i];
         const uint64_t a0 = lower_key(a, key), a1 = upper_key(a, key);
@@ -164,7 +169,9 @@ __global__ __launch_bounds__(kOB) void k_contains(View a, View r, const unsigned
         bool present;
         if ((unsigned)key == JG_NULL_ELEM) present = !same;  // !nullRemoveGuid.SetEquals(nullAddGuid)
         else present = ca > 0 && (cr == 0 || !same);        // add key, and not in removeSet or !SetEquals
-        out[i] = present ? 1 : 0;
+        const uint64_t o = at ? at[i] : i;
+        if (out64) out64[o] = present ? 1 : 0;
+        else out[o] = present ? 1 : 0;
     }
 }
 
@@ -1014,8 +1021,10 @@ void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in) {
 // The by-name entry points (orset_names.hip) resolve names on the device and hand device arrays to the kernels of
 // jg_orset_contains / jg_orset_lookup_all (queued on the context's stream, counts folded by the caller), and host
 // ids to the record side of jg_orset_apply_ops(_ords).
-void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out) {
-    hipLaunchKernelGGL(k_contains, dim3(grid_for(s->ctx, n, 16)), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_q, n, d_out);
+void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out, const uint32_t* d_at,
+                           const unsigned long long* d_count, long long* d_out64) {
+    hipLaunchKernelGGL(k_contains, dim3(grid_for(s->ctx, n, 16)), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_q, n, d_out, d_at,
+                       d_count, d_out64);
     JG_HIP(hipGetLastError());
 }
 void orset_lookup_all_device(jg_orset* s, const uint32_t* d_set, uint64_t n, uint64_t* d_cnt_off, uint32_t* d_out) {
@@ -1201,7 +1210,8 @@ int jg_orset_contains(jg_orset* s, const uint32_t* set, const uint32_t* elem, ui
         auto* dq = reinterpret_cast<unsigned long long*>(st);
         auto* dout = reinterpret_cast<uint8_t*>(st + n * 8);
         JG_HIP(hipMemcpyAsync(dq, q.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_contains, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dq, n, dout);
+        hipLaunchKernelGGL(k_contains, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dq, n, dout,
+                           (const uint32_t*)nullptr, (const unsigned long long*)nullptr, (long long*)nullptr);
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipStreamSynchronize(ctx->stream));

@@ -286,15 +286,21 @@ __device__ __forceinline__ typename Acc<EB>::T checked_row_sum(const typename El
     return carry;
 }
 
+// at / count / of_code serve the reads by key name (query.hip): answer q goes to slot at[q] (NULL: q), only the
+// first *count keys of the list are answered (NULL: all n; the list was appended to by the launch before, so its
+// length never visits the host), and an overflow is reported as of_code (jg_pnc_values: 1).
 template <int EB>
 __global__ __launch_bounds__(kBlock) void k_values(const typename Elem<EB>::T* __restrict__ P, const typename Elem<EB>::T* __restrict__ N,
                                                    uint32_t R, const uint32_t* __restrict__ keys, uint64_t n,
-                                                   long long* __restrict__ out, uint8_t* __restrict__ ovf) {
+                                                   long long* __restrict__ out, uint8_t* __restrict__ ovf,
+                                                   const uint32_t* __restrict__ at, const unsigned long long* __restrict__ count,
+                                                   uint8_t of_code) {
     using T = typename Elem<EB>::T;
     using UT = std::make_unsigned_t<T>;
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    if (count && *count < n) n = *count;
     for (uint64_t q = wave; q < n; q += n_waves) {
         const uint64_t k = keys ? keys[q] : q;
         bool of = false;
@@ -303,8 +309,9 @@ __global__ __launch_bounds__(kBlock) void k_values(const typename Elem<EB>::T* _
         if (lane == 0) {
             // ΣP and ΣN are in range when !of; '-' is unchecked: wrap at the width.
             const T v = (T)((UT)(T)sp - (UT)(T)sn);
-            out[q] = of ? 0 : (long long)v;
-            ovf[q] = of ? 1 : 0;
+            const uint64_t o = at ? at[q] : q;
+            out[o] = of ? 0 : (long long)v;
+            ovf[o] = of ? of_code : 0;
         }
     }
 }
@@ -699,6 +706,25 @@ int jg_pnc_read_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, void* 
     });
 }
 
+}  // extern "C"
+
+namespace jg {
+void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long* d_out, uint8_t* d_ovf, const uint32_t* d_at,
+                       const unsigned long long* d_count, uint8_t of_code) {
+    jg_ctx* ctx = p->ctx;
+    const unsigned grid = grid_for(ctx, n * 64, 16);
+    if (p->eb == 8)
+        hipLaunchKernelGGL(k_values<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const long long*)p->P.p, (const long long*)p->N.p, p->R,
+                           d_keys, n, d_out, d_ovf, d_at, d_count, of_code);
+    else
+        hipLaunchKernelGGL(k_values<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const int*)p->P.p, (const int*)p->N.p, p->R, d_keys, n,
+                           d_out, d_ovf, d_at, d_count, of_code);
+    JG_HIP(hipGetLastError());
+}
+}  // namespace jg
+
+extern "C" {
+
 int jg_pnc_merge_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, const void* P, const void* N) {
     return jg::guard([&] {
         auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
@@ -769,14 +795,7 @@ int jg_pnc_values(jg_pnc* p, const uint32_t* key_idx, uint64_t n, int64_t* out, 
         char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch2, n * 9 + 64));
         long long* dout = (long long*)st;
         uint8_t* dovf = (uint8_t*)(st + n * 8);
-        const unsigned grid = grid_for(ctx, n * 64, 16);
-        if (p->eb == 8)
-            hipLaunchKernelGGL(k_values<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const long long*)p->P.p, (const long long*)p->N.p,
-                               p->R, dk, n, dout, dovf);
-        else
-            hipLaunchKernelGGL(k_values<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const int*)p->P.p, (const int*)p->N.p, p->R, dk,
-                               n, dout, dovf);
-        JG_HIP(hipGetLastError());
+        jg::pnc_values_device(p, dk, n, dout, dovf, nullptr, nullptr, 1);
         JG_HIP(hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipMemcpyAsync(overflow, dovf, n, hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipStreamSynchronize(ctx->stream));

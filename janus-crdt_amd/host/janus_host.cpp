@@ -1,5 +1,6 @@
 // janus_host.cpp — see janus_host.hpp.
 #include "janus_host.hpp"
+#include "keyspace.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -42,6 +43,13 @@ GpuStableStore::GpuStableStore(int device, uint32_t max_keys, uint32_t replicas,
     check(jg_node_create(pnc_, orset_, &node_));
 }
 
+GpuStableStore::GpuStableStore(jg_ctx* shared, uint32_t max_keys, uint32_t replicas, uint32_t elem_bytes)
+    : ctx_(shared), own_ctx_(false), max_keys_(max_keys), R_(replicas), eb_(elem_bytes) {
+    check(jg_pnc_create(ctx_, max_keys, replicas, elem_bytes, &pnc_));
+    check(jg_orset_create(ctx_, 0, 0, &orset_));
+    check(jg_node_create(pnc_, orset_, &node_));
+}
+
 GpuStableStore::~GpuStableStore() {
     if (p_bytes_) jg_host_free(p_bytes_);
     if (pin_buf_) jg_host_free(pin_buf_);
@@ -50,7 +58,7 @@ GpuStableStore::~GpuStableStore() {
     if (node_) jg_node_destroy(node_);
     if (orset_) jg_orset_destroy(orset_);
     if (pnc_) jg_pnc_destroy(pnc_);
-    if (ctx_) jg_close(ctx_);
+    if (ctx_ && own_ctx_) jg_close(ctx_);
 }
 
 
@@ -751,6 +759,53 @@ bool GpuStableStore::QueryStableORSet(const Guid& uid, const std::optional<std::
     uint8_t out = 0;
     check(jg_orset_contains(orset_, &set, &id, 1, &out));
     return out != 0;
+}
+
+PackedKeyQueries PackKeyQueries(const std::vector<KeyQuery>& queries) {
+    PackedKeyQueries p;
+    const size_t n = queries.size();
+    size_t kb = 0, eb = 0;
+    for (const KeyQuery& q : queries) {
+        kb += q.key.size();
+        if (q.has_arg && q.elem) eb += q.elem->size();
+        p.any_arg = p.any_arg || q.has_arg;
+    }
+    p.key_off.reserve(n + 1);
+    p.key_bytes.reserve(kb);
+    p.key_off.push_back(0);
+    for (const KeyQuery& q : queries) {
+        p.key_bytes.insert(p.key_bytes.end(), q.key.begin(), q.key.end());
+        p.key_off.push_back(p.key_bytes.size());
+    }
+    if (!p.any_arg) return p;
+    p.elem_off.reserve(n + 1);
+    p.elem_bytes.reserve(eb + 1);
+    p.elem_flag.reserve(n);
+    p.elem_off.push_back(0);
+    for (const KeyQuery& q : queries) {
+        if (q.has_arg && q.elem) p.elem_bytes.insert(p.elem_bytes.end(), q.elem->begin(), q.elem->end());
+        p.elem_off.push_back(p.elem_bytes.size());
+        p.elem_flag.push_back(!q.has_arg ? 0 : q.elem ? 1 : 2);
+    }
+    if (p.elem_bytes.empty()) p.elem_bytes.push_back(0);  // the three elem pointers are given together
+    return p;
+}
+
+std::vector<KeyAnswer> GpuStableStore::QueryKeys(GpuKeySpace& ks, const std::vector<KeyQuery>& queries) {
+    const size_t n = queries.size();
+    std::vector<KeyAnswer> out(n);
+    if (n == 0) return out;
+    flush_registrations();  // CreateSafeCRDTs not yet sent: the node's uid table
+    flush_names();          // names interned here that the engine's element table has not seen
+    const PackedKeyQueries p = PackKeyQueries(queries);
+    std::vector<int64_t> value(n);
+    std::vector<uint8_t> status(n), kind(n);
+    std::vector<jg_guid> guid(n);
+    check(jg_node_query_keys(node_, ks.handle(), n, p.key_off.data(), p.key_bytes.data(), p.any_arg ? p.elem_off.data() : nullptr,
+                             p.any_arg ? p.elem_bytes.data() : nullptr, p.any_arg ? p.elem_flag.data() : nullptr, value.data(), status.data(),
+                             kind.data(), guid.data()));
+    for (size_t i = 0; i < n; ++i) out[i] = KeyAnswer{value[i], status[i], kind[i], Guid{guid[i].lo, guid[i].hi}};
+    return out;
 }
 
 std::vector<std::string> GpuStableStore::EncodePNCStates(const std::vector<Guid>& uids) {

@@ -134,10 +134,36 @@ struct ClientUpdate {
     double now_ms = 0;    // DateTime.Now when the batcher sees it (the 100 ms flush rule, SafeCRDTManager.cs:170)
 };
 
+// One read by key name, "gp" / "gs" (PNCounterCommand.cs:27-41, ORSetCommand.cs:28-42), and its answer
+// (jg_node_query_keys).  has_arg = false: the command carries no element; has_arg with elem = nullopt: the C# null.
+struct KeyQuery {
+    std::string key;
+    bool has_arg = false;
+    std::optional<std::string> elem;
+};
+struct KeyAnswer {
+    int64_t value = 0;
+    uint8_t status = 0;  // JG_Q_*
+    uint8_t kind = 255;  // 0 PNCounter, 1 ORSet, 255 unresolved
+    Guid guid;           // keySpaces[key], empty when the dictionary lacks the key
+};
+// The batch as jg_node_query_keys takes it: offsets, bytes, flags (elem_* empty when no query carries an argument).
+struct PackedKeyQueries {
+    std::vector<uint64_t> key_off, elem_off;
+    std::vector<uint8_t> key_bytes, elem_bytes, elem_flag;
+    bool any_arg = false;
+};
+PackedKeyQueries PackKeyQueries(const std::vector<KeyQuery>& queries);
+
+class GpuKeySpace;  // keyspace.hpp
+
 // One CRDT copy (stable or prospective) of every key of one node, resident on one GPU.
 class GpuStableStore {
   public:
     GpuStableStore(int device, uint32_t max_keys, uint32_t replicas, uint32_t elem_bytes);
+    // The same on a context the caller owns: both copies of a node and its key space share one (jg_node_query_keys
+    // needs the key space and the node on one context).
+    GpuStableStore(jg_ctx* shared, uint32_t max_keys, uint32_t replicas, uint32_t elem_bytes);
     ~GpuStableStore();
     GpuStableStore(const GpuStableStore&) = delete;
     GpuStableStore& operator=(const GpuStableStore&) = delete;
@@ -233,6 +259,12 @@ class GpuStableStore {
     // OverflowException) and ORSet.Contains.
     int64_t QueryStablePNC(const Guid& uid);
     bool QueryStableORSet(const Guid& uid, const std::optional<std::string>& elem);
+    // A batch of reads by key NAME on this copy (the stable copy answers "gs", the prospective one "gp"): ONE
+    // jg_node_query_keys, which resolves key -> Guid -> (type, row | set) -> element id on the device; this mirror's
+    // own uid and element tables are not asked (registrations and names not yet sent are flushed first).  The key
+    // space must live on this store's context.  Statuses are reported, not thrown: the caller maps them to the
+    // reference's outputs.
+    std::vector<KeyAnswer> QueryKeys(GpuKeySpace& ks, const std::vector<KeyQuery>& queries);
     // GetLastSynchronizedUpdate().Encode() of PN-Counter keys, encoded on the device — the payload
     // SafeCRDT.Update ships after a client op (SafeCRDT.cs:49; batch producer).
     std::vector<std::string> EncodePNCStates(const std::vector<Guid>& uids);
@@ -367,6 +399,7 @@ class GpuStableStore {
     jg::WorkerPool& pool();  // persistent host workers for the flatten
 
     jg_ctx* ctx_ = nullptr;
+    bool own_ctx_ = true;  // false: the caller's context (the second constructor)
     jg_pnc* pnc_ = nullptr;
     jg_orset* orset_ = nullptr;
     jg_node* node_ = nullptr;
@@ -400,5 +433,10 @@ class GpuStableStore {
     double last_submit_ms_ = 0;                 // lastSumittedTime
     uint64_t next_seq_ = 1;                     // message identity for the safe-update tracker
 };
+
+// "gp" / "gs" for a batch of key names on the chosen copy of a node (the prospective or the stable store).
+inline std::vector<KeyAnswer> QueryKeys(GpuKeySpace& ks, GpuStableStore& copy, const std::vector<KeyQuery>& queries) {
+    return copy.QueryKeys(ks, queries);
+}
 
 }  // namespace janus

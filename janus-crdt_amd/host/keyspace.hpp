@@ -29,6 +29,7 @@ class GpuKeySpace {
     std::string Encode();                                   // GetLastSynchronizedUpdate().Encode() of the set
     std::optional<jg_guid> Lookup(const std::string& key);  // keySpaces[key]
     jg_tpset* set() const { return set_; }
+    jg_keyspace* handle() const { return ks_; }  // for GpuStableStore::QueryKeys (jg_node_query_keys)
 
   private:
     jg_keyspace* ks_ = nullptr;

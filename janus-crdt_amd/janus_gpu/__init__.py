@@ -45,7 +45,7 @@ EXPORTS = [
     "jg_tpset_create", "jg_tpset_destroy", "jg_tpset_size", "jg_tpset_apply_ops", "jg_tpset_contains", "jg_tpset_lookup_all",
     "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
-    "jg_keyspace_new_keys", "jg_keyspace_lookup",
+    "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
 ]
 
@@ -169,11 +169,46 @@ _SIGS = {
     "jg_keyspace_receive": ([_vp, _u64, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(C.c_uint8), C.POINTER(_u64)], C.c_int),
     "jg_keyspace_new_keys": ([_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
     "jg_keyspace_lookup": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_node_query_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
 }
 GUID_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])  # jg_guid
+
+# jg_node_query_keys: status[i] and kind[i]
+JG_Q_OK, JG_Q_NO_KEY, JG_Q_NO_CRDT, JG_Q_OVERFLOW, JG_Q_NO_ARG = range(5)
+Q_PNCOUNTER, Q_ORSET, Q_UNRESOLVED = 0, 1, 255
+
+
+class _NullElem:
+    """Node.query_keys: the C# null element as an OR-Set read's argument (None means no argument)."""
+
+    def __repr__(self):
+        return "NULL_ARG"
+
+
+NULL_ARG = _NullElem()
+
+
+def _utf8(x) -> bytes:
+    return x.encode() if isinstance(x, str) else bytes(x)
+
+
+def pack_queries(keys, elems=None):
+    """Node.query_keys' packing: (key_off u64[n+1], key_bytes u8, elem_off | None, elem_bytes | None, elem_flag | None).
+    keys: str | bytes; elems[i]: None = no argument (flag 0), str | bytes = that string (flag 1), NULL_ARG = the C# null
+    element (flag 2).  elems None: the three elem arrays are None (no query carries an argument)."""
+    kdata, koff = pack_wave([_utf8(k) for k in keys])
+    if elems is None:
+        return koff, kdata, None, None, None
+    if len(elems) != len(keys):
+        raise ValueError("query_keys: one elems entry per key")
+    flag = np.array([0 if e is None else 2 if e is NULL_ARG else 1 for e in elems], np.uint8)
+    edata, eoff = pack_wave([b"" if e is None or e is NULL_ARG else _utf8(e) for e in elems])
+    if edata.size == 0:
+        edata = np.zeros(1, np.uint8)  # all three pointers are given or none is
+    return koff, kdata, eoff, edata, flag
 
 
 class JanusError(RuntimeError):
@@ -937,6 +972,18 @@ class Node:
 
     def set_shard(self, rank: int, world: int) -> None:
         _check(load().jg_node_set_shard(self._h, rank, world))
+
+    def query_keys(self, keyspace: "KeySpace", keys, elems=None, with_guid: bool = False):
+        """jg_node_query_keys: "gp" / "gs" of this copy for a batch of key names, resolved on the device.  Returns
+        (value i64, status u8 (JG_Q_*), kind u8 (Q_*)), with_guid: also the GUID_DTYPE array of keySpaces[key].
+        elems as pack_queries takes them."""
+        n = len(keys)
+        koff, kdata, eoff, edata, flag = pack_queries(keys, elems)
+        value, status, kind = np.zeros(n, np.int64), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        guid = np.zeros(n, GUID_DTYPE) if with_guid else None
+        _check(load().jg_node_query_keys(self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(eoff), _ptr(edata), _ptr(flag),
+                                         _ptr(value), _ptr(status), _ptr(kind), _ptr(guid)))
+        return (value, status, kind, guid) if with_guid else (value, status, kind)
 
     def _commit(self, lo, hi, types, seqs, msgs=None, data=None, off=None, pinned=None):
         if msgs is not None:

@@ -1,0 +1,516 @@
+"""GPU parity of the client reads by key name (jg_node_query_keys, csrc/query.hip).
+
+Every batch is checked two ways:
+  * against a Python model: a dict key -> guid, a dict guid -> (type, idx), oracle_ref.pnc_values for Get and its
+    overflow, orset_names_ref.ORSetStr for Contains;
+  * against the composed path through the calls that existed before: KeySpace.lookup -> the Python dict ->
+    PNCStore.values / ORSetStore.contains_names.  value, status, kind and guid must be equal.
+"""
+import os
+import subprocess
+import sys
+import threading
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import janus_gpu as jg
+import jsongen as J
+import oracle_ref as orc
+from gen import random_pnc
+from orset_names_ref import ADD, CLEAR, REMOVE, ORSetStr
+from test_keyspace_gpu import entry, msg
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+NA = jg.NULL_ARG
+OK, NO_KEY, NO_CRDT, OVERFLOW, NO_ARG = jg.JG_Q_OK, jg.JG_Q_NO_KEY, jg.JG_Q_NO_CRDT, jg.JG_Q_OVERFLOW, jg.JG_Q_NO_ARG
+
+
+def _b(x):
+    return x.encode() if isinstance(x, str) else bytes(x)
+
+
+class World:
+    """One copy of a keyspace: a key space, a node over a PN-Counter and / or an OR-Set store, and the model of all."""
+
+    def __init__(self, ctx, rows=64, R=4, eb=8, pnc=True, orset=True, seed=1, ks=None, cap_keys=8192):
+        self.rng = np.random.default_rng(seed)
+        self.own_ks = ks is None
+        self.ks = ks if ks is not None else jg.KeySpace(ctx, cap_keys, cap_keys * 400)
+        self.pnc = jg.PNCStore(ctx, rows, R, eb) if pnc else None
+        self.ors = jg.ORSetStore(ctx) if orset else None
+        self.node = jg.Node(self.pnc, self.ors)
+        self.guid, self.reg, self.sets = {}, {}, {}  # key -> guid; guid -> (type, idx); set id -> ORSetStr
+        if pnc:
+            info = np.iinfo(np.int32 if eb == 4 else np.int64)
+            self.P = random_pnc(self.rng, rows, R, eb, absent=False, lo=info.min // (2 * R), hi=info.max // (2 * R))
+            self.N = random_pnc(self.rng, rows, R, eb, absent=False, lo=info.min // (2 * R), hi=info.max // (2 * R))
+            self.pnc.write_rows(self.P, self.N)
+        self._vals = None
+
+    def close(self):
+        self.node.close()
+        for h in (self.pnc, self.ors):
+            if h is not None:
+                h.close()
+        if self.own_ks:
+            self.ks.close()
+
+    # ---- state -------------------------------------------------------------------------------------------
+    def write(self, P, N):
+        self.P, self.N, self._vals = P, N, None
+        self.pnc.write_rows(P, N)
+
+    def create(self, keys, guids=None):
+        """CreateNewKVPair of new keys; returns their guids."""
+        guids = guids or J.random_guids(self.rng, len(keys))
+        assert all(self.ks.create_keys([(_b(k), g) for k, g in zip(keys, guids)]))
+        for k, g in zip(keys, guids):
+            self.guid[_b(k)] = g
+        return guids
+
+    def register(self, guids, types, idx):
+        self.node.register([g[0] for g in guids], [g[1] for g in guids], types, idx)
+        for g, t, i in zip(guids, types, idx):
+            self.reg[g] = (t, i)
+
+    def add_keys(self, keys, types, idx):
+        self.register(self.create(keys), types, idx)
+
+    def ops(self, ops):
+        """[(set, op, name | None)] by name on the store and on the model."""
+        n = len(ops)
+        lo, hi = self.rng.integers(1, 2**63, n, dtype=np.uint64), self.rng.integers(0, 2**63, n, dtype=np.uint64)
+        for k, (s, op, name) in enumerate(ops):
+            self.sets.setdefault(s, ORSetStr()).apply(op, name, (int(lo[k]), int(hi[k])))
+        self.ors.apply_ops_names([o[0] for o in ops], [o[2] for o in ops], [o[1] for o in ops], lo, hi)
+
+    # ---- the two yardsticks ------------------------------------------------------------------------------
+    def values(self):
+        if self._vals is None:
+            self._vals = orc.pnc_values(self.P, self.N)
+        return self._vals
+
+    def model(self, keys, elems=None):
+        n = len(keys)
+        value, status, kind = np.zeros(n, np.int64), np.zeros(n, np.uint8), np.full(n, 255, np.uint8)
+        guid = np.zeros(n, jg.GUID_DTYPE)
+        present = {}
+        for i, k in enumerate(keys):
+            g = self.guid.get(_b(k))
+            if g is None:
+                status[i] = NO_KEY
+                continue
+            guid[i] = g
+            if g not in self.reg:
+                status[i] = NO_CRDT
+                continue
+            t, idx = self.reg[g]
+            kind[i] = t
+            if t == 0:
+                ev, eo = self.values()
+                value[i], status[i] = (0, OVERFLOW) if eo[idx] else (ev[idx], OK)
+                continue
+            e = None if elems is None else elems[i]
+            if e is None:
+                status[i] = NO_ARG
+                continue
+            if idx not in present:
+                present[idx] = set(self.sets[idx].LookupAll()) if idx in self.sets else set()
+            value[i] = 1 if (None if e is NA else _b(e)) in present[idx] else 0
+        return value, status, kind, guid
+
+    def composed(self, keys, elems=None):
+        """KeySpace.lookup -> the caller's dictionary -> PNCStore.values / ORSetStore.contains_names."""
+        n = len(keys)
+        value, status, kind = np.zeros(n, np.int64), np.zeros(n, np.uint8), np.full(n, 255, np.uint8)
+        guid = np.zeros(n, jg.GUID_DTYPE)
+        found = self.ks.lookup([_b(k) for k in keys]) if n else []
+        pi, prow, oi, oset, oname = [], [], [], [], []
+        for i, g in enumerate(found):
+            if g is None:
+                status[i] = NO_KEY
+                continue
+            guid[i] = g
+            if g not in self.reg:
+                status[i] = NO_CRDT
+                continue
+            t, idx = self.reg[g]
+            kind[i] = t
+            e = None if elems is None else elems[i]
+            if t == 0:
+                pi.append(i), prow.append(idx)
+            elif e is None:
+                status[i] = NO_ARG
+            else:
+                oi.append(i), oset.append(idx), oname.append(None if e is NA else _b(e))
+        if pi:
+            v, o = self.pnc.values(np.array(prow, np.uint32))
+            value[pi], status[pi] = v, np.where(o != 0, OVERFLOW, OK)
+        if oi:
+            value[oi] = self.ors.contains_names(oset, oname)
+        return value, status, kind, guid
+
+    def check(self, keys, elems=None):
+        got = self.node.query_keys(self.ks, keys, elems, with_guid=True)
+        for name, g, m, c in zip(("value", "status", "kind", "guid"), got, self.model(keys, elems), self.composed(keys, elems)):
+            assert np.array_equal(g, m), (name, "model", np.flatnonzero(g != m)[:8])
+            assert np.array_equal(g, c), (name, "composed", np.flatnonzero(g != c)[:8])
+        value, status, kind = self.node.query_keys(self.ks, keys, elems)  # without the guid array
+        assert np.array_equal(value, got[0]) and np.array_equal(status, got[1]) and np.array_equal(kind, got[2])
+        return got
+
+
+# ---- the standing world: every status and kind ----------------------------------------------------------------
+KEY_LENS = (0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 300)
+SAME32 = b"0123456789abcdef0123456789ABCDEF"  # two keys equal for 32 bytes, differing in the last
+
+
+def key_of_len(n):
+    return (b"k%03d-" % n + b"x" * n)[:n] if n >= 5 else b"abcd"[:n]
+
+
+SHAPE_KEYS = [key_of_len(n) for n in KEY_LENS] + ["schlüssel-日本語-🔑".encode(), "ключ".encode(), SAME32 + b"a", SAME32 + b"b", b"prefix", b"prefix-longer"]
+# OR-Set sets: 0 members / removed / "" / null present; 1 null absent, never-seen name; 2 Cleared; 3 registered, no records;
+# 5000 registered past anything the element table has seen
+SET_KEYS = {b"set-0": 0, b"set-1": 1, b"set-cleared": 2, b"set-empty": 3, b"set-far": 5000}
+
+
+def standing(ctx, eb):
+    R = 4 if eb == 4 else 65  # 65: the checked Sum's second chunk of 64 columns
+    w = World(ctx, rows=64, R=R, eb=eb, seed=10 + eb)
+    info = np.iinfo(np.int32 if eb == 4 else np.int64)
+    P, N = w.P.copy(), w.N.copy()
+    P[:4], N[:4] = 0, 0
+    P[0, :3] = info.max, 1, -5   # overflows at the 2nd prefix (test_values_checked_sum's rows 0-49)
+    P[1, :3] = info.max, -5, 1   # the same multiset in an order that never overflows (rows 50-99)
+    P[2, 0], N[2, 0] = 1, info.min  # wraps in the unchecked subtraction (rows 100-199)
+    N[3, :3] = info.min, -1, 5   # the N side overflows
+    w.write(P, N)
+    w.add_keys([b"pn-%d" % i for i in range(8)], [0] * 8, list(range(8)))
+    # the key shapes: PN-Counter rows 8.., every third an OR-Set key of set 0
+    types = [1 if i % 3 == 2 else 0 for i in range(len(SHAPE_KEYS))]
+    w.add_keys(SHAPE_KEYS, types, [0 if t else 8 + i for i, t in enumerate(types)])
+    w.add_keys(list(SET_KEYS), [1] * len(SET_KEYS), list(SET_KEYS.values()))
+    w.create([b"created-only", b"created-only-2"])  # in the dictionary, never registered: NO_CRDT
+    w.ops([(0, ADD, b"member"), (0, ADD, b"gone"), (0, REMOVE, b"gone"), (0, ADD, b""), (0, ADD, None), (0, ADD, "élément".encode()),
+           (1, ADD, b"only-in-1"), (1, ADD, None), (1, REMOVE, None),
+           (2, ADD, b"before-clear"), (2, ADD, None), (2, CLEAR, None), (2, ADD, b"after-clear")])
+    return w
+
+
+def standing_pool(w):
+    """(key, elem) queries covering every status and kind of the standing world."""
+    q = [(b"pn-%d" % i, None) for i in range(8)]
+    q += [(b"pn-0", b"ignored"), (b"pn-1", NA), (b"pn-5", b"")]  # a PN-Counter key ignores any argument
+    q += [(k, b"member" if i % 3 == 2 else None) for i, k in enumerate(SHAPE_KEYS)]
+    for k in (b"set-0", b"set-1", b"set-cleared", b"set-empty", b"set-far"):
+        q += [(k, e) for e in (b"member", b"gone", b"", NA, "élément".encode(), b"only-in-1", b"before-clear", b"after-clear", b"never-seen", None)]
+    q += [(b"created-only", None), (b"created-only-2", b"member")]
+    q += [(b"no-such-key", None), (b"no-such-key", b"member"), (b"pn-0\0", None), (b"pre\0fix", NA), (SAME32, None), (SAME32 + b"c", None),
+          (b"prefi", None), (b"prefix-longer!", None), (b"\0", None)]
+    return q
+
+
+@pytest.fixture(scope="module")
+def worlds(ctx):
+    ws = {eb: standing(ctx, eb) for eb in (4, 8)}
+    yield ws
+    for w in ws.values():
+        w.close()
+
+
+def shuffled(w, pool, n, seed):
+    rng = np.random.default_rng(seed)
+    qs = [pool[i % len(pool)] for i in range(n)]
+    order = rng.permutation(n)
+    return [qs[i][0] for i in order], [qs[i][1] for i in order]
+
+
+@pytest.mark.parametrize("eb", [4, 8])
+def test_every_status_and_kind_in_one_batch(worlds, eb):
+    w = worlds[eb]
+    pool = standing_pool(w)
+    keys, elems = shuffled(w, pool, 3 * len(pool), 5)
+    value, status, kind, guid = w.check(keys, elems)
+    assert set(status.tolist()) == {OK, NO_KEY, NO_CRDT, OVERFLOW, NO_ARG} and set(kind.tolist()) == {0, 1, 255}
+    # the facts the model rests on, stated once
+    one = dict(zip(zip(keys, map(lambda e: e if e is None or e is NA else bytes(e), elems)), zip(value.tolist(), status.tolist())))
+    assert one[(b"pn-0", None)] == (0, OVERFLOW) and one[(b"pn-1", None)][1] == OK and one[(b"pn-3", None)] == (0, OVERFLOW)
+    assert one[(b"pn-0", b"ignored")] == (0, OVERFLOW) and one[(b"pn-1", NA)] == one[(b"pn-1", None)]
+    assert one[(b"set-0", b"member")] == (1, OK) and one[(b"set-0", b"gone")] == (0, OK) and one[(b"set-0", b"")] == (1, OK)
+    assert one[(b"set-0", NA)] == (1, OK) and one[(b"set-1", NA)] == (0, OK) and one[(b"set-1", b"member")] == (0, OK)
+    assert one[(b"set-cleared", b"before-clear")] == (0, OK) and one[(b"set-cleared", b"after-clear")] == (1, OK)
+    assert one[(b"set-empty", b"member")] == (0, OK) and one[(b"set-far", NA)] == (0, OK) and one[(b"set-0", None)] == (0, NO_ARG)
+    assert one[(b"pn-0\0", None)] == (0, NO_KEY) and one[(b"created-only", None)] == (0, NO_CRDT)
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 256, 257, 1000])
+def test_batch_sizes(worlds, n):
+    w = worlds[8]
+    keys, elems = shuffled(w, standing_pool(w), n, 100 + n)
+    w.check(keys, elems)
+    w.check(keys)  # no query carries an argument: the three elem pointers are NULL
+
+
+def test_key_shapes(worlds):
+    w = worlds[4]
+    probes = SHAPE_KEYS + [k + b"\0" for k in SHAPE_KEYS] + [k[:-1] for k in SHAPE_KEYS if k] + [k + b"x" for k in SHAPE_KEYS]
+    value, status, kind, guid = w.check(probes, [b"member"] * len(probes))
+    assert (status[:len(SHAPE_KEYS)] == OK).all()
+    assert (status[len(SHAPE_KEYS):2 * len(SHAPE_KEYS)] == NO_KEY).all()  # an embedded NUL is never in the dictionary
+
+
+def test_hot_keys(worlds):
+    w = worlds[8]
+    for n in (64, 4096):
+        w.check([b"pn-2"] * n)
+        w.check([b"set-0"] * n, [b"member"] * n)
+        w.check([b"pn-2", b"set-0"] * (n // 2), [None, NA] * (n // 2))
+        w.check([b"pn-0", b"pn-1"] * (n // 2))  # overflow beside its reordered twin
+
+
+def test_nodes_with_one_store(ctx):
+    for pnc, orset in ((True, False), (False, True)):
+        w = World(ctx, rows=8, R=3, eb=8, pnc=pnc, orset=orset, seed=3)
+        try:
+            w.create([b"a", b"b", b"c"])
+            if pnc:
+                w.register([w.guid[b"a"], w.guid[b"b"]], [0, 0], [7, 0])
+            else:
+                w.register([w.guid[b"a"], w.guid[b"b"]], [1, 1], [0, 9])
+                w.ops([(0, ADD, b"x"), (0, ADD, None)])
+            keys = [b"a", b"b", b"c", b"d"] * 40
+            value, status, kind, guid = w.check(keys, [b"x", NA, None, b"x"] * 40)
+            assert status[:4].tolist() == [OK, OK, NO_CRDT, NO_KEY] and kind[:4].tolist() == ([0, 0] if pnc else [1, 1]) + [255, 255]
+            w.check(keys)
+        finally:
+            w.close()
+
+
+def test_state_that_changes_between_calls(ctx):
+    w = World(ctx, rows=16, R=3, eb=8, seed=4)
+    try:
+        w.add_keys([b"p0", b"s0"], [0, 1], [0, 0])
+        w.ops([(0, ADD, b"e0")])
+        probe = lambda: w.check(list(w.guid) + [b"absent"], [b"e0"] * (len(w.guid) + 1))  # noqa: E731
+        probe()
+        # registrations after a query: the dirty slots are uploaded by the next one
+        w.add_keys([b"p1", b"s1"], [0, 1], [5, 1])
+        w.create([b"late"])
+        assert probe()[1][-2] == NO_CRDT
+        w.register([w.guid[b"late"]], [0], [15])
+        assert probe()[1][-2] == OK
+        # 3000 registrations: the uid table rehashes (a whole upload)
+        w.pnc.reserve(4000, 0)
+        w.P = np.vstack([w.P, np.zeros((4000 - 16, 3), w.P.dtype)])
+        w.N = np.vstack([w.N, np.zeros((4000 - 16, 3), w.N.dtype)])
+        w._vals = None
+        w.add_keys([b"bulk-%d" % i for i in range(3000)], [0] * 3000, list(range(16, 3016)))
+        probe()
+        # keys learnt from a peer between queries (KeySpace.receive)
+        gs = J.random_guids(w.rng, 40)
+        new = [b"peer-%d" % i for i in range(40)]
+        assert w.ks.receive([msg([entry(k, g) for k, g in zip(new[:20], gs[:20])]), msg([entry(k, g) for k, g in zip(new[20:], gs[20:])])]) == 40
+        for k, g in zip(new, gs):
+            w.guid[k] = g
+        assert (probe()[1][-41:-1] == NO_CRDT).all()
+        w.register(gs, [0, 1] * 20, [3100 + i for i in range(40)])
+        probe()
+        # jg_pnc_reserve: more replica columns and more keys, written through the new shape
+        w.pnc.reserve(5000, 6)
+        assert w.pnc.shape()[:2] == (5000, 6)
+        P, N = np.zeros((5000, 6), w.P.dtype), np.zeros((5000, 6), w.N.dtype)
+        P[:4000, :3], N[:4000, :3] = w.P, w.N
+        P[:, 3:] = w.rng.integers(0, 1 << 40, (5000, 3))
+        w.write(P, N)
+        w.add_keys([b"grown"], [0], [4999])
+        probe()
+        # an apply_ops_names batch large enough to rebuild the element table
+        names = [b"name-%d" % i for i in range(6000)]
+        w.ops([(i % 3, ADD, nm) for i, nm in enumerate(names)])
+        w.add_keys([b"s2"], [1], [2])
+        keys = [b"s0", b"s1", b"s2"] * 600
+        w.check(keys, [names[i] for i in range(0, 3600, 2)])
+        probe()
+    finally:
+        w.close()
+
+
+def test_two_copies_share_one_key_space(ctx):
+    """"gs" lags "gp" until the wave is committed (KVStoreTests.cs:225-286)."""
+    rng = np.random.default_rng(6)
+    ks = jg.KeySpace(ctx, 64, 1 << 14)
+    stable, prosp = (World(ctx, rows=8, R=2, eb=8, orset=False, seed=7, ks=ks) for _ in range(2))
+    try:
+        for w in (stable, prosp):
+            w.write(np.zeros((8, 2), np.int64), np.zeros((8, 2), np.int64))
+        keys = [b"counter-%d" % i for i in range(8)]
+        gs = stable.create(keys)
+        prosp.guid = stable.guid
+        for w in (stable, prosp):
+            w.register(gs, [0] * 8, list(range(8)))
+        replica = J.random_guids(rng, 1)
+        wave = [(gs[i % 8], J.encode_pnc(replica, [10 + i], [i % 3])) for i in range(24)]
+        lo, hi, msgs = [u[0] for u, _ in wave], [u[1] for u, _ in wave], [m for _, m in wave]
+        cut, rc = prosp.node.apply_block(lo, hi, [1] * 24, msgs)
+        assert (cut, rc) == (None, jg.JG_OK)
+        P, N = prosp.pnc.read_rows()
+        prosp.P, prosp.N, prosp._vals = P, N, None
+        q = keys * 10
+        gp, gs_ = prosp.check(q), stable.check(q)
+        # key k took messages k, k + 8, k + 16: P = 26 + k, N = 2 (i % 3 takes every residue)
+        assert gp[0][:8].tolist() == [24 + k for k in range(8)] and (gs_[0] == 0).all()
+        assert not np.array_equal(gp[0], gs_[0]) and np.array_equal(gp[3], gs_[3])
+        done, cut, rc = stable.node.apply_committed(None, lo, hi, [1] * 24, None, msgs)
+        assert (cut, rc) == (None, jg.JG_OK)
+        stable.P, stable.N, stable._vals = P, N, None
+        gp, gs_ = prosp.check(q), stable.check(q)
+        for a, b in zip(gp, gs_):
+            assert np.array_equal(a, b)
+    finally:
+        stable.close()
+        prosp.close()
+        ks.close()
+
+
+def test_refusals_leave_the_outputs_untouched(ctx, worlds):
+    w = worlds[8]
+    lib = jg.load()
+    n = 3
+    koff, kdata, eoff, edata, flag = jg.pack_queries([b"pn-0", b"set-0", b"nope"], [None, b"member", NA])
+    p = jg._ptr
+
+    def call(node=w.node._h, ks=w.ks._h, n=n, koff=koff, kdata=kdata, eoff=eoff, edata=edata, flag=flag, null=(), want=jg.JG_EINVAL):
+        out = {"value": np.full(3, 0x5A5A5A5A5A5A5A5A, np.int64), "status": np.full(3, 0xA5, np.uint8), "kind": np.full(3, 0xA5, np.uint8),
+               "guid": np.full(6, 0xA5A5A5A5A5A5A5A5, np.uint64)}
+        before = {k: v.copy() for k, v in out.items()}
+        rc = lib.jg_node_query_keys(node, ks, n, p(koff), p(kdata), p(eoff), p(edata), p(flag),
+                                    *(None if k in null else p(out[k]) for k in ("value", "status", "kind", "guid")))
+        assert rc == want
+        if want != jg.JG_OK or n == 0:
+            for k in out:
+                assert np.array_equal(out[k], before[k]), k
+        return out
+
+    call(node=None)
+    call(ks=None)
+    call(null=("value",))
+    call(null=("status",))
+    call(koff=np.array([0, 5, 4, 9], np.uint64))       # offsets that decrease
+    call(eoff=np.array([0, 6, 2, 6], np.uint64))
+    call(koff=np.array([1, 4, 9, 13], np.uint64))      # off[0] = 0 as everywhere else
+    call(flag=np.array([0, 3, 2], np.uint8))           # a flag other than 0, 1, 2
+    call(eoff=None)                                    # only some of the three elem pointers
+    call(edata=None)
+    call(flag=None)
+    call(eoff=None, edata=None)
+    call(n=0, want=jg.JG_OK)
+    call(n=0, node=None, ks=None, null=("value", "status", "kind", "guid"), want=jg.JG_OK)
+    other = jg.Context(int(os.environ.get("JANUS_GPU_DEVICE", "0")))
+    try:
+        with jg.KeySpace(other, 8, 1 << 10) as ks2:  # a key space and a node of different contexts
+            call(ks=ks2._h)
+    finally:
+        other.close()
+    out = call(want=jg.JG_OK)                          # and the same arguments, unbroken, answer
+    assert out["status"].tolist() == [OVERFLOW, OK, NO_KEY] and out["value"].tolist() == [0, 1, 0] and out["kind"].tolist() == [0, 1, 255]
+    out = call(null=("kind", "guid"), want=jg.JG_OK)   # kind and guid are optional
+    assert out["status"].tolist() == [OVERFLOW, OK, NO_KEY]
+    w.check([b"pn-0", b"set-0", b"nope"], [None, b"member", NA])  # nothing changed
+
+
+def test_readers_beside_a_merging_thread(ctx):
+    """Two readers call query_keys while a third thread merges into the PN-Counter store (test_threads_gpu's pattern):
+    every answer equals the model at some merge boundary."""
+    rng = np.random.default_rng(8)
+    K, R = 512, 4
+    w = World(ctx, rows=K, R=R, eb=8, orset=False, seed=9)
+    try:
+        A = random_pnc(rng, K, R, 8, absent=False, lo=0, hi=1 << 40), random_pnc(rng, K, R, 8, absent=False, lo=0, hi=1 << 40)
+        w.write(*A)
+        keys = [b"t-%d" % i for i in range(K)]
+        w.add_keys(keys, [0] * K, list(range(K)))
+        batches, states = [], [orc.pnc_values(*A)[0]]
+        P, N = A
+        for _ in range(4):
+            BP, BN = random_pnc(rng, 256, R, 8, lo=0, hi=1 << 41), random_pnc(rng, 256, R, 8, lo=0, hi=1 << 41)
+            idx = rng.integers(0, K, 256).astype(np.uint32)
+            batches.append((BP, BN, idx))
+            P, N = orc.pnc_merge(P, N, BP, BN, idx)
+            states.append(orc.pnc_values(P, N)[0])
+        q = [keys[i] for i in rng.integers(0, K, 700)] + [b"missing"]
+        rows = [int(k[2:]) for k in q[:-1]]
+        want = [np.append(s[rows], 0) for s in states]
+        errors = []
+
+        def reader():
+            try:
+                for _ in range(30):
+                    value, status, kind = w.node.query_keys(w.ks, q)
+                    if not (status[:-1] == OK).all() or status[-1] != NO_KEY or not any(np.array_equal(value, x) for x in want):
+                        errors.append("an answer matches no merge boundary")
+                        return
+            except Exception as e:  # noqa: BLE001
+                errors.append(repr(e))
+
+        def merger():
+            try:
+                for BP, BN, idx in batches:
+                    w.pnc.merge_rows(BP, BN, idx)
+            except Exception as e:  # noqa: BLE001
+                errors.append(repr(e))
+
+        threads = [threading.Thread(target=f) for f in (reader, reader, merger)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join(timeout=100)
+        assert not any(t.is_alive() for t in threads), "a caller did not finish"
+        assert not errors, errors
+        value, status, kind = w.node.query_keys(w.ks, q)
+        assert np.array_equal(value, want[-1])
+    finally:
+        w.close()
+
+
+# ---- under the 4-bit string hash ---------------------------------------------------------------------------------
+def collision_scenario(ctx):
+    """200 keys in 16 probe chains: every status against the model and the composed path."""
+    w = World(ctx, rows=256, R=3, eb=8, seed=11)
+    try:
+        keys = [b"key-%03d" % i for i in range(200)] + [b"key-%03d" % i + b"x" * (1 + i % 40) for i in range(0, 200, 7)]
+        types = [i % 4 == 3 for i in range(len(keys))]
+        w.add_keys(keys, [int(t) for t in types], [(i % 5) if t else i for i, t in enumerate(types)])
+        w.create([b"unregistered-%d" % i for i in range(20)])
+        P = w.P.copy()
+        P[0, :3] = np.iinfo(np.int64).max, 1, -5  # key-000's Get overflows
+        w.write(P, w.N)
+        w.ops([(s, ADD, b"el-%d" % j) for s in range(5) for j in range(8)] + [(1, REMOVE, b"el-3"), (2, ADD, None)])
+        rng = np.random.default_rng(12)
+        pool = [(k, (None, b"el-3", b"el-9", NA)[(i // 4) % 4]) for i, k in enumerate(keys)]  # every fourth key is an OR-Set
+        pool += [(b"unregistered-%d" % i, None) for i in range(20)] + [(b"absent-%d" % i, b"el-1") for i in range(30)] + [(b"key-001\0", None)]
+        order = rng.permutation(len(pool) * 2) % len(pool)
+        value, status, kind, guid = w.check([pool[i][0] for i in order], [pool[i][1] for i in order])
+        assert set(status.tolist()) == {OK, NO_KEY, NO_CRDT, OVERFLOW, NO_ARG}
+    finally:
+        w.close()
+
+
+def test_statuses_with_hash_collisions():
+    """The test build's string hash keeps 4 bits (-DJANUS_TEST_HOOKS; tpset_dict.hpp's str_key, which tpset.hip's inserts
+    and query.hip's lookups share): a lookup that hashed differently from the inserts would find nothing, and every probe
+    chain is long.  In a child process through JANUS_GPU_LIB, as test_scale_and_random_parity_with_hash_collisions."""
+    lib = ROOT / "janus-crdt_amd" / "lib" / "libjanusgpu_test.so"
+    assert lib.exists(), "the test build is made by __graft_entry__.build()"
+    code = ("import sys; sys.path[:0] = [%r, %r]\n"
+            "import janus_gpu as jg, test_query_keys_gpu as t\n"
+            "assert 'libjanusgpu_test' in str(jg.LIB_PATH)\n"
+            "ctx = jg.Context(0)\nt.collision_scenario(ctx)\nctx.close()\nprint('PARITY OK')\n"
+            % (str(ROOT / "janus-crdt_amd"), str(ROOT / "tests")))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=240, env=dict(os.environ, JANUS_GPU_LIB=str(lib)),
+                         cwd=str(ROOT / "tests"))
+    assert out.returncode == 0 and "PARITY OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
