@@ -7,7 +7,8 @@
 //   k_merge_dense    A = max(A, B) over identity rows.  Reads A.P A.N B.P B.N: 4 x elem_bytes per cell
 //                    (32 B at int64), and writes back only the 128-B lines of A.P / A.N that a cell of B
 //                    raised: up to 2 x elem_bytes more (48 B per cell when every line changes, 32 B for a
-//                    re-delivered batch).  One 16-B vector per array per lane, non-temporal.  This is
+//                    re-delivered batch).  Two halves of one grid: P's workgroups, then N's (two read streams
+//                    at a time); kDenseVecs 16-B vectors of A and of B per lane, non-temporal.  This is
 //                    PNCounter.Merge (PNCounters.cs:131-144).
 //   k_merge_indexed  scatter-max of received rows into their keys (atomicMax: rows may repeat a
 //                    key inside one committed batch, SafeCRDTManager.cs:122-146).
@@ -71,26 +72,46 @@ __device__ __forceinline__ bool group_changed(unsigned long long mask, uint32_t 
     return ((mask >> (lane & (64 - kElideLanes))) & ((1u << kElideLanes) - 1)) != 0;
 }
 
-// Dense merge: nv 16-byte vectors per array, one vector of each array per lane, plus `tail` trailing
-// cells (< 16 B) done by block 0.  Measured on MI355X against grid-stride / multi-vector-per-lane /
-// block-chunk variants (tools/tune_pnc.hip, profiles/r01/tune_pnc_*.txt): a flat grid with one
-// vector per lane and non-temporal loads/stores (every byte is touched once) was fastest.  P and N are
-// elided separately (a batch that only raises P leaves N unwritten); the bounds test is a predicate, not a
-// branch around the ballots, so every lane of a wave that loaded data votes (lanes past nv vote unchanged).
+// Dense merge: nv 16-byte vectors per array plus `tail` trailing cells (< 16 B) done by block 0.  The grid is two
+// halves of `half` workgroups: the first merges P (A.P, B.P), the second N (A.N, B.N), so in dispatch order the chip
+// streams two arrays at a time, then the other two, instead of four at once.  A workgroup takes kDenseVecs vectors
+// per lane, kDenseBlock apart (a wave-instruction reads 1 KB contiguous, an aligned group of kElideLanes lanes is one
+// 128-B line), every load issued before the first use.  Measured on MI355X in the regime the kernel now mostly
+// runs in — four read streams, nothing stored — and behind batches that raise one column per key or every cell
+// (tools/tune_pnc.hip `steady`, profiles/r08/tune_pnc_steady*.txt), against the four-streams-per-workgroup shape it
+// had since round 1 and against 2 / 4 vectors per lane, workgroups of 512 / 1024, bounded grids (grid-stride and
+// block-chunk walks), P then N inside a workgroup, default-policy loads and LDS-DMA loads: see DESIGN.md §4 for
+// what each measured.  P and N are elided separately as before (each half writes only its own array); the bounds
+// test is a predicate, not a branch around the ballot, so every lane of a wave that loaded data votes (lanes past
+// nv vote unchanged).
+constexpr int kDenseVecs = 1;     // 16-B vectors of each array per lane
+constexpr int kDenseBlock = 256;  // lanes per workgroup: kDenseVecs x kDenseBlock vectors per workgroup
+
 template <int EB>
-__global__ __launch_bounds__(kBlock) void k_merge_dense(uint4* __restrict__ AP, uint4* __restrict__ AN,
-                                                        const uint4* __restrict__ BP, const uint4* __restrict__ BN,
-                                                        uint64_t nv, uint32_t tail) {
+__global__ __launch_bounds__(kDenseBlock) void k_merge_dense(uint4* __restrict__ AP, uint4* __restrict__ AN,
+                                                             const uint4* __restrict__ BP, const uint4* __restrict__ BN,
+                                                             uint64_t nv, uint32_t tail, uint32_t half) {
     using T = typename Elem<EB>::T;
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool in = i < nv;
-    uint4 ap{}, bp{}, an{}, bn{};
-    if (in) ap = nt_load(AP + i), bp = nt_load(BP + i), an = nt_load(AN + i), bn = nt_load(BN + i);
-    const uint4 mp = vmax<EB>(ap, bp), mn = vmax<EB>(an, bn);
-    const unsigned long long cp = __ballot(in && differs(mp, ap)), cn = __ballot(in && differs(mn, an));
+    const bool isN = blockIdx.x >= half;
+    uint4* const A = isN ? AN : AP;
+    const uint4* const B = isN ? BN : BP;
+    const uint64_t base = (uint64_t)(blockIdx.x - (isN ? half : 0)) * (kDenseVecs * kDenseBlock) + threadIdx.x;
+    uint4 a[kDenseVecs], b[kDenseVecs];
+    bool in[kDenseVecs];
+#pragma unroll
+    for (int u = 0; u < kDenseVecs; ++u) {
+        const uint64_t i = base + u * kDenseBlock;
+        in[u] = i < nv;
+        a[u] = b[u] = uint4{};
+        if (in[u]) a[u] = nt_load(A + i), b[u] = nt_load(B + i);
+    }
     const uint32_t lane = threadIdx.x & 63;
-    if (in && group_changed(cp, lane)) nt_store(AP + i, mp);
-    if (in && group_changed(cn, lane)) nt_store(AN + i, mn);
+#pragma unroll
+    for (int u = 0; u < kDenseVecs; ++u) {
+        const uint4 m = vmax<EB>(a[u], b[u]);
+        const unsigned long long c = __ballot(in[u] && differs(m, a[u]));
+        if (in[u] && group_changed(c, lane)) nt_store(A + base + u * kDenseBlock, m);
+    }
     if (blockIdx.x == 0 && threadIdx.x < tail) {
         T* ap = reinterpret_cast<T*>(AP + nv) + threadIdx.x;
         T* an = reinterpret_cast<T*>(AN + nv) + threadIdx.x;
@@ -390,15 +411,16 @@ void launch_merge_dense(jg_ctx* ctx, uint32_t eb, void* AP, void* AN, const void
     const uint64_t bytes = n_cells * eb;
     const uint64_t nv = bytes / 16;
     const uint32_t tail = (uint32_t)((bytes - nv * 16) / eb);
-    const uint64_t blocks = (nv + kBlock - 1) / kBlock;
-    JG_REQUIRE(blocks < 0xFFFFFFFFull, JG_EINVAL, "merge: %llu cells exceed one launch", (unsigned long long)n_cells);
-    const unsigned grid = blocks ? (unsigned)blocks : 1u;
+    constexpr uint64_t per = (uint64_t)kDenseVecs * kDenseBlock;
+    const uint64_t blocks = (nv + per - 1) / per;  // per array: the grid holds P's, then N's
+    JG_REQUIRE(2 * blocks < 0xFFFFFFFFull, JG_EINVAL, "merge: %llu cells exceed one launch", (unsigned long long)n_cells);
+    const unsigned half = blocks ? (unsigned)blocks : 1u;  // block 0 exists for the trailing cells
     if (eb == 8)
-        hipLaunchKernelGGL(k_merge_dense<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
-                           (const uint4*)BN, nv, tail);
+        hipLaunchKernelGGL(k_merge_dense<8>, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
+                           (const uint4*)BN, nv, tail, half);
     else
-        hipLaunchKernelGGL(k_merge_dense<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
-                           (const uint4*)BN, nv, tail);
+        hipLaunchKernelGGL(k_merge_dense<4>, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
+                           (const uint4*)BN, nv, tail, half);
     JG_HIP(hipGetLastError());
 }
 

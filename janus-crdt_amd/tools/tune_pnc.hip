@@ -1,10 +1,12 @@
 // tune_pnc.hip — dev tool: interleaved A/B timing of PN-Counter dense-merge kernel variants on the
 // C2 shape (10M keys x 64 replicas, int64), one process, hipEvents per launch, median of rounds.
 // `tune_pnc <rounds> elide`: the store-elision sweep instead (granularity x share of cells changed per launch).
+// `tune_pnc <rounds> steady`: the read-only steady state bench.py times (data x cadence, then the read-side shapes).
 // Build: make -C janus-crdt_amd build/tune_pnc (hipcc -O3 --offload-arch=gfx950) ; run on the GPU box.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -253,6 +255,338 @@ int elide_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int round
     return ok ? 0 : 1;
 }
 
+// ---- read-only steady state (`tune_pnc <rounds> steady`) -------------------------------------------------
+// The regime bench.py times: launches back to back on a batch that is already merged, so a launch reads the four
+// arrays and stores nothing.  Part 1 sets the elide sweep's protocol (one launch per event pair behind a fill of
+// B, the tool's cells) beside bench.py's (5 untimed launches, then 20 between one event pair, k_synth_pnc's cells).
+// Part 2 times read-side shapes of the per-line-eliding kernel in the bench's regime and, behind a fill as in the
+// elide sweep, on the one-column and the 100 % pattern.
+
+constexpr unsigned long long kBenchSeed = 0x4A414E5553ull;  // bench.py SEED
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31; return x;
+}
+
+// csrc/synth.hip k_synth_pnc's cell i of array `which` (0 local P, 1 local N, 2 received P, 3 received N)
+__device__ __forceinline__ long long synth_cell(unsigned long long i, unsigned which) {
+    const unsigned long long h = mix64(kBenchSeed + (((i << 2) | which) + 1) * 0x9E3779B97F4A7C15ull);
+    if (h % 100 < 30) return which < 2 ? 0 : (long long)(1ull << 63);
+    return (long long)((h >> 33) % 2147483647ull);
+}
+
+__global__ __launch_bounds__(256) void k_synth(v2* X, v2* Y, unsigned long long nv, unsigned which0) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nv) return;
+    X[i] = v2{synth_cell(2 * i, which0), synth_cell(2 * i + 1, which0)};
+    Y[i] = v2{synth_cell(2 * i, which0 + 1), synth_cell(2 * i + 1, which0 + 1)};
+}
+
+__device__ __forceinline__ bool vdiff(v2 a, v2 b) { return a.x != b.x || a.y != b.y; }
+
+// One trip of a workgroup over both counters: U vectors of each array per lane at base + u * B + thread, so a
+// wave-instruction reads 1 KB contiguous and an aligned group of 8 lanes is one 128-B line; every load is issued
+// before the first use.  `base` is the same in every lane of the workgroup (the ballots need whole waves).
+template <int U, int B, bool NTA, bool NTB>
+__device__ __forceinline__ void trip_pn(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long base, unsigned long long nv) {
+    v2 ap[U], bp[U], an[U], bn[U];
+    bool in[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned long long i = base + u * B + threadIdx.x;
+        in[u] = i < nv;
+        ap[u] = bp[u] = an[u] = bn[u] = 0;
+        if (in[u]) ap[u] = ld<NTA>(AP + i), bp[u] = ld<NTB>(BP + i), an[u] = ld<NTA>(AN + i), bn[u] = ld<NTB>(BN + i);
+    }
+    const unsigned lane = threadIdx.x & 63;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned long long i = base + u * B + threadIdx.x;
+        const v2 mp = vmax(ap[u], bp[u]), mn = vmax(an[u], bn[u]);
+        const unsigned long long cp = __ballot(in[u] && vdiff(mp, ap[u])), cn = __ballot(in[u] && vdiff(mn, an[u]));
+        if (in[u] && group_changed<8>(cp, lane)) st<true>(AP + i, mp);
+        if (in[u] && group_changed<8>(cn, lane)) st<true>(AN + i, mn);
+    }
+}
+
+// The same trip over one counter (the two-streams variants).
+template <int U, int B>
+__device__ __forceinline__ void trip_one(v2* A, const v2* Bv, unsigned long long base, unsigned long long nv) {
+    v2 a[U], b[U];
+    bool in[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned long long i = base + u * B + threadIdx.x;
+        in[u] = i < nv;
+        a[u] = b[u] = 0;
+        if (in[u]) a[u] = ld<true>(A + i), b[u] = ld<true>(Bv + i);
+    }
+    const unsigned lane = threadIdx.x & 63;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned long long i = base + u * B + threadIdx.x;
+        const v2 m = vmax(a[u], b[u]);
+        const unsigned long long c = __ballot(in[u] && vdiff(m, a[u]));
+        if (in[u] && group_changed<8>(c, lane)) st<true>(A + i, m);
+    }
+}
+
+// flat grid: workgroup b takes the B * U vectors from b * B * U
+template <int U, int B, bool NTA, bool NTB>
+__global__ __launch_bounds__(B) void k_rflat(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv) {
+    trip_pn<U, B, NTA, NTB>(AP, AN, BP, BN, (unsigned long long)blockIdx.x * (B * U), nv);
+}
+
+// bounded grid, grid-stride walk: trips of B * U vectors, gridDim.x trips apart (k_stride with elision)
+template <int U, int B>
+__global__ __launch_bounds__(B) void k_rstride(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv) {
+    const unsigned long long step = (unsigned long long)gridDim.x * (B * U);
+    for (unsigned long long base = (unsigned long long)blockIdx.x * (B * U); base < nv; base += step) trip_pn<U, B, true, true>(AP, AN, BP, BN, base, nv);
+}
+
+// bounded grid, block-chunk walk: workgroup b owns [b * per_block, (b + 1) * per_block) (k_chunk with elision);
+// per_block is a multiple of B * U, so trips stay line-aligned
+template <int U, int B>
+__global__ __launch_bounds__(B) void k_rchunk(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv, unsigned long long per_block) {
+    const unsigned long long beg = (unsigned long long)blockIdx.x * per_block;
+    const unsigned long long end = beg + per_block < nv ? beg + per_block : nv;
+    for (unsigned long long base = beg; base < end; base += B * U) trip_pn<U, B, true, true>(AP, AN, BP, BN, base, end);
+}
+
+// two streams at a time, by halves of the grid: workgroups [0, half) merge P, [half, 2 * half) merge N
+template <int U, int B>
+__global__ __launch_bounds__(B) void k_rhalves(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv, unsigned half) {
+    const bool isN = blockIdx.x >= half;
+    trip_one<U, B>(isN ? AN : AP, isN ? BN : BP, (unsigned long long)(blockIdx.x - (isN ? half : 0)) * (B * U), nv);
+}
+
+// two streams at a time, per workgroup: P of the workgroup's B * U vectors, then N of the same vectors
+template <int U, int B>
+__global__ __launch_bounds__(B) void k_rpn(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * (B * U);
+    trip_one<U, B>(AP, BP, base, nv);
+    trip_one<U, B>(AN, BN, base, nv);
+}
+
+// LDS-DMA: the four vectors go global -> LDS (each wave fills its own 1 KB of each array's image, base + lane x 16 B)
+// and are read back by the lane that asked for them; the barrier drains the loads.  AUX: the loads' cache policy
+// bits (0 default, 2 non-temporal).
+typedef __attribute__((address_space(1))) const void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+template <int B, unsigned AUX>
+__global__ __launch_bounds__(B) void k_rlds(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv) {
+    __shared__ v2 img[4][B];
+    const unsigned long long i = (unsigned long long)blockIdx.x * B + threadIdx.x;
+    const bool in = i < nv;
+    const unsigned w0 = threadIdx.x & ~63u, lane = threadIdx.x & 63;
+    if (in) {
+        __builtin_amdgcn_global_load_lds((gptr_t)(AP + i), (lptr_t)&img[0][w0], 16, 0, AUX);
+        __builtin_amdgcn_global_load_lds((gptr_t)(BP + i), (lptr_t)&img[1][w0], 16, 0, AUX);
+        __builtin_amdgcn_global_load_lds((gptr_t)(AN + i), (lptr_t)&img[2][w0], 16, 0, AUX);
+        __builtin_amdgcn_global_load_lds((gptr_t)(BN + i), (lptr_t)&img[3][w0], 16, 0, AUX);
+    }
+    __syncthreads();
+    v2 ap = 0, bp = 0, an = 0, bn = 0;
+    if (in) ap = img[0][threadIdx.x], bp = img[1][threadIdx.x], an = img[2][threadIdx.x], bn = img[3][threadIdx.x];
+    const v2 mp = vmax(ap, bp), mn = vmax(an, bn);
+    const unsigned long long cp = __ballot(in && vdiff(mp, ap)), cn = __ballot(in && vdiff(mn, an));
+    if (in && group_changed<8>(cp, lane)) st<true>(AP + i, mp);
+    if (in && group_changed<8>(cn, lane)) st<true>(AN + i, mn);
+}
+
+// csrc/pnc.hip's k_merge_dense<8> as it stands (uint4 vectors, __restrict__, the tail cells' branch; tail = 0
+// here): the library's own instructions beside k_elide<8,256>, which the sweeps take for them
+__global__ __launch_bounds__(256) void k_lib(uint4* __restrict__ AP, uint4* __restrict__ AN, const uint4* __restrict__ BP,
+                                             const uint4* __restrict__ BN, unsigned long long nv, unsigned tail) {
+    const auto ldv = [](const uint4* p) { return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v2*>(p))); };
+    const auto stv = [](uint4* p, uint4 v) { __builtin_nontemporal_store(__builtin_bit_cast(v2, v), reinterpret_cast<v2*>(p)); };
+    const auto mx = [](uint4 a, uint4 b) { return __builtin_bit_cast(uint4, vmax(__builtin_bit_cast(v2, a), __builtin_bit_cast(v2, b))); };
+    const auto differs = [](uint4 a, uint4 b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0; };
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < nv;
+    uint4 ap{}, bp{}, an{}, bn{};
+    if (in) ap = ldv(AP + i), bp = ldv(BP + i), an = ldv(AN + i), bn = ldv(BN + i);
+    const uint4 mp = mx(ap, bp), mn = mx(an, bn);
+    const unsigned long long cp = __ballot(in && differs(mp, ap)), cn = __ballot(in && differs(mn, an));
+    const unsigned lane = threadIdx.x & 63;
+    if (in && group_changed<8>(cp, lane)) stv(AP + i, mp);
+    if (in && group_changed<8>(cn, lane)) stv(AN + i, mn);
+    if (blockIdx.x == 0 && threadIdx.x < tail) {
+        long long* a = reinterpret_cast<long long*>(AP + nv) + threadIdx.x;
+        long long* b = reinterpret_cast<long long*>(AN + nv) + threadIdx.x;
+        const long long p = reinterpret_cast<const long long*>(BP + nv)[threadIdx.x];
+        const long long n = reinterpret_cast<const long long*>(BN + nv)[threadIdx.x];
+        if (p > *a) *a = p;
+        if (n > *b) *b = n;
+    }
+}
+void L_lib(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    hipLaunchKernelGGL(k_lib, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, (uint4*)a, (uint4*)b, (const uint4*)c, (const uint4*)d, nv, 0u);
+}
+
+unsigned blocks_of(unsigned long long nv, unsigned long long per) { return (unsigned)((nv + per - 1) / per); }
+
+template <int U, int B, bool NTA, bool NTB>
+void L_rflat(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    hipLaunchKernelGGL((k_rflat<U, B, NTA, NTB>), dim3(blocks_of(nv, B * U)), dim3(B), 0, s, a, b, c, d, nv);
+}
+template <int U, int B, int PER_CU>
+void L_rstride(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    hipLaunchKernelGGL((k_rstride<U, B>), dim3(std::min(blocks_of(nv, B * U), (unsigned)(num_cus * PER_CU))), dim3(B), 0, s, a, b, c, d, nv);
+}
+template <int U, int B, int PER_CU>
+void L_rchunk(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    const unsigned long long trip = B * U, want = (unsigned long long)num_cus * PER_CU;
+    const unsigned long long per = std::max<unsigned long long>((nv + want * trip - 1) / (want * trip), 1) * trip;
+    hipLaunchKernelGGL((k_rchunk<U, B>), dim3(blocks_of(nv, per)), dim3(B), 0, s, a, b, c, d, nv, per);
+}
+template <int U, int B>
+void L_rhalves(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    const unsigned half = blocks_of(nv, B * U);
+    hipLaunchKernelGGL((k_rhalves<U, B>), dim3(2 * half), dim3(B), 0, s, a, b, c, d, nv, half);
+}
+template <int U, int B>
+void L_rpn(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    hipLaunchKernelGGL((k_rpn<U, B>), dim3(blocks_of(nv, B * U)), dim3(B), 0, s, a, b, c, d, nv);
+}
+template <int B, unsigned AUX>
+void L_rlds(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
+    hipLaunchKernelGGL((k_rlds<B, AUX>), dim3(blocks_of(nv, B)), dim3(B), 0, s, a, b, c, d, nv);
+}
+
+float median(std::vector<float> v) {
+    std::sort(v.begin(), v.end());
+    return v[v.size() / 2];
+}
+
+int steady_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int rounds) {
+    hipStream_t s;
+    CK(hipStreamCreate(&s));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    if (rounds > 500) rounds = 500;  // the generation stays below 2^16 (k_fill_b)
+    unsigned* bad;
+    CK(hipMalloc(&bad, 4));
+    CK(hipMemsetAsync(bad, 0, 4, s));
+    long long gen = 0;
+    const unsigned g256 = (unsigned)((nv + 255) / 256);
+    const Variant parent = {"flat U1 B256 (parent)", L_elide<8>};
+
+    // data: the tool's cells (A = B = the bases, so a fill at 0 % rewrites B's values) or the bench's (A merged once)
+    const auto set_data = [&](bool bench) {
+        if (bench) {
+            hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, AP, AN, nv, 0u);
+            hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, BP, BN, nv, 2u);
+            parent.launch(AP, AN, BP, BN, nv, s, 0);
+        } else {
+            hipLaunchKernelGGL(k_fill_b, dim3(g256), dim3(256), 0, s, AP, AN, nv, 0, 0ull, 0ll);
+            hipLaunchKernelGGL(k_fill_b, dim3(g256), dim3(256), 0, s, BP, BN, nv, 0, 0ull, 0ll);
+        }
+    };
+    // interleaved: an untimed write-only fill of B, then one launch between an event pair (the elide sweep)
+    const auto t_interleaved = [&](const Variant& v, bool bench, int mode, unsigned long long thresh) {
+        if (bench) hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, BP, BN, nv, 2u);
+        else hipLaunchKernelGGL(k_fill_b, dim3(g256), dim3(256), 0, s, BP, BN, nv, mode, thresh, ++gen);
+        CK(hipEventRecord(e0, s));
+        v.launch(AP, AN, BP, BN, nv, s, 0);
+        CK(hipEventRecord(e1, s));
+        CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        return ms;
+    };
+    // back to back: 5 untimed launches, a fence, 20 launches between one event pair (bench.py timed())
+    const auto t_b2b = [&](const Variant& v) {
+        for (int i = 0; i < 5; ++i) v.launch(AP, AN, BP, BN, nv, s, 0);
+        CK(hipStreamSynchronize(s));
+        CK(hipEventRecord(e0, s));
+        for (int i = 0; i < 20; ++i) v.launch(AP, AN, BP, BN, nv, s, 0);
+        CK(hipEventRecord(e1, s));
+        CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        return ms / 20;
+    };
+    const auto check = [&] { hipLaunchKernelGGL(k_count_behind, dim3(g256), dim3(256), 0, s, AP, AN, BP, BN, nv, bad); };
+
+    std::printf("C2 shape: 10M keys x 64 replicas, int64; every launch reads 4 x 5.12 GB; median of %d rounds, ms per launch\n\n", rounds);
+    std::printf("Part 1: the parent kernel (k_elide<8,256>), nothing changed; A/A = the same kernel timed twice per round\n");
+    std::printf("%-28s %12s %8s %14s %8s\n", "data", "interleaved", "A/A", "back to back", "A/A");
+    for (int bench = 0; bench < 2; ++bench) {
+        set_data(bench);
+        std::vector<float> ti[2], tb[2];
+        for (int r = -1; r < rounds; ++r)
+            for (int k = 0; k < 2; ++k) {
+                const float a = t_interleaved(parent, bench, 0, 0), b = t_b2b(parent);
+                if (r >= 0) ti[k].push_back(a), tb[k].push_back(b);
+            }
+        const float i0 = median(ti[0]), i1 = median(ti[1]), b0 = median(tb[0]), b1 = median(tb[1]);
+        std::printf("%-28s %12.3f %8.3f %14.3f %8.3f\n", bench ? "bench (k_synth_pnc, merged)" : "tool (k_fill_b bases)", i0, std::fabs(i1 - i0), b0, std::fabs(b1 - b0));
+    }
+
+    const std::vector<Variant> vs = {
+        parent,
+        {"csrc/pnc.hip's own body", L_lib},
+        {"flat U2 B256",L_rflat<2, 256, true, true>},
+        {"flat U4 B256", L_rflat<4, 256, true, true>},
+        {"flat U1 B512", L_rflat<1, 512, true, true>},
+        {"flat U1 B1024", L_rflat<1, 1024, true, true>},
+        {"flat U2 B512", L_rflat<2, 512, true, true>},
+        {"flat U4 B1024", L_rflat<4, 1024, true, true>},
+        {"stride U4 B256 8/CU (16KB)", L_rstride<4, 256, 8>},
+        {"stride U2 B256 8/CU (8KB)", L_rstride<2, 256, 8>},
+        {"stride U4 B1024 2/CU (64KB)", L_rstride<4, 1024, 2>},
+        {"stride U1 B256 8/CU (4KB)", L_rstride<1, 256, 8>},
+        {"chunk U4 B256 8/CU", L_rchunk<4, 256, 8>},
+        {"chunk U2 B256 8/CU", L_rchunk<2, 256, 8>},
+        {"chunk U4 B256 64/CU", L_rchunk<4, 256, 64>},
+        {"halves P|N U1 B256", L_rhalves<1, 256>},
+        {"halves P|N U2 B256", L_rhalves<2, 256>},
+        {"P then N U2 B256", L_rpn<2, 256>},
+        {"P then N U4 B256", L_rpn<4, 256>},
+        {"flat U1 B256 A plain B nt", L_rflat<1, 256, false, true>},
+        {"flat U1 B256 A nt B plain", L_rflat<1, 256, true, false>},
+        {"flat U1 B256 both plain", L_rflat<1, 256, false, false>},
+        {"lds-dma U1 B256 default", L_rlds<256, 0>},
+        {"lds-dma U1 B256 nt", L_rlds<256, 2>},
+        {"flat U1 B256 (parent again)", L_elide<8>},
+    };
+    const size_t nvar = vs.size();
+    std::vector<std::vector<float>> t0(nvar), t1(nvar), t2(nvar);
+    // 0 % changed: the bench's data, back to back
+    set_data(true);
+    for (int r = -1; r < rounds; ++r)
+        for (size_t k = 0; k < nvar; ++k) {
+            const float ms = t_b2b(vs[k]);
+            if (r >= 0) t0[k].push_back(ms);
+            else check();
+        }
+    // one column per key and 100 %: the tool's data, each launch behind the fill that raises the pattern's cells
+    set_data(false);
+    for (int pat = 0; pat < 2; ++pat)
+        for (int r = -1; r < rounds; ++r)
+            for (size_t k = 0; k < nvar; ++k) {
+                const float ms = pat == 0 ? t_interleaved(vs[k], false, 1, 0) : t_interleaved(vs[k], false, 0, 1ull << 32);
+                if (r >= 0) (pat == 0 ? t1 : t2)[k].push_back(ms);
+                else check();
+            }
+    std::printf("\nPart 2: read-side shapes, per-line store elision in all of them\n");
+    std::printf("%-30s %22s %22s %22s\n", "", "0 % (bench data,", "one column per key", "100 %");
+    std::printf("%-30s %22s %22s %22s\n", "variant", "back to back)", "(behind a fill)", "(behind a fill)");
+    for (size_t k = 0; k < nvar; ++k) std::printf("%-30s %22.3f %22.3f %22.3f\n", vs[k].name, median(t0[k]), median(t1[k]), median(t2[k]));
+    std::printf("%-30s %22.3f %22.3f %22.3f\n", "A/A spread (parent twice)", std::fabs(median(t0[0]) - median(t0[nvar - 1])),
+                std::fabs(median(t1[0]) - median(t1[nvar - 1])), std::fabs(median(t2[0]) - median(t2[nvar - 1])));
+    std::printf("%-30s %22.3f %22.3f %22.3f\n", "parent, min of rounds", *std::min_element(t0[0].begin(), t0[0].end()),
+                *std::min_element(t1[0].begin(), t1[0].end()), *std::min_element(t2[0].begin(), t2[0].end()));
+    std::printf("%-30s %22.3f %22.3f %22.3f\n", "parent, max of rounds", *std::max_element(t0[0].begin(), t0[0].end()),
+                *std::max_element(t1[0].begin(), t1[0].end()), *std::max_element(t2[0].begin(), t2[0].end()));
+    unsigned h = 0;
+    CK(hipMemcpy(&h, bad, 4, hipMemcpyDeviceToHost));
+    const bool ok = h == 0;
+    std::printf("vectors of A left behind B over every variant and pattern: %u%s\n", h, ok ? " (ok)" : " (WRONG)");
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     const unsigned long long n_cells = 10000000ull * 64, nv = n_cells / 2;
     hipDeviceProp_t prop;
@@ -261,6 +595,7 @@ int main(int argc, char** argv) {
     v2 *AP, *AN, *BP, *BN;
     CK(hipMalloc(&AP, nv * 16)); CK(hipMalloc(&AN, nv * 16)); CK(hipMalloc(&BP, nv * 16)); CK(hipMalloc(&BN, nv * 16));
     if (argc > 2 && std::string(argv[2]) == "elide") return elide_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
+    if (argc > 2 && std::string(argv[2]) == "steady") return steady_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
     CK(hipMemset(AP, 1, nv * 16)); CK(hipMemset(AN, 2, nv * 16)); CK(hipMemset(BP, 3, nv * 16)); CK(hipMemset(BN, 0, nv * 16));
     std::vector<Variant> vs = {
         {"stride U4 B256 g16/CU (prod r1)", L_stride<4, false, false, 256, 16>},
