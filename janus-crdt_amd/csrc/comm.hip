@@ -41,7 +41,7 @@
 #include <thread>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 
 static_assert(sizeof(ncclUniqueId) == 128, "the ABI passes the unique id as 128 bytes");
 
@@ -149,9 +149,7 @@ void wait_stream(jg_comm* c) {
     }
 }
 
-void ensure(jg::DevBuf& b, size_t bytes) {
-    if (b.bytes < bytes) b.alloc(bytes + bytes / 4 + 256);
-}
+using jg::ensure;
 
 uint8_t* pinned(jg_comm* c, size_t bytes) {
     if (c->pin_cap < bytes) {
@@ -241,7 +239,7 @@ void post_runs(jg_comm* c, const Plan& pl, uint32_t k, uint32_t j, const char* s
         if (p != c->rank) sb[p] = pl.send_n[(size_t)p * k + j] * es, rb[p] = pl.recv_n[(size_t)p * k + j] * es, ts += sb[p], tr += rb[p];
     uint8_t* h = pinned(c, ts + tr + 64);
     uint8_t* hs = h;
-    uint8_t* hr = h + ((ts + 63) & ~63ull);
+    uint8_t* hr = h + jg::round_up(ts, 64);
     uint64_t o = 0;
     for (uint32_t p = 0; p < W; ++p)
         if (sb[p]) {

@@ -24,7 +24,7 @@
 #include <cstring>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "sha256_device.hpp"
 
 namespace {
@@ -260,10 +260,8 @@ __global__ void __launch_bounds__(kBlock) k_sha_chain(const uint4* __restrict__ 
     out[2 * u + 1] = make_uint4(bswap(H[4]), bswap(H[5]), bswap(H[6]), bswap(H[7]));
 }
 
-uint32_t grid_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 // k_sha_chain: one wave per workgroup, so the few chain waves spread over as many CUs as there are waves
 constexpr uint32_t kChainBlock = 64;
-uint32_t chain_grid(uint64_t n) { return (uint32_t)((n + kChainBlock - 1) / kChainBlock); }
 
 void check_first(uint64_t n, uint64_t n_upd, const uint64_t* first) {
     JG_REQUIRE(first[0] == 0, JG_EINVAL, "update digests: first[0] must be 0");
@@ -290,8 +288,6 @@ uint64_t chain_offsets(const uint64_t* first, uint64_t n_upd, uint64_t* boff) {
     return boff[n_upd];
 }
 
-inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
-
 // The second level from per-payload digests already on the device (D: n state-word digests, zeros for null):
 // update digests to the host (synchronous).
 void chain_digests(jg_ctx* ctx, const uint4* D, uint64_t n, uint64_t n_upd, const uint64_t* first, uint8_t* digest) {
@@ -299,11 +295,12 @@ void chain_digests(jg_ctx* ctx, const uint4* D, uint64_t n, uint64_t n_upd, cons
     std::vector<uint64_t> hb(2 * (n_upd + 1));
     std::memcpy(hb.data(), first, (n_upd + 1) * 8);
     const uint64_t B = chain_offsets(first, n_upd, hb.data() + n_upd + 1);
-    char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch3, n_upd * 32 + hb.size() * 8 + B * 256 + 512));
-    auto* out = reinterpret_cast<uint4*>(s);
-    auto* d_first = reinterpret_cast<uint64_t*>(s + n_upd * 32);
+    uint4 *out, *KW;
+    uint64_t* d_first;  // first[], then boff[]
+    jg::Layout L;
+    L.add(out, 2 * n_upd, 16), L.add(d_first, hb.size(), 8), L.add(KW, B * 16);
+    L.bind(jg::scratch(ctx, ctx->scratch3, L.bytes() + 256));
     uint64_t* d_boff = d_first + n_upd + 1;
-    auto* KW = reinterpret_cast<uint4*>(s + ((n_upd * 32 + hb.size() * 8 + 255) & ~255ull));
     hipStream_t st = ctx->stream;
     // from the context's page-locked write area when it fits (a pageable source is staged by the runtime)
     const void* src = hb.data();
@@ -313,8 +310,8 @@ void chain_digests(jg_ctx* ctx, const uint4* D, uint64_t n, uint64_t n_upd, cons
         src = pin;
     }
     JG_HIP(hipMemcpyAsync(d_first, src, hb.size() * 8, hipMemcpyHostToDevice, st));
-    k_sha_expand<<<grid_for(B), kBlock, 0, st>>>(D, d_first, d_boff, n_upd, KW);
-    k_sha_chain<<<chain_grid(n_upd), kChainBlock, 0, st>>>(KW, d_boff, n_upd, out);
+    k_sha_expand<<<jg::blocks_for(B), kBlock, 0, st>>>(D, d_first, d_boff, n_upd, KW);
+    k_sha_chain<<<jg::blocks_for(n_upd, kChainBlock), kChainBlock, 0, st>>>(KW, d_boff, n_upd, out);
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemcpyAsync(digest, out, n_upd * 32, hipMemcpyDeviceToHost, st));
     JG_HIP(hipStreamSynchronize(st));
@@ -336,18 +333,18 @@ void run_digests(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, con
     std::vector<uint64_t> hb(2 * (n_upd + 1));  // first[] then boff[] (second-level block offsets)
     std::memcpy(hb.data(), first, (n_upd + 1) * 8);
     const uint64_t B = chain_offsets(first, n_upd, hb.data() + n_upd + 1);
-    char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch3, n * 32 + n_upd * 32 + hb.size() * 8 + B * 256 + 512));
-    auto* D = reinterpret_cast<uint4*>(s);
-    auto* out = reinterpret_cast<uint4*>(s + n * 32);
-    auto* d_first = reinterpret_cast<uint64_t*>(s + n * 32 + n_upd * 32);
+    uint4 *D, *out, *KW;
+    uint64_t* d_first;  // first[], then boff[]
+    jg::Layout L;
+    L.add(D, 2 * n, 16), L.add(out, 2 * n_upd, 16), L.add(d_first, hb.size(), 8), L.add(KW, B * 16);
+    L.bind(jg::scratch(ctx, ctx->scratch3, L.bytes() + 256));
     uint64_t* d_boff = d_first + n_upd + 1;
-    auto* KW = reinterpret_cast<uint4*>(s + ((n * 32 + n_upd * 32 + hb.size() * 8 + 255) & ~255ull));
     hipStream_t st = ctx->stream;
     JG_HIP(hipMemcpyAsync(d_first, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, st));
-    if (n) k_sha_msgs<false><<<grid_for(n), kBlock, 0, st>>>(d_bytes, d_off, d_null, n, D);
+    if (n) k_sha_msgs<false><<<jg::blocks_for(n), kBlock, 0, st>>>(d_bytes, d_off, d_null, n, D);
     if (n_upd) {
-        k_sha_expand<<<grid_for(B), kBlock, 0, st>>>(D, d_first, d_boff, n_upd, KW);
-        k_sha_chain<<<chain_grid(n_upd), kChainBlock, 0, st>>>(KW, d_boff, n_upd, out);
+        k_sha_expand<<<jg::blocks_for(B), kBlock, 0, st>>>(D, d_first, d_boff, n_upd, KW);
+        k_sha_chain<<<jg::blocks_for(n_upd, kChainBlock), kChainBlock, 0, st>>>(KW, d_boff, n_upd, out);
     }
     JG_HIP(hipGetLastError());
     if (digest && n_upd) JG_HIP(hipMemcpyAsync(digest, out, n_upd * 32, hipMemcpyDeviceToHost, st));
@@ -368,8 +365,8 @@ void sha256_device(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, u
     if (n == 0) return;
     auto* D = static_cast<uint4*>(jg::scratch(ctx, ctx->scratch3, n * 32 + 256));
     hipStream_t st = ctx->stream;
-    k_sha_msgs<false><<<grid_for(n), kBlock, 0, st>>>(d_bytes, d_off, nullptr, n, D);
-    k_bswap_words<<<std::min<uint64_t>(grid_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
+    k_sha_msgs<false><<<jg::blocks_for(n), kBlock, 0, st>>>(d_bytes, d_off, nullptr, n, D);
+    k_bswap_words<<<std::min<uint64_t>(jg::blocks_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemcpyAsync(out, D, n * 32, hipMemcpyDeviceToHost, st));
 }
@@ -390,10 +387,12 @@ int jg_update_digests(jg_ctx* ctx, uint64_t n, const uint64_t* off, const uint8_
         check_first(n, n_updates, first);
         jg::ensure_device(ctx);
         const uint64_t nb = off[n];
-        char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch, ((nb + 15) & ~15ull) + (n + 1) * 8 + n + 256));
-        auto* d_bytes = reinterpret_cast<uint8_t*>(s);
-        auto* d_off = reinterpret_cast<uint64_t*>(s + ((nb + 15) & ~15ull));
-        uint8_t* d_null = is_null ? reinterpret_cast<uint8_t*>(d_off + n + 1) : nullptr;
+        uint8_t *d_bytes, *d_null;
+        uint64_t* d_off;
+        jg::Layout L;
+        L.add(d_bytes, nb, 16), L.add(d_off, n + 1, 16), L.add(d_null, n, 1);
+        L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 256));
+        if (!is_null) d_null = nullptr;
         hipStream_t st = ctx->stream;
         if (nb) JG_HIP(hipMemcpyAsync(d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
         JG_HIP(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
@@ -414,15 +413,17 @@ int jg_sha256_batch(jg_ctx* ctx, uint64_t n, const uint64_t* off, const uint8_t*
         if (n == 0) return;
         jg::ensure_device(ctx);
         const uint64_t nb = off[n];
-        char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch, ((nb + 15) & ~15ull) + (n + 1) * 8 + n * 32 + 256));
-        auto* d_bytes = reinterpret_cast<uint8_t*>(s);
-        auto* d_off = reinterpret_cast<uint64_t*>(s + ((nb + 15) & ~15ull));
-        auto* D = reinterpret_cast<uint4*>(s + ((((nb + 15) & ~15ull) + (n + 1) * 8 + 15) & ~15ull));
+        uint8_t* d_bytes;
+        uint64_t* d_off;
+        uint4* D;
+        jg::Layout L;
+        L.add(d_bytes, nb, 16), L.add(d_off, n + 1, 16), L.add(D, 2 * n, 16);
+        L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 256));
         hipStream_t st = ctx->stream;
         if (nb) JG_HIP(hipMemcpyAsync(d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
         JG_HIP(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-        k_sha_msgs<false><<<grid_for(n), kBlock, 0, st>>>(d_bytes, d_off, nullptr, n, D);
-        k_bswap_words<<<std::min<uint64_t>(grid_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
+        k_sha_msgs<false><<<jg::blocks_for(n), kBlock, 0, st>>>(d_bytes, d_off, nullptr, n, D);
+        k_bswap_words<<<std::min<uint64_t>(jg::blocks_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemcpyAsync(out, D, n * 32, hipMemcpyDeviceToHost, st));
         JG_HIP(hipStreamSynchronize(st));
@@ -443,10 +444,10 @@ int jg_update_digests_of(jg_ctx* ctx, uint64_t n, const uint8_t* msg_digest, con
         hipStream_t st = ctx->stream;
         if (n) {
             JG_HIP(hipMemcpyAsync(D, msg_digest, n * 32, hipMemcpyHostToDevice, st));
-            k_bswap_words<<<std::min<uint64_t>(grid_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
+            k_bswap_words<<<std::min<uint64_t>(jg::blocks_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
             if (is_null) {  // a null payload hashes as 32 zero bytes whatever its row holds
                 JG_HIP(hipMemcpyAsync(d_null, is_null, n, hipMemcpyHostToDevice, st));
-                k_zero_null<<<grid_for(n), kBlock, 0, st>>>(D, d_null, n);
+                k_zero_null<<<jg::blocks_for(n), kBlock, 0, st>>>(D, d_null, n);
             }
             JG_HIP(hipGetLastError());
         }
@@ -492,10 +493,10 @@ int jg_waves_update_digests(const jg_wave* const* waves, uint64_t n_waves, const
             const uint64_t nu = n_updates[k];
             std::memcpy(&hm[moff[k]], first[k], (nu + 1) * 8);
             blocks[k] = chain_offsets(first[k], nu, &hm[moff[k] + nu + 1]);
-            slot = std::max(slot, align256(waves[k]->n * 32) + blocks[k] * 256);
+            slot = std::max(slot, jg::round_up(waves[k]->n * 32, 256) + blocks[k] * 256);
         }
-        slot = align256(slot);
-        const uint64_t m_bytes = align256(hm.size() * 8), o_bytes = align256(ooff[n_waves]);
+        slot = jg::round_up(slot, 256);
+        const uint64_t m_bytes = jg::round_up(hm.size() * 8, 256), o_bytes = jg::round_up(ooff[n_waves], 256);
         jg::ensure_device(ctx);
         char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch3, m_bytes + o_bytes + 2 * slot + 256));
         auto* d_meta = reinterpret_cast<uint64_t*>(s);
@@ -524,15 +525,15 @@ int jg_waves_update_digests(const jg_wave* const* waves, uint64_t n_waves, const
             const int sl = (int)(k & 1);
             char* base = s + m_bytes + o_bytes + sl * slot;
             auto* D = reinterpret_cast<uint4*>(base);
-            auto* KW = reinterpret_cast<uint4*>(base + align256(w->n * 32));
+            auto* KW = reinterpret_cast<uint4*>(base + jg::round_up(w->n * 32, 256));
             const uint64_t* d_first = d_meta + moff[k];
             const uint64_t* d_boff = d_first + nu + 1;
             if (k >= 2) JG_HIP(hipStreamWaitEvent(s1, ctx->chain_free[sl], 0));
-            if (w->n) k_sha_msgs<false><<<grid_for(w->n), kBlock, 0, s1>>>(w->bytes.as<uint8_t>(), w->off.as<uint64_t>(), nullptr, w->n, D);
-            if (nu) k_sha_expand<<<grid_for(blocks[k]), kBlock, 0, s1>>>(D, d_first, d_boff, nu, KW);
+            if (w->n) k_sha_msgs<false><<<jg::blocks_for(w->n), kBlock, 0, s1>>>(w->bytes.as<uint8_t>(), w->off.as<uint64_t>(), nullptr, w->n, D);
+            if (nu) k_sha_expand<<<jg::blocks_for(blocks[k]), kBlock, 0, s1>>>(D, d_first, d_boff, nu, KW);
             JG_HIP(hipEventRecord(ctx->level1_done[sl], s1));
             JG_HIP(hipStreamWaitEvent(sd, ctx->level1_done[sl], 0));
-            if (nu) k_sha_chain<<<chain_grid(nu), kChainBlock, 0, sd>>>(KW, d_boff, nu, reinterpret_cast<uint4*>(d_out + ooff[k]));
+            if (nu) k_sha_chain<<<jg::blocks_for(nu, kChainBlock), kChainBlock, 0, sd>>>(KW, d_boff, nu, reinterpret_cast<uint4*>(d_out + ooff[k]));
             JG_HIP(hipEventRecord(ctx->chain_free[sl], sd));
         }
         JG_HIP(hipGetLastError());
@@ -553,7 +554,7 @@ int jg_wave_sha256(const jg_wave* w, void* d_out, uint8_t async) {
         JG_REQUIRE(w && (d_out || w->n == 0), JG_EINVAL, "jg_wave_sha256: NULL argument");
         jg::ensure_device(w->ctx);
         hipStream_t st = w->ctx->stream;
-        if (w->n) k_sha_msgs<true><<<grid_for(w->n), kBlock, 0, st>>>(w->bytes.as<uint8_t>(), w->off.as<uint64_t>(), nullptr, w->n,
+        if (w->n) k_sha_msgs<true><<<jg::blocks_for(w->n), kBlock, 0, st>>>(w->bytes.as<uint8_t>(), w->off.as<uint64_t>(), nullptr, w->n,
                                                                       static_cast<uint4*>(d_out));
         JG_HIP(hipGetLastError());
         if (!async) JG_HIP(hipStreamSynchronize(st));

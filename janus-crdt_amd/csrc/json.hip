@@ -49,7 +49,7 @@
 #include <cstring>
 #include <hipcub/hipcub.hpp>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "wire_cursor.hpp"
 
 namespace {
@@ -577,7 +577,8 @@ __global__ void k_gather_cols(const Guid16* __restrict__ cols, const uint32_t* _
     if (c == 0) nout[q] = ncols[row];
 }
 
-unsigned blocks_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+using jg::blocks_for;
+using jg::grow_keep;
 
 // ---- GetLastSynchronizedUpdate().Encode() on the device ----------------------
 // PNCounterMsg.Encode (PNCounters.cs:46-49) of a row: {"pVector":{"<guid D>":P,...},"nVector":{...}}
@@ -755,30 +756,33 @@ hipError_t sort_row_keys(void* tmp, size_t& bytes, const unsigned long long* in,
 }
 
 DeferredLists select_deferred(jg_ctx* ctx, const unsigned long long* marks, uint64_t n, uint64_t n_keys, unsigned long long* count) {
-    JG_REQUIRE(n <= 0x7FFFFFFFull, JG_EINVAL, "sort: %llu entries exceed one radix sort", (unsigned long long)n);
     using ull = unsigned long long;
+    const int items = jg::cub_count(n, "wave entries");
     DeferredLists d{};
     int row_bits = 1;
     while (row_bits < 32 && (1ull << row_bits) < n_keys) ++row_bits;
     d.end_bit = 32 + row_bits;
-    size_t tsel = 0, tsort = 0;
-    JG_HIP(hipcub::DeviceSelect::If(nullptr, tsel, marks, (ull*)nullptr, (ull*)nullptr, (int)n, IsDeferred(), ctx->stream));
-    JG_HIP(sort_row_keys(nullptr, tsort, (const ull*)nullptr, (ull*)nullptr, n, d.end_bit, ctx->stream));
-    const size_t a = (n * 8 + 255) & ~255ull;
-    d.tmp_bytes = std::max(tsel, tsort);
-    char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch3, 2 * a + d.tmp_bytes + 256));
-    d.list = reinterpret_cast<ull*>(s);
-    d.sorted = reinterpret_cast<ull*>(s + a);
-    d.tmp = s + 2 * a;
-    JG_HIP(hipcub::DeviceSelect::If(d.tmp, tsel, marks, d.list, count, (int)n, IsDeferred(), ctx->stream));
+    const auto select = [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceSelect::If(temp, bytes, marks, d.list, count, items, IsDeferred(), ctx->stream);
+    };
+    // the select and the sort that follows it (sort_deferred) share one workspace
+    d.tmp_bytes = std::max(jg::cub_temp_bytes(select), jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                               return sort_row_keys(temp, bytes, (const ull*)nullptr, (ull*)nullptr, n, d.end_bit, ctx->stream);
+                           }));
+    uint8_t* tmp;
+    jg::Layout L;
+    L.add(d.list, n), L.add(d.sorted, n), L.add(tmp, d.tmp_bytes + 256);
+    L.bind(jg::scratch(ctx, ctx->scratch3, L.bytes()));
+    d.tmp = tmp;
+    jg::cub_run(jg::cub_in(d.tmp, d.tmp_bytes), select);
     return d;
 }
 
 // The list comes out of the (stable) select in message order, so a stable sort on the row bits alone gives the
 // order of the whole key (row, then message): 20 bits for 1M keys instead of 52.
 unsigned long long* sort_deferred(jg_ctx* ctx, DeferredLists& d, uint64_t nd) {
-    size_t t = d.tmp_bytes;
-    JG_HIP(sort_row_keys(d.tmp, t, d.list, d.sorted, nd, d.end_bit, ctx->stream));
+    jg::cub_run(jg::cub_in(d.tmp, d.tmp_bytes),
+                [&](void* temp, size_t& bytes) { return sort_row_keys(temp, bytes, d.list, d.sorted, nd, d.end_bit, ctx->stream); });
     return d.sorted;
 }
 
@@ -789,12 +793,14 @@ unsigned long long* sort_keys(jg_ctx* ctx, unsigned long long* keys, uint64_t n,
     int row_bits = 1;
     while (row_bits < 32 && (1ull << row_bits) < n_keys) ++row_bits;
     const int end_bit = 32 + row_bits;
-    size_t temp = 0;
-    JG_HIP(sort_row_keys(nullptr, temp, keys, keys, n, end_bit, ctx->stream));
-    char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch3, temp + n * 8 + 256));
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(s);
-    void* tmp = s + ((n * 8 + 255) & ~255ull);
-    JG_HIP(sort_row_keys(tmp, temp, keys, out, n, end_bit, ctx->stream));
+    unsigned long long* out = nullptr;
+    const auto sort = [&](void* temp, size_t& bytes) { return sort_row_keys(temp, bytes, keys, out, n, end_bit, ctx->stream); };
+    const size_t temp = jg::cub_temp_bytes(sort);
+    uint8_t* tmp;
+    jg::Layout L;
+    L.add(out, n), L.add(tmp, temp);
+    L.bind(jg::scratch(ctx, ctx->scratch3, L.bytes() + 256));
+    jg::cub_run(jg::cub_in(tmp, temp), sort);
     return out;
 }
 
@@ -832,17 +838,6 @@ struct RowFull : jg::Error {};
     jg::fail(JG_EINVAL, "%s %llu is not a PNCounterMsg in the accepted JSON form (JsonException)", what, (unsigned long long)m);
 }
 
-// Grow a wave buffer to `need` bytes keeping the first `keep` bytes (stream-ordered copy).
-void grow_keep(jg_ctx* ctx, jg::DevBuf& b, size_t need, size_t keep) {
-    if (b.bytes >= need) return;
-    jg::DevBuf nb;
-    nb.alloc(need + need / 2);
-    if (keep) JG_HIP(hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream));
-    JG_HIP(hipStreamSynchronize(ctx->stream));
-    std::swap(nb.p, b.p);
-    std::swap(nb.bytes, b.bytes);
-}
-
 // Wave-level device scratch: status words, pass A's deferred marks and the roll-back slots (n messages),
 // pass A's per-message entries and its list of messages for pass B to parse again.
 struct WaveScratch {
@@ -866,7 +861,7 @@ WaveScratch wave_scratch(jg_pnc* p, uint64_t n, uint64_t keep = 0) {
     n = (p->wstat.bytes - 64 - 256) / 12;  // the capacity actually there
     char* s = p->wstat.as<char>();
     return WaveScratch{reinterpret_cast<unsigned long long*>(s), reinterpret_cast<unsigned long long*>(s + 64),
-                       reinterpret_cast<uint32_t*>(s + 64 + ((n * 8 + 15) & ~15ull)), p->wemit.as<uint8_t>(), p->wguid.as<Guid16>(),
+                       reinterpret_cast<uint32_t*>(s + 64 + jg::round_up(n * 8, 16)), p->wemit.as<uint8_t>(), p->wguid.as<Guid16>(),
                        p->wslow.as<unsigned long long>()};
 }
 
@@ -904,8 +899,9 @@ void launch_scan(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
     const Table t = table_of(p);
     const int G = json_group();
     const bool fuse = p->fuse;
-    if (p->eb == 8) launch_scan_g<8>(G, p->ctx->stream, bytes, off, rows, m0, m1, t, w.status, w.deferred, w.emit, w.eguid, w.slow, p->P.p, p->N.p, fuse);
-    else launch_scan_g<4>(G, p->ctx->stream, bytes, off, rows, m0, m1, t, w.status, w.deferred, w.emit, w.eguid, w.slow, p->P.p, p->N.p, fuse);
+    jg::dispatch_eb(p->eb, [&](auto EB) {
+        launch_scan_g<EB()>(G, p->ctx->stream, bytes, off, rows, m0, m1, t, w.status, w.deferred, w.emit, w.eguid, w.slow, p->P.p, p->N.p, fuse);
+    });
     JG_HIP(hipGetLastError());
     p->scan_hi = std::max(p->scan_hi, m1);
 }
@@ -916,9 +912,10 @@ void undo_applied(jg_pnc* p, const uint32_t* rows) {
     const uint64_t n = p->scan_hi;
     if (n == 0 || !p->wemit.p) return;
     const Table t = table_of(p);
-    const unsigned g = (unsigned)((n * kEmitLanes + kBlock - 1) / kBlock);
-    if (p->eb == 8) hipLaunchKernelGGL(k_undo_applied<8>, dim3(g), dim3(kBlock), 0, p->ctx->stream, p->wemit.as<uint8_t>(), rows, n, t.R, p->P.p, p->N.p);
-    else hipLaunchKernelGGL(k_undo_applied<4>, dim3(g), dim3(kBlock), 0, p->ctx->stream, p->wemit.as<uint8_t>(), rows, n, t.R, p->P.p, p->N.p);
+    const unsigned g = blocks_for(n * kEmitLanes);
+    jg::dispatch_eb(p->eb, [&](auto EB) {
+        hipLaunchKernelGGL(k_undo_applied<EB()>, dim3(g), dim3(kBlock), 0, p->ctx->stream, p->wemit.as<uint8_t>(), rows, n, t.R, p->P.p, p->N.p);
+    });
     JG_HIP(hipGetLastError());
 }
 
@@ -928,7 +925,7 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
     jg_ctx* ctx = p->ctx;
     const Table t = table_of(p);
     const int G = json_group();
-    const unsigned ge = (unsigned)((n * kEmitLanes + kBlock - 1) / kBlock);
+    const unsigned ge = blocks_for(n * kEmitLanes);
     if (G > 1) {
         // The steady state of a fused wave (every payload compact and valid, every replica known): pass A's status
         // alone ends it — one read, no slow-list launches (round 6: k_scan_slow and k_apply_slow cost ~5 µs each
@@ -941,8 +938,9 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
             }
         }
         // the payloads the group parse left to the serial parser (count read on the device)
-        if (p->eb == 8) hipLaunchKernelGGL(k_scan_slow<8>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, t, w.status, w.deferred, w.emit, w.slow);
-        else hipLaunchKernelGGL(k_scan_slow<4>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, t, w.status, w.deferred, w.emit, w.slow);
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            hipLaunchKernelGGL(k_scan_slow<EB()>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, t, w.status, w.deferred, w.emit, w.slow);
+        });
         JG_HIP(hipGetLastError());
         // The steady state (every payload valid, every replica known): pass B right away, guarded on the
         // device by pass A's status, so the wave costs one status read.  If pass A failed or deferred a
@@ -950,13 +948,10 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
         // (json_fuse) applied every record pass B would read here (a deferral sends the wave to the full path,
         // whose pass B runs unguarded): only the slow list's launch is left.
         const bool fused = p->fuse;
-        if (p->eb == 8) {
-            if (!fused) hipLaunchKernelGGL(k_apply_emit<8>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, w.status);
-            hipLaunchKernelGGL(k_apply_slow<8>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, w.slow, t, p->P.p, p->N.p, w.status);
-        } else {
-            if (!fused) hipLaunchKernelGGL(k_apply_emit<4>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, w.status);
-            hipLaunchKernelGGL(k_apply_slow<4>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, w.slow, t, p->P.p, p->N.p, w.status);
-        }
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            if (!fused) hipLaunchKernelGGL(k_apply_emit<EB()>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, w.status);
+            hipLaunchKernelGGL(k_apply_slow<EB()>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, w.slow, t, p->P.p, p->N.p, w.status);
+        });
         JG_HIP(hipGetLastError());
         const Status st = read_status(ctx, w.status);
         if (st.first_bad != ~0ull) undo_applied(p, rows), fail_msg(st.first_bad, bad_msg, "state message");
@@ -977,15 +972,16 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
         sorted_deferred = sorted;
         const unsigned gd = blocks_for(nd);
         // the resume list reuses pass A's deferral marks (dead once compacted)
-        if (p->eb == 8) launch_resolve_g<8>(G, ctx->stream, bytes, off, sorted, nd, t, w.emit, w.eguid, w.saved, w.status, w.deferred);
-        else launch_resolve_g<4>(G, ctx->stream, bytes, off, sorted, nd, t, w.emit, w.eguid, w.saved, w.status, w.deferred);
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            launch_resolve_g<EB()>(G, ctx->stream, bytes, off, sorted, nd, t, w.emit, w.eguid, w.saved, w.status, w.deferred);
+        });
         JG_HIP(hipGetLastError());
         st = read_status(ctx, w.status);
         if (st.n_resume && st.resolve_bad == ~0ull) {  // walks the group parse handed to the serial parser
-            if (p->eb == 8)
-                hipLaunchKernelGGL(k_resolve_resume<8>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, sorted, nd, t, w.status, w.deferred, w.emit, w.eguid);
-            else
-                hipLaunchKernelGGL(k_resolve_resume<4>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, sorted, nd, t, w.status, w.deferred, w.emit, w.eguid);
+            jg::dispatch_eb(p->eb, [&](auto EB) {
+                hipLaunchKernelGGL(k_resolve_resume<EB()>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, sorted, nd, t, w.status, w.deferred, w.emit,
+                                   w.eguid);
+            });
             JG_HIP(hipGetLastError());
             st = read_status(ctx, w.status);
         }
@@ -1000,16 +996,18 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
     // pass B: pass A's records (resolved by pass C where deferred), then the messages left to the serial
     // parser (slow: not in the compact form; with JANUS_JSON_GROUP=1 also the deferred ones).  max is
     // order-free.
-    if (p->eb == 8) hipLaunchKernelGGL(k_apply_emit<8>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, nullptr);
-    else hipLaunchKernelGGL(k_apply_emit<4>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, nullptr);
+    jg::dispatch_eb(p->eb, [&](auto EB) {
+        hipLaunchKernelGGL(k_apply_emit<EB()>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, nullptr);
+    });
     JG_HIP(hipGetLastError());
     const unsigned long long* lists[2] = {st.n_deferred ? sorted_deferred : nullptr, w.slow};
     const uint64_t counts[2] = {st.n_deferred, st.n_slow};
     for (int l = G > 1 ? 1 : 0; l < 2; ++l) {
         if (!counts[l]) continue;
         const unsigned gl = blocks_for(counts[l]);
-        if (p->eb == 8) hipLaunchKernelGGL(k_apply_list<8>, dim3(gl), dim3(kBlock), 0, ctx->stream, bytes, off, rows, lists[l], counts[l], t, p->P.p, p->N.p, w.status);
-        else hipLaunchKernelGGL(k_apply_list<4>, dim3(gl), dim3(kBlock), 0, ctx->stream, bytes, off, rows, lists[l], counts[l], t, p->P.p, p->N.p, w.status);
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            hipLaunchKernelGGL(k_apply_list<EB()>, dim3(gl), dim3(kBlock), 0, ctx->stream, bytes, off, rows, lists[l], counts[l], t, p->P.p, p->N.p, w.status);
+        });
         JG_HIP(hipGetLastError());
     }
     st = read_status(ctx, w.status);
@@ -1142,13 +1140,12 @@ int jg_pnc_intern(jg_pnc* p, uint64_t n, const uint32_t* key_idx, const jg_guid*
         jg_ctx* ctx = p->ctx;
         jg::ensure_device(ctx);
         ensure_table(p);
-        char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch, 64 + n * (4 + 16 + 8 + 4 + 4) + 256));
-        auto* status = reinterpret_cast<unsigned long long*>(s);
-        auto* keys = reinterpret_cast<unsigned long long*>(s + 64);
-        auto* g = reinterpret_cast<Guid16*>(s + 64 + n * 8);
-        auto* rows = reinterpret_cast<uint32_t*>(s + 64 + n * 24);
-        auto* cols = rows + n;
-        auto* saved = cols + n;
+        unsigned long long *status, *keys;
+        Guid16* g;
+        uint32_t *rows, *cols, *saved;
+        jg::Layout L;
+        L.add(status, 8, 64), L.add(keys, n, 8), L.add(g, n, 8), L.add(rows, n, 4), L.add(cols, n, 4), L.add(saved, n, 4);
+        L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 256));
         const Status init{~0ull, 0, ~0ull, 0};
         JG_HIP(hipMemcpyAsync(rows, key_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(g, replica, n * 16, hipMemcpyHostToDevice, ctx->stream));
@@ -1183,10 +1180,11 @@ int jg_pnc_columns(jg_pnc* p, uint64_t n, const uint32_t* key_idx, jg_guid* repl
         jg_ctx* ctx = p->ctx;
         jg::ensure_device(ctx);
         ensure_table(p);
-        char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * (4 + 4 + 16ull * p->R) + 256));
-        auto* rows = reinterpret_cast<uint32_t*>(s);
-        auto* nout = rows + n;
-        auto* out = reinterpret_cast<Guid16*>(s + ((n * 8 + 15) & ~15ull));
+        uint32_t *rows, *nout;
+        Guid16* out;
+        jg::Layout L;
+        L.add(rows, n, 4), L.add(nout, n, 4), L.add(out, n * p->R, 16);
+        L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 256));
         JG_HIP(hipMemcpyAsync(rows, key_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_gather_cols, dim3(blocks_for(n * p->R)), dim3(kBlock), 0, ctx->stream, p->cols.as<Guid16>(), p->ncols.as<uint32_t>(),
                            rows, n, p->R, out, nout);
@@ -1208,7 +1206,7 @@ int jg_wave_create(jg_ctx* ctx, uint64_t cap_msgs, uint64_t cap_bytes, jg_wave**
         w->cap_msgs = cap_msgs;
         w->cap_bytes = cap_bytes;
         try {
-            w->bytes.alloc(((cap_bytes + 15) & ~15ull) + 16);  // the parser reads aligned 16-byte windows
+            w->bytes.alloc(jg::round_up(cap_bytes, 16) + 16);  // the parser reads aligned 16-byte windows
             w->off.alloc((cap_msgs + 1) * 8);
             w->keys.alloc(cap_msgs * 4 + 4);
         } catch (...) {
@@ -1275,7 +1273,7 @@ int jg_pnc_wave_begin(jg_pnc* p, uint64_t cap_msgs, uint64_t cap_bytes) {
         jg_ctx* ctx = p->ctx;
         jg::ensure_device(ctx);
         ensure_table(p);
-        grow_keep(ctx, p->wbytes, ((cap_bytes + 15) & ~15ull) + 16, 0);
+        grow_keep(ctx, p->wbytes, jg::round_up(cap_bytes, 16) + 16, 0);
         grow_keep(ctx, p->woff, (cap_msgs + 1) * 8, 0);
         grow_keep(ctx, p->wrows, cap_msgs * 4 + 4, 0);
         const WaveScratch w = wave_scratch(p, cap_msgs);
@@ -1302,9 +1300,9 @@ int jg_pnc_wave_append(jg_pnc* p, uint64_t n, const uint32_t* key_idx, const uin
         jg::ensure_device(ctx);
         const uint64_t m0 = p->wn, b0 = p->wnb, nb = off[n];
         // grow (rare: the caller's capacity hint was short); earlier chunks are kept
-        if (p->wbytes.bytes < ((b0 + nb + 15) & ~15ull) + 16 || p->woff.bytes < (m0 + n + 1) * 8 || p->wrows.bytes < (m0 + n) * 4 + 4) {
+        if (p->wbytes.bytes < jg::round_up(b0 + nb, 16) + 16 || p->woff.bytes < (m0 + n + 1) * 8 || p->wrows.bytes < (m0 + n) * 4 + 4) {
             const uint64_t need_m = 2 * (m0 + n), need_b = 2 * (b0 + nb);
-            grow_keep(ctx, p->wbytes, ((need_b + 15) & ~15ull) + 16, b0);
+            grow_keep(ctx, p->wbytes, jg::round_up(need_b, 16) + 16, b0);
             grow_keep(ctx, p->woff, (need_m + 1) * 8, (m0 + 1) * 8);
             grow_keep(ctx, p->wrows, need_m * 4 + 4, m0 * 4);
         }
@@ -1442,6 +1440,18 @@ __global__ void k_prefix_scatter(const unsigned long long* __restrict__ sorted, 
     dn[i] = (long long)(0ull - (excl[s].n + vals[s].n));
 }
 
+// One workspace for the per-key PN2 scan over n items and a sum of m Ts (the apply-ops calls run one after the other):
+// sized before their arrays exist.
+extern "C++" template <class T> size_t scans_temp_bytes(jg_ctx* ctx, int n, int m) {
+    return std::max(jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                        return hipcub::DeviceScan::ExclusiveScanByKey(temp, bytes, (const uint32_t*)nullptr, (const PN2*)nullptr, (PN2*)nullptr, PN2Add(),
+                                                                      PN2{0, 0}, n, hipcub::Equality(), ctx->stream);
+                    }),
+                    jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                        return hipcub::DeviceScan::ExclusiveSum(temp, bytes, (const T*)nullptr, (T*)nullptr, m, ctx->stream);
+                    }));
+}
+
 // jg_pnc_encode_json(_before): length pass, scan, offsets to the host; with `out`, the write pass and its bytes.
 void encode_rows(jg_pnc* p, uint64_t n, const uint32_t* key_idx, uint32_t col, const int64_t* dp, const int64_t* dn, uint64_t* off, uint8_t* out,
                  uint64_t cap, const char* fn, uint8_t* sha = nullptr) {
@@ -1456,36 +1466,36 @@ void encode_rows(jg_pnc* p, uint64_t n, const uint32_t* key_idx, uint32_t col, c
     jg::ensure_device(ctx);
     ensure_table(p);
     const Table t = table_of(p);
-    char* s = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * 4 + (n + 1) * 16 + (dp ? n * 16 : 0) + 768));
-    auto* rows = reinterpret_cast<uint32_t*>(s);
-    auto* len = reinterpret_cast<unsigned long long*>(s + ((n * 4 + 255) & ~255ull));
-    auto* doff = len + n + 1;
-    long long* ddp = nullptr;
-    long long* ddn = nullptr;
+    uint32_t* rows;
+    unsigned long long *len, *doff;
+    long long *ddp, *ddn;
+    jg::Layout L;
+    L.add(rows, n), L.add(len, n + 1), L.add(doff, n + 1, 8), L.add(ddp, dp ? n : 0, 8), L.add(ddn, dp ? n : 0, 8);
+    L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 256));
+    if (!dp) ddp = ddn = nullptr;
     JG_HIP(hipMemcpyAsync(rows, key_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (dp) {
-        ddp = reinterpret_cast<long long*>(doff + n + 1);
-        ddn = ddp + n;
         JG_HIP(hipMemcpyAsync(ddp, dp, n * 8, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(ddn, dn, n * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     const unsigned g = blocks_for(n);
-    if (p->eb == 8) hipLaunchKernelGGL((k_encode<8, 0>), dim3(g), dim3(kBlock), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
-    else hipLaunchKernelGGL((k_encode<4, 0>), dim3(g), dim3(kBlock), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
+    jg::dispatch_eb(p->eb, [&](auto EB) {
+        hipLaunchKernelGGL((k_encode<EB(), 0>), dim3(g), dim3(kBlock), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
+    });
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemsetAsync(len + n, 0, 8, ctx->stream));
-    size_t temp = 0;
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, len, doff, (int)(n + 1), ctx->stream));
-    void* tmp = jg::scratch(ctx, ctx->scratch3, temp + 256);
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, temp, len, doff, (int)(n + 1), ctx->stream));
+    const int n_len = jg::cub_count(n + 1, "rows");
+    jg::cub_run(jg::cub_in(ctx, ctx->scratch3),
+                [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, len, doff, n_len, ctx->stream); });
     JG_HIP(hipMemcpyAsync(off, doff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     JG_HIP(hipStreamSynchronize(ctx->stream));
     if (!out) return;  // size query
     JG_REQUIRE(off[n] <= cap, JG_ESTATE, "%s: %llu bytes exceed cap %llu", fn, (unsigned long long)off[n], (unsigned long long)cap);
     auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, off[n] + 64));
-    const unsigned g1 = (unsigned)((n + kEncLanes - 1) / kEncLanes);  // the write pass: one wave per workgroup
-    if (p->eb == 8) hipLaunchKernelGGL((k_encode<8, 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
-    else hipLaunchKernelGGL((k_encode<4, 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
+    const unsigned g1 = blocks_for(n, kEncLanes);  // the write pass: one wave per workgroup
+    jg::dispatch_eb(p->eb, [&](auto EB) {
+        hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
+    });
     JG_HIP(hipGetLastError());
     if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(doff), n, sha);  // each state's SHA-256 (ComputeDigest's first level)
     JG_HIP(hipMemcpyAsync(out, dout, off[n], hipMemcpyDeviceToHost, ctx->stream));
@@ -1513,54 +1523,51 @@ int jg_pnc_apply_ops_rewind(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         jg::ensure_device(ctx);
         using ull = unsigned long long;
         const uint64_t n = n_ops;
-        auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
+        const int n_i = jg::cub_count(n, "ops");
         // the ops (scratch2): key, delta, is_n, need, then the need positions
-        const uint64_t o_del = al(n * 4), o_isn = o_del + al(n * 8), o_need = o_isn + al(n), o_pos = o_need + al(n), o_end = o_pos + al(n * 4);
-        char* a = static_cast<char*>(jg::scratch(ctx, ctx->scratch2, o_end + 256));
-        auto* dkey = reinterpret_cast<uint32_t*>(a);
-        auto* ddel = reinterpret_cast<long long*>(a + o_del);
-        auto* disn = reinterpret_cast<uint8_t*>(a + o_isn);
-        auto* dneed = reinterpret_cast<uint8_t*>(a + o_need);
-        auto* dpos = reinterpret_cast<uint32_t*>(a + o_pos);
+        uint32_t *dkey, *dpos;
+        long long* ddel;
+        uint8_t *disn, *dneed;
+        jg::Layout A;
+        A.add(dkey, n), A.add(ddel, n), A.add(disn, n), A.add(dneed, n), A.add(dpos, n);
+        A.bind(jg::scratch(ctx, ctx->scratch2, A.bytes() + 256));
         JG_HIP(hipMemcpyAsync(dkey, key, n * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(ddel, delta, n * 8, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(disn, is_n, n, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(dneed, need, n, hipMemcpyHostToDevice, ctx->stream));
         // Increment / Decrement (k_apply_ops with every op on column col)
         const unsigned g = blocks_for(n);
-        if (p->eb == 8) hipLaunchKernelGGL(k_apply_ops_col<8>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
-        else hipLaunchKernelGGL(k_apply_ops_col<4>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            hipLaunchKernelGGL(k_apply_ops_col<EB()>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
+        });
         JG_HIP(hipGetLastError());
         if (n_need == 0) {
             JG_HIP(hipStreamSynchronize(ctx->stream));
             return;
         }
         // the rewinds (scratch: keys, values, sums, segments, the scans' temp; sort_keys uses scratch3)
-        const uint64_t o_val = al(n * 8), o_sum = o_val + al(n * 16), o_seg = o_sum + al(n * 16), o_dp = o_seg + al(n * 4),
-                       o_tmp = o_dp + al(n_need * 16);
-        size_t t_scan = 0, t_pos = 0;
-        JG_HIP(hipcub::DeviceScan::ExclusiveScanByKey(nullptr, t_scan, (const uint32_t*)nullptr, (const PN2*)nullptr, (PN2*)nullptr, PN2Add(),
-                                                      PN2{0, 0}, (int)n, hipcub::Equality(), ctx->stream));
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t_pos, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, ctx->stream));
-        char* b = static_cast<char*>(jg::scratch(ctx, ctx->scratch, o_tmp + std::max(t_scan, t_pos) + 256));
-        auto* keys = reinterpret_cast<ull*>(b);
-        auto* vals = reinterpret_cast<PN2*>(b + o_val);
-        auto* later = reinterpret_cast<PN2*>(b + o_sum);
-        auto* seg = reinterpret_cast<uint32_t*>(b + o_seg);
-        auto* ddp = reinterpret_cast<long long*>(b + o_dp);
-        auto* ddn = ddp + n_need;
-        void* tmp = b + o_tmp;
+        const size_t t_both = scans_temp_bytes<uint32_t>(ctx, n_i, n_i);
+        ull* keys;
+        PN2 *vals, *later;
+        uint32_t* seg;
+        long long* ddp;
+        uint8_t* dtmp;
+        jg::Layout B;
+        B.add(keys, n), B.add(vals, n), B.add(later, n), B.add(seg, n), B.add(ddp, 2 * n_need), B.add(dtmp, t_both + 256);
+        B.bind(jg::scratch(ctx, ctx->scratch, B.bytes()));
+        long long* ddn = ddp + n_need;
+        const auto tmp = jg::cub_in(dtmp, t_both);
         // need positions first (the flags as u32 in `seg`: a scan of u8 would sum in u8), then the keys
         hipLaunchKernelGGL(k_flags_u32, dim3(g), dim3(kBlock), 0, ctx->stream, dneed, n, seg);
-        size_t t = t_pos;
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, t, seg, dpos, (int)n, ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, seg, dpos, n_i, ctx->stream); });
         hipLaunchKernelGGL(k_make_keys_rev, dim3(g), dim3(kBlock), 0, ctx->stream, dkey, n, keys);
         JG_HIP(hipGetLastError());
         const ull* sorted = sort_keys(ctx, keys, n, p->n_keys);
         hipLaunchKernelGGL(k_rewind_vals, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, ddel, disn, p->eb, vals, seg);
         JG_HIP(hipGetLastError());
-        t = t_scan;
-        JG_HIP(hipcub::DeviceScan::ExclusiveScanByKey(tmp, t, seg, vals, later, PN2Add(), PN2{0, 0}, (int)n, hipcub::Equality(), ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceScan::ExclusiveScanByKey(temp, bytes, seg, vals, later, PN2Add(), PN2{0, 0}, n_i, hipcub::Equality(), ctx->stream);
+        });
         hipLaunchKernelGGL(k_rewind_scatter, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, later, dneed, dpos, ddp, ddn);
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemcpyAsync(dp, ddp, n_need * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1589,28 +1596,19 @@ int jg_pnc_apply_ops_encode(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         const Table t = table_of(p);
         using ull = unsigned long long;
         const uint64_t n = n_ops;
-        auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-        // everything but the sort (scratch3) and the bytes (scratch2) in ctx->scratch, sized once
-        const uint64_t o_del = al(n * 4), o_isn = o_del + al(n * 8), o_k64 = o_isn + al(n), o_val = o_k64 + al(n * 8),
-                       o_exc = o_val + al(n * 16), o_seg = o_exc + al(n * 16), o_dp = o_seg + al(n * 4), o_dn = o_dp + al(n * 8),
-                       o_len = o_dn + al(n * 8), o_off = o_len + al((n + 1) * 8), o_tmp = o_off + al((n + 1) * 8);
-        size_t t_scan = 0, t_sum = 0;
-        JG_HIP(hipcub::DeviceScan::ExclusiveScanByKey(nullptr, t_scan, (const uint32_t*)nullptr, (const PN2*)nullptr, (PN2*)nullptr, PN2Add(),
-                                                      PN2{0, 0}, (int)n, hipcub::Equality(), ctx->stream));
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t_sum, (const ull*)nullptr, (ull*)nullptr, (int)(n + 1), ctx->stream));
-        char* a = static_cast<char*>(jg::scratch(ctx, ctx->scratch, o_tmp + std::max(t_scan, t_sum) + 256));
-        auto* dkey = reinterpret_cast<uint32_t*>(a);
-        auto* ddel = reinterpret_cast<long long*>(a + o_del);
-        auto* disn = reinterpret_cast<uint8_t*>(a + o_isn);
-        auto* keys = reinterpret_cast<ull*>(a + o_k64);
-        auto* vals = reinterpret_cast<PN2*>(a + o_val);
-        auto* excl = reinterpret_cast<PN2*>(a + o_exc);
-        auto* seg = reinterpret_cast<uint32_t*>(a + o_seg);
-        auto* ddp = reinterpret_cast<long long*>(a + o_dp);
-        auto* ddn = reinterpret_cast<long long*>(a + o_dn);
-        auto* len = reinterpret_cast<ull*>(a + o_len);
-        auto* doff = reinterpret_cast<ull*>(a + o_off);
-        void* tmp = a + o_tmp;
+        const int n_i = jg::cub_count(n, "ops"), n1_i = jg::cub_count(n + 1, "ops");
+        const size_t t_both = scans_temp_bytes<ull>(ctx, n_i, n1_i);
+        // everything but the sort (scratch3) and the bytes (scratch2) in ctx->scratch
+        uint32_t *dkey, *seg;
+        long long *ddel, *ddp, *ddn;
+        uint8_t *disn, *dtmp;
+        ull *keys, *len, *doff;
+        PN2 *vals, *excl;
+        jg::Layout A;
+        A.add(dkey, n), A.add(ddel, n), A.add(disn, n), A.add(keys, n), A.add(vals, n), A.add(excl, n), A.add(seg, n), A.add(ddp, n), A.add(ddn, n);
+        A.add(len, n + 1), A.add(doff, n + 1), A.add(dtmp, t_both + 256);
+        A.bind(jg::scratch(ctx, ctx->scratch, A.bytes()));
+        const auto tmp = jg::cub_in(dtmp, t_both);
         JG_HIP(hipMemcpyAsync(dkey, key, n * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(ddel, delta, n * 8, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(disn, is_n, n, hipMemcpyHostToDevice, ctx->stream));
@@ -1621,31 +1619,29 @@ int jg_pnc_apply_ops_encode(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         const ull* sorted = sort_keys(ctx, keys, n, p->n_keys);
         hipLaunchKernelGGL(k_rewind_vals, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, ddel, disn, p->eb, vals, seg);
         JG_HIP(hipGetLastError());
-        size_t tt = t_scan;
-        JG_HIP(hipcub::DeviceScan::ExclusiveScanByKey(tmp, tt, seg, vals, excl, PN2Add(), PN2{0, 0}, (int)n, hipcub::Equality(), ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceScan::ExclusiveScanByKey(temp, bytes, seg, vals, excl, PN2Add(), PN2{0, 0}, n_i, hipcub::Equality(), ctx->stream);
+        });
         hipLaunchKernelGGL(k_prefix_scatter, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, vals, excl, ddp, ddn);
         JG_HIP(hipGetLastError());
         // the snapshots' lengths from the rows as they stand (nothing applied yet), their offsets to the host
-        if (p->eb == 8) hipLaunchKernelGGL((k_encode<8, 0>), dim3(g), dim3(kBlock), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
-        else hipLaunchKernelGGL((k_encode<4, 0>), dim3(g), dim3(kBlock), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            hipLaunchKernelGGL((k_encode<EB(), 0>), dim3(g), dim3(kBlock), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
+        });
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemsetAsync(len + n, 0, 8, ctx->stream));
-        tt = t_sum;
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tt, len, doff, (int)(n + 1), ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, len, doff, n1_i, ctx->stream); });
         JG_HIP(hipMemcpyAsync(off, doff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipStreamSynchronize(ctx->stream));
         JG_REQUIRE(off[n] <= cap, JG_ESTATE, "jg_pnc_apply_ops_encode: %llu bytes exceed cap %llu (nothing applied)", (unsigned long long)off[n],
                    (unsigned long long)cap);
         // the bytes, then the ops (stream order: the write pass reads the rows before the adds land), the hashes
         auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, off[n] + 64));
-        const unsigned g1 = (unsigned)((n + kEncLanes - 1) / kEncLanes);  // the write pass: one wave per workgroup
-        if (p->eb == 8) {
-            hipLaunchKernelGGL((k_encode<8, 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
-            hipLaunchKernelGGL(k_apply_ops_col<8>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
-        } else {
-            hipLaunchKernelGGL((k_encode<4, 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
-            hipLaunchKernelGGL(k_apply_ops_col<4>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
-        }
+        const unsigned g1 = blocks_for(n, kEncLanes);  // the write pass: one wave per workgroup
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
+            hipLaunchKernelGGL(k_apply_ops_col<EB()>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
+        });
         JG_HIP(hipGetLastError());
         if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(doff), n, sha);
         JG_HIP(hipMemcpyAsync(out, dout, off[n], hipMemcpyDeviceToHost, ctx->stream));

@@ -702,7 +702,7 @@ inline int json_group() {
     const int v = e ? std::atoi(e) : 8;
     return v == 1 || v == 4 || v == 16 || v == 32 || v == 64 ? v : 8;
 }
-inline unsigned json_blocks(uint64_t n, int G) { return (unsigned)((n * (uint64_t)G + kBlock - 1) / kBlock); }
+inline unsigned json_blocks(uint64_t n, int G) { return jg::blocks_for(n * (uint64_t)G); }
 
 template <int EB>
 void launch_resolve_g(int G, hipStream_t st, const uint8_t* bytes, const uint64_t* off, const unsigned long long* keys, uint64_t nd,

@@ -28,14 +28,13 @@
 #include <hipcub/hipcub.hpp>
 
 #include <atomic>
-#include <chrono>
 #include <memory>
 #include <string>
 #include <unordered_set>
 #include <vector>
 
 #include "host_pool.hpp"
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "uid_table.hpp"
 
 namespace {
@@ -43,12 +42,10 @@ namespace {
 constexpr int kBlock = 256;
 constexpr unsigned long long kTomb = ~0ull;
 
-unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
-uint64_t pow2_at_least(uint64_t x, uint64_t lo = 1024) {
-    uint64_t p = lo;
-    while (p < x) p <<= 1;
-    return p;
-}
+using jg::blocks_for;
+using jg::ensure;
+using jg::pow2_at_least;
+double now_s() { return jg::now_us() * 1e-6; }
 
 using jg::DevUids;
 using jg::kNoSlot;
@@ -245,12 +242,6 @@ __global__ __launch_bounds__(kBlock) void k_count_applied(const uint32_t* __rest
 struct NonZero {
     __host__ __device__ bool operator()(const unsigned long long& x) const { return x != 0; }
 };
-
-void ensure(jg::DevBuf& b, size_t bytes) {
-    if (b.bytes < bytes) b.alloc(bytes + bytes / 4 + 256);
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
 
@@ -454,7 +445,7 @@ struct jg_node {
         return *pool;
     }
     char* stage(size_t n) {
-        n = (n + 255) & ~size_t(255);
+        n = jg::round_up(n, 256);
         while (arena_i < arenas.size() && arena_off + n > arenas[arena_i].second) {
             ++arena_i;
             arena_off = 0;
@@ -497,7 +488,7 @@ struct jg_node {
         if (!htab.empty() && 2 * total <= htab.size()) return;
         std::vector<UidSlot> old;
         old.swap(htab);
-        htab.assign(pow2_at_least(4 * total), UidSlot{0, 0, 0, 0, 0});
+        htab.assign(pow2_at_least(4 * total, 1024), UidSlot{0, 0, 0, 0, 0});
         upload_all = true;
         dirty.clear();
         for (const UidSlot& s : old)
@@ -519,7 +510,7 @@ struct jg_node {
         for (uint64_t i = 0; i < n; ++i) v[i] = htab[dirty[i]];
         char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * 36 + 512));
         auto* dat = reinterpret_cast<uint32_t*>(st);
-        auto* dv = reinterpret_cast<UidSlot*>(st + ((n * 4 + 255) & ~255ull));
+        auto* dv = reinterpret_cast<UidSlot*>(st + jg::round_up(n * 4, 256));
         JG_HIP(hipMemcpyAsync(dat, dirty.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(dv, v.data(), n * sizeof(UidSlot), hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_uid_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, dtab.as<UidSlot>(), dat, dv, n);
@@ -609,7 +600,7 @@ void wave_begin(jg_node* nd, WaveRun& r, jg_tracker* tr, uint64_t n, uint64_t to
     r.tcnt.assign((r.chunk_msgs + kTask - 1) / kTask + 2, 0);
     r.tbytes.assign(r.tcnt.size(), 0);
     tp[4] = now_s();
-    ensure(nd->bytes, ((total_bytes + 15) & ~15ull) + 64);  // the parsers read aligned 16-byte windows
+    ensure(nd->bytes, jg::round_up(total_bytes, 16) + 64);  // the parsers read aligned 16-byte windows
     ensure(nd->off, (n + 1) * 8);
     ensure(nd->uid, n * 16);
     ensure(nd->seq, n * 8);
@@ -727,7 +718,7 @@ void wave_chunk(jg_node* nd, WaveRun& r, const jg_commit* w, uint64_t gbase, uin
                (unsigned long long)(r.b0 + nb), (unsigned long long)r.n, (unsigned long long)r.total_bytes);
     const uint64_t meta_bytes = (m + 1) * 8 + m * 25;  // offsets, uids (16), identities (8), types (1)
     JG_REQUIRE(r.mo + meta_bytes <= r.meta_cap, JG_EINVAL, "jg_apply_stream_append: more chunks than the wave was sized for");
-    const uint64_t nb_pad = direct ? 0 : (nb + 15) & ~15ull;
+    const uint64_t nb_pad = direct ? 0 : jg::round_up(nb, 16);
     char* buf = nd->stage(nb_pad + (m + 1) * 8 + m * 16 + m * 8 + m + 64);
     auto* soff = reinterpret_cast<uint64_t*>(buf + nb_pad);
     auto* suid = reinterpret_cast<jg_guid*>(soff + m + 1);
@@ -764,7 +755,7 @@ void wave_chunk(jg_node* nd, WaveRun& r, const jg_commit* w, uint64_t gbase, uin
     if (nb) JG_HIP(hipMemcpyAsync(d_bytes + b0, src, nb, hipMemcpyHostToDevice, ctx->copy));
     uint8_t* d_meta = nd->meta.as<uint8_t>() + r.mo;
     JG_HIP(hipMemcpyAsync(d_meta, soff, meta_bytes, hipMemcpyHostToDevice, ctx->copy));
-    r.mo += (meta_bytes + 63) & ~63ull;
+    r.mo += jg::round_up(meta_bytes, 64);
     jg::upload_done(ctx);
     JG_HIP(hipEventRecord(nd->event(2 * r.n_ev), ctx->stream));
     hipLaunchKernelGGL(k_unstage, dim3(blocks_for(m)), dim3(kBlock), 0, ctx->stream, d_meta, m, m0, b0, d_off, nd->uid.as<Guid16>(),
@@ -904,10 +895,10 @@ void wave_end(jg_node* nd, WaveRun& r, uint64_t* completed, uint64_t* n_complete
         hipLaunchKernelGGL(k_complete, dim3(blocks_for(cut)), dim3(kBlock), 0, ctx->stream, nd->tslot.as<uint32_t>(), cut, dt, d_origin);
         hipLaunchKernelGGL(k_claim_reset, dim3(blocks_for(nn)), dim3(kBlock), 0, ctx->stream, nd->tslot.as<uint32_t>(), nn, dt.claim);
         JG_HIP(hipGetLastError());
-        size_t temp = 0;
-        JG_HIP(hipcub::DeviceSelect::If(nullptr, temp, d_origin, d_done, d_status + 1, (int)cut, NonZero(), ctx->stream));
-        ensure(nd->cub, temp + 256);
-        JG_HIP(hipcub::DeviceSelect::If(nd->cub.p, temp, d_origin, d_done, d_status + 1, (int)cut, NonZero(), ctx->stream));
+        const int n_cut = jg::cub_count(cut, "messages");
+        jg::cub_run(jg::cub_in(nd->cub), [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceSelect::If(temp, bytes, d_origin, d_done, d_status + 1, n_cut, NonZero(), ctx->stream);
+        });
         hipLaunchKernelGGL(k_count_sub, dim3(1), dim3(1), 0, ctx->stream, tr->count.as<unsigned long long>(), d_status + 1);
         JG_HIP(hipGetLastError());
         unsigned long long k = 0;
@@ -1201,7 +1192,7 @@ int jg_tracker_contains(jg_tracker* t, uint64_t n, const uint64_t* seq, uint8_t*
         t->flush();
         char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * 9 + 512));
         auto* ds = reinterpret_cast<unsigned long long*>(st);
-        auto* dout = reinterpret_cast<uint8_t*>(st + ((n * 8 + 255) & ~255ull));
+        auto* dout = reinterpret_cast<uint8_t*>(st + jg::round_up(n * 8, 256));
         JG_HIP(hipMemcpyAsync(ds, seq, n * 8, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_track_lookup, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, t->dev(), ds, n, dout);
         JG_HIP(hipGetLastError());

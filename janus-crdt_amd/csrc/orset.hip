@@ -21,7 +21,6 @@
 #include <cstring>
 #include <hipcub/hipcub.hpp>
 
-#include <chrono>
 
 #include <algorithm>
 #include <cstdlib>
@@ -31,7 +30,7 @@
 #include <vector>
 
 #include "host_pool.hpp"
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "orset_union.hpp"
 
 namespace {
@@ -293,19 +292,12 @@ __global__ __launch_bounds__(kOB) void k_gather_raw(View a, View r, const uint64
     }
 }
 
-unsigned grid_for(jg_ctx* ctx, uint64_t items, unsigned per_cu = 8) {
-    uint64_t g = (items + kOB - 1) / kOB;
-    const uint64_t cap = (uint64_t)ctx->num_cus * per_cu;
-    if (g > cap) g = cap;
-    return g == 0 ? 1u : (unsigned)g;
-}
-
 uint64_t tiles_for(uint64_t records) { return (records + kTile - 1) / kTile; }
 
 // Workspace of one union: [part (n_tiles+1) x 8 | pad][pchunk 2 (n_tiles+1) x 4 | pad].
 size_t union_ws_bytes(uint64_t total) {
     const uint64_t p = tiles_for(total) + 1;
-    return ((p * 8 + 255) & ~(size_t)255) + ((p * 8 + 255) & ~(size_t)255);
+    return 2 * jg::round_up(p * 8, 256);
 }
 
 // Renumber a stream's ords to 0..n-1 in the same order (ties keep rank order); next = n.  Synchronous
@@ -314,22 +306,23 @@ void renumber(jg_ctx* ctx, jg_stream_soa& s) {
     if (s.n == 0) { s.next = 0; return; }
     JG_REQUIRE(s.n < 0xFFFFFFFFull, JG_ESTATE, "OR-Set stream of %llu records exceeds the 32-bit ordinal range", (unsigned long long)s.n);
     const uint64_t n = s.n;
+    const int items = jg::cub_count(n, "records");
+    uint32_t *k0 = nullptr, *v0 = nullptr, *k1 = nullptr, *v1 = nullptr;
+    const auto sort = [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceRadixSort::SortPairs(temp, bytes, k0, k1, v0, v1, items, 0, 32, ctx->stream);
+    };
+    const size_t temp = jg::cub_temp_bytes(sort);
+    uint8_t* tmp;
+    jg::Layout L;
+    L.add(k0, n), L.add(v0, n), L.add(k1, n), L.add(v1, n), L.add(tmp, temp + 256);
     jg::DevBuf buf;
-    size_t temp = 0;
-    uint32_t* nul = nullptr;
-    JG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, nul, nul, nul, nul, (int)n, 0, 32, ctx->stream));
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255;
-    buf.alloc(4 * a4 + temp + 256);
-    auto* k0 = buf.as<uint32_t>();
-    auto* v0 = reinterpret_cast<uint32_t*>(buf.as<char>() + a4);
-    auto* k1 = reinterpret_cast<uint32_t*>(buf.as<char>() + 2 * a4);
-    auto* v1 = reinterpret_cast<uint32_t*>(buf.as<char>() + 3 * a4);
-    void* tmp = buf.as<char>() + 4 * a4;
+    buf.alloc(L.bytes());
+    L.bind(buf.p);
     const View v = view(s);
-    hipLaunchKernelGGL(k_ord_by_rank, dim3(grid_for(ctx, (uint64_t)s.nch * kChunk, 16)), dim3(kOB), 0, ctx->stream, v, s.cnt.as<uint32_t>(), k0, v0);
+    hipLaunchKernelGGL(k_ord_by_rank, dim3(jg::grid_for(ctx, (uint64_t)s.nch * kChunk, kOB, 16)), dim3(kOB), 0, ctx->stream, v, s.cnt.as<uint32_t>(), k0, v0);
     JG_HIP(hipGetLastError());
-    JG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, temp, k0, k1, v0, v1, (int)n, 0, 32, ctx->stream));
-    hipLaunchKernelGGL(k_ord_scatter, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, v, s.ord.as<uint32_t>(), v1, n);
+    jg::cub_run(jg::cub_in(tmp, temp), sort);
+    hipLaunchKernelGGL(k_ord_scatter, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, v, s.ord.as<uint32_t>(), v1, n);
     JG_HIP(hipGetLastError());
     JG_HIP(hipStreamSynchronize(ctx->stream));
     s.next = n;
@@ -381,7 +374,7 @@ UnionLaunch prepare_union(jg_ctx* ctx, const jg_stream_soa& a, const jg_stream_s
     u.n_tiles = tiles_for(u.total);
     JG_REQUIRE(u.n_tiles < 0xFFFFFFFFull, JG_EINVAL, "union: %llu records exceed the chunk index range", (unsigned long long)u.total);
     u.part = reinterpret_cast<uint64_t*>(ws);
-    u.pchunk = reinterpret_cast<uint32_t*>(ws + (((u.n_tiles + 1) * 8 + 255) & ~(size_t)255));
+    u.pchunk = reinterpret_cast<uint32_t*>(ws + jg::round_up((u.n_tiles + 1) * 8, 256));
     u.va = view(a);
     u.vb = view(b);
     return u;
@@ -412,9 +405,9 @@ void union_store(jg_ctx* ctx, jg_orset* a, jg_orset* b, jg_stream_soa& oa, jg_st
     const uint64_t parts = pa.n_parts + pr.n_parts;
     if (parts) {
         if (parts <= kFewParts)  // a wave into a store: latency of the search, not throughput (orset_union.hpp)
-            hipLaunchKernelGGL((jgk::k_partition_lanes2<kTile, 64>), dim3((unsigned)((parts * 64 + 255) / 256)), dim3(256), 0, ctx->stream, pa, pr);
+            hipLaunchKernelGGL((jgk::k_partition_lanes2<kTile, 64>), dim3(jg::blocks_for(parts * 64)), dim3(256), 0, ctx->stream, pa, pr);
         else
-            hipLaunchKernelGGL((jgk::k_partition_gallop2<kTile>), dim3((unsigned)((parts + 255) / 256)), dim3(256), 0, ctx->stream, pa, pr);
+            hipLaunchKernelGGL((jgk::k_partition_gallop2<kTile>), dim3(jg::blocks_for(parts)), dim3(256), 0, ctx->stream, pa, pr);
         JG_HIP(hipGetLastError());
     }
     launch_tiles(ctx, ua, drop);
@@ -459,10 +452,10 @@ void upload_stream(jg_ctx* ctx, jg_stream_soa& s, const jg_tagrec* recs, uint64_
     auto* span = reinterpret_cast<unsigned long long*>(ctx->flags.as<char>() + 64);
     JG_HIP(hipMemcpyAsync(st, recs, n * sizeof(jg_tagrec), hipMemcpyHostToDevice, ctx->stream));
     JG_HIP(hipMemsetAsync(span, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_unpack, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, st, n, s.key.as<unsigned long long>(), s.tag.as<uint4>(),
+    hipLaunchKernelGGL(k_unpack, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, st, n, s.key.as<unsigned long long>(), s.tag.as<uint4>(),
                        s.ord.as<uint32_t>(), ctx->flags.as<unsigned>(), span);
     JG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_check_sorted, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, s.key.as<unsigned long long>(),
+    hipLaunchKernelGGL(k_check_sorted, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, s.key.as<unsigned long long>(),
                        s.tag.as<uint4>(), n, ctx->flags.as<unsigned>());
     JG_HIP(hipGetLastError());
     unsigned long long h = 0;
@@ -474,7 +467,7 @@ void upload_stream(jg_ctx* ctx, jg_stream_soa& s, const jg_tagrec* recs, uint64_
 void download_stream(jg_ctx* ctx, const jg_stream_soa& s, jg_tagrec* out) {
     if (s.n == 0) return;
     auto* st = static_cast<jg_tagrec*>(jg::scratch(ctx, ctx->scratch2, s.n * sizeof(jg_tagrec)));
-    hipLaunchKernelGGL(k_pack, dim3(grid_for(ctx, (uint64_t)s.nch * kChunk, 16)), dim3(kOB), 0, ctx->stream, view(s), s.cnt.as<uint32_t>(), st);
+    hipLaunchKernelGGL(k_pack, dim3(jg::grid_for(ctx, (uint64_t)s.nch * kChunk, kOB, 16)), dim3(kOB), 0, ctx->stream, view(s), s.cnt.as<uint32_t>(), st);
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemcpyAsync(out, st, s.n * sizeof(jg_tagrec), hipMemcpyDeviceToHost, ctx->stream));
     JG_HIP(hipStreamSynchronize(ctx->stream));
@@ -484,7 +477,7 @@ void download_stream(jg_ctx* ctx, const jg_stream_soa& s, jg_tagrec* out) {
 void merge_into(jg_orset* s, jg_orset* src, bool async, jgk::Drop drop = {nullptr, 0}) {
     jg_ctx* ctx = s->ctx;
     const bool tr = std::getenv("JANUS_TRACE_MERGE") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e6; };
+    const auto now = jg::now_us;
     const double t0 = tr ? now() : 0;
     jg::sync_counts(s);
     const double t1 = tr ? now() : 0;
@@ -539,7 +532,7 @@ void gather_stream(jg_ctx* ctx, const jg_stream_soa& st, const std::vector<uint6
     JG_HIP(hipMemcpyAsync(m, src.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
     JG_HIP(hipMemcpyAsync(m + n, len.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
     JG_HIP(hipMemcpyAsync(m + 2 * n, off.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_ranges, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(st), m, m + n, m + 2 * n, n,
+    hipLaunchKernelGGL(k_gather_ranges, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, view(st), m, m + n, m + 2 * n, n,
                        data.as<jg_tagrec>());
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemcpyAsync(out.data(), data.p, off[n] * sizeof(jg_tagrec), hipMemcpyDeviceToHost, ctx->stream));
@@ -558,7 +551,7 @@ Runs fetch_runs(jg_orset* s, const std::vector<unsigned long long>& keys) {
     auto* dq = q.as<unsigned long long>();
     auto* db = reinterpret_cast<uint64_t*>(dq + n);
     JG_HIP(hipMemcpyAsync(dq, keys.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_runs, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dq, n, db);
+    hipLaunchKernelGGL(k_runs, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dq, n, db);
     JG_HIP(hipGetLastError());
     std::vector<uint64_t> bounds(4 * n);
     JG_HIP(hipMemcpyAsync(bounds.data(), db, 4 * n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -598,7 +591,7 @@ void load_group(const jg_tagrec* b, const jg_tagrec* e, std::vector<TagKey>& ord
 void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
                const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim = nullptr, uint64_t* rem_lim = nullptr) {
     static const bool tr = std::getenv("JANUS_TRACE_APPLY") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e3; };
+    const auto now = [] { return jg::now_us() * 1e-3; };  // this trace line is in ms
     double tp[6] = {tr ? now() : 0};
     // the ops grouped by set, op order kept within a set: a counting sort when the set ids are dense enough (the
     // comparison sort cost 2-5 ms of host time per 50-100k ORSetWorkload ops, JANUS_TRACE_APPLY), else a stable sort
@@ -803,21 +796,19 @@ void jg_stream_soa::reserve_records(uint64_t records) {
     // a growing store's reservation ~2.3 ms), the new block first, then the old one freed: hipMalloc does not
     // wait for the device, hipFree does, so a reservation made while the device is still busy
     // (orset_reserve_union, during a wave's uploads) costs the host that wait, not the device an idle gap
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t sz[6] = {al(slots * 8), al(slots * 16), al(slots * 4), al((c ? c : 1) * 4), al((c + 1) * 8), al(((slots >> jgk::kQShift) + 2) * 4)};
+    const size_t sz[6] = {slots * 8, slots * 16, slots * 4, (c ? c : 1) * 4, (c + 1) * 8, ((slots >> jgk::kQShift) + 2) * 4};
+    jg::Layout L;
+    size_t at[6];
+    for (int i = 0; i < 6; ++i) at[i] = L.skip(sz[i], 256);
     static const bool tr = std::getenv("JANUS_TRACE_MERGE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = jg::now_us();
     jg::DevBuf nb;
-    nb.alloc(sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5]);
-    const auto t1 = std::chrono::steady_clock::now();
+    nb.alloc(L.bytes());
+    const double t1 = jg::now_us();
     std::swap(block.p, nb.p);
     std::swap(block.bytes, nb.bytes);
     jg::DevBuf* cur[6] = {&key, &tag, &ord, &cnt, &off, &lut};
-    char* q = block.as<char>();
-    for (int i = 0; i < 6; ++i) {
-        cur[i]->view(q, sz[i]);
-        q += sz[i];
-    }
+    for (int i = 0; i < 6; ++i) cur[i]->view(block.as<char>() + at[i], jg::round_up(sz[i], 256));
     cap_chunks = c;
     // the old block is retired, not freed: hipFree waits for the whole device and then costs ms of host time on
     // the box (measured inside a node wave: 2.9-5.7 ms, uploads in flight).  Retired blocks are freed at the
@@ -830,7 +821,7 @@ void jg_stream_soa::reserve_records(uint64_t records) {
     }
     if (tr)
         std::fprintf(stderr, "reserve_records: %llu records: hipMalloc %.0f us\n", (unsigned long long)(c * kChunk),
-                     std::chrono::duration<double>(t1 - t0).count() * 1e6);
+                     t1 - t0);
 }
 
 jg_stream_soa::~jg_stream_soa() { free_retired(); }
@@ -845,7 +836,7 @@ void set_dense(jg_ctx* ctx, jg_stream_soa& s, uint64_t n) {
     s.reserve_records(n);
     const uint64_t nch = (n + kChunk - 1) / kChunk;
     const uint64_t nlut = (n >> jgk::kQShift) + 2;
-    hipLaunchKernelGGL(jgk::k_dense_meta, dim3(grid_for(ctx, std::max(nch + 1, nlut), 4)), dim3(256), 0, ctx->stream, n, kChunk, (uint32_t)nch,
+    hipLaunchKernelGGL(jgk::k_dense_meta, dim3(jg::grid_for(ctx, std::max(nch + 1, nlut), kOB, 4)), dim3(256), 0, ctx->stream, n, kChunk, (uint32_t)nch,
                        s.cnt.as<uint32_t>(), s.off.as<uint64_t>(), s.lut.as<uint32_t>(), nlut);
     JG_HIP(hipGetLastError());
     s.n = n;
@@ -867,22 +858,23 @@ OrsetGathered orset_gather_sets(jg_orset* s, uint64_t n, const uint32_t* d_sets,
     auto* bounds = buf.as<uint64_t>();
     auto* cnt = reinterpret_cast<unsigned long long*>(bounds + 4 * n);
     auto* roff = cnt + 2 * n + 1;
-    hipLaunchKernelGGL(k_set_runs, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), d_sets, n, bounds);
-    hipLaunchKernelGGL(k_raw_counts, dim3((unsigned)((2 * n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, bounds, n, cnt);
+    hipLaunchKernelGGL(k_set_runs, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), d_sets, n, bounds);
+    hipLaunchKernelGGL(k_raw_counts, dim3(jg::blocks_for(2 * n + 1)), dim3(256), 0, ctx->stream, bounds, n, cnt);
     JG_HIP(hipGetLastError());
-    size_t temp = 0;
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, cnt, roff, (int)(2 * n + 1), ctx->stream));
-    void* tmp = jg::scratch(ctx, ctx->scratch3, temp + 256);
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, temp, cnt, roff, (int)(2 * n + 1), ctx->stream));
+    const int n_cnt = jg::cub_count(2 * n + 1, "set segments");
+    jg::cub_run(jg::cub_in(ctx, ctx->scratch3),
+                [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, roff, n_cnt, ctx->stream); });
     jg::pin_get(ctx, 0, roff + 2 * n, 8);
     jg::pin_sync(ctx);
     std::memcpy(&o.R, jg::pin_at(ctx, 0), 8);
     JG_REQUIRE(o.R < 0x7FFFFFF0ull, JG_EINVAL, "jg_orset_encode_json: %llu records exceed one call", (unsigned long long)o.R);
     o.roff = roff;
     if (o.R == 0) return o;
-    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-    const uint64_t head = al(n * 32 + (2 * n + 1) * 16);
-    const uint64_t need = head + 3 * al(o.R * 8) + 2 * al(o.R * 4) + al(o.R);
+    jg::Layout L;
+    L.skip(n * 32 + (2 * n + 1) * 16);  // bounds, cnt, roff (above)
+    const uint64_t head = L.add(o.key, o.R);
+    L.add(o.tlo, o.R), L.add(o.thi, o.R), L.add(o.ord, o.R), L.add(o.qs, o.R), L.add(o.keep, o.R);
+    const uint64_t need = L.bytes();
     if (buf.bytes < need) {  // grown keeping the bounds and offsets
         jg::DevBuf nb;
         nb.alloc(need + need / 4);
@@ -894,14 +886,8 @@ OrsetGathered orset_gather_sets(jg_orset* s, uint64_t n, const uint32_t* d_sets,
         roff = reinterpret_cast<unsigned long long*>(bounds + 4 * n) + 2 * n + 1;
         o.roff = roff;
     }
-    char* p = buf.as<char>() + head;
-    o.key = reinterpret_cast<unsigned long long*>(p);
-    o.tlo = reinterpret_cast<unsigned long long*>(p + al(o.R * 8));
-    o.thi = reinterpret_cast<unsigned long long*>(p + 2 * al(o.R * 8));
-    o.ord = reinterpret_cast<uint32_t*>(p + 3 * al(o.R * 8));
-    o.qs = reinterpret_cast<uint32_t*>(p + 3 * al(o.R * 8) + al(o.R * 4));
-    o.keep = reinterpret_cast<uint8_t*>(p + 3 * al(o.R * 8) + 2 * al(o.R * 4));
-    hipLaunchKernelGGL(k_gather_raw, dim3(grid_for(ctx, o.R, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), bounds, roff, n, o.R, d_lim,
+    L.bind(buf.p);
+    hipLaunchKernelGGL(k_gather_raw, dim3(jg::grid_for(ctx, o.R, kOB, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), bounds, roff, n, o.R, d_lim,
                        o.key, o.tlo, o.thi, o.ord, o.qs, o.keep);
     JG_HIP(hipGetLastError());
     return o;
@@ -929,7 +915,7 @@ uint64_t ord_span(jg_ctx* ctx, const uint32_t* ord, uint64_t n) {
     if (n == 0) return 0;
     auto* span = reinterpret_cast<unsigned long long*>(ctx->flags.as<char>() + 64);
     JG_HIP(hipMemsetAsync(span, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_ord_span, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, ord, n, span);
+    hipLaunchKernelGGL(k_ord_span, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, ord, n, span);
     JG_HIP(hipGetLastError());
     unsigned long long h = 0;
     JG_HIP(hipMemcpyAsync(&h, span, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -956,7 +942,7 @@ void orset_merge_runs(jg_orset* s, uint32_t n_runs, const uint64_t* add_counts, 
         JG_HIP(hipMemcpyAsync(st.tag.p, t, n * 16, hipMemcpyDeviceToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(st.ord.p, o, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
         st.next = ord_span(ctx, st.ord.as<uint32_t>(), n);
-        hipLaunchKernelGGL(k_check_sorted, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, st.key.as<unsigned long long>(),
+        hipLaunchKernelGGL(k_check_sorted, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, st.key.as<unsigned long long>(),
                            st.tag.as<uint4>(), n, ctx->flags.as<unsigned>());
         JG_HIP(hipGetLastError());
     };
@@ -1023,12 +1009,12 @@ void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in) {
 // ids to the record side of jg_orset_apply_ops(_ords).
 void orset_contains_device(jg_orset* s, const unsigned long long* d_q, uint64_t n, uint8_t* d_out, const uint32_t* d_at,
                            const unsigned long long* d_count, long long* d_out64) {
-    hipLaunchKernelGGL(k_contains, dim3(grid_for(s->ctx, n, 16)), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_q, n, d_out, d_at,
+    hipLaunchKernelGGL(k_contains, dim3(jg::grid_for(s->ctx, n, kOB, 16)), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_q, n, d_out, d_at,
                        d_count, d_out64);
     JG_HIP(hipGetLastError());
 }
 void orset_lookup_all_device(jg_orset* s, const uint32_t* d_set, uint64_t n, uint64_t* d_cnt_off, uint32_t* d_out) {
-    const unsigned g = grid_for(s->ctx, n, 16);
+    const unsigned g = jg::grid_for(s->ctx, n, kOB, 16);
     if (d_out) hipLaunchKernelGGL(k_lookup_all<1>, dim3(g), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_set, n, d_cnt_off, d_out);
     else hipLaunchKernelGGL(k_lookup_all<0>, dim3(g), dim3(kOB), 0, s->ctx->stream, view(s->add), view(s->rem), d_set, n, d_cnt_off, d_out);
     JG_HIP(hipGetLastError());
@@ -1210,7 +1196,7 @@ int jg_orset_contains(jg_orset* s, const uint32_t* set, const uint32_t* elem, ui
         auto* dq = reinterpret_cast<unsigned long long*>(st);
         auto* dout = reinterpret_cast<uint8_t*>(st + n * 8);
         JG_HIP(hipMemcpyAsync(dq, q.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_contains, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dq, n, dout,
+        hipLaunchKernelGGL(k_contains, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dq, n, dout,
                            (const uint32_t*)nullptr, (const unsigned long long*)nullptr, (long long*)nullptr);
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1232,9 +1218,9 @@ int jg_orset_read_sets(jg_orset* s, uint64_t n, const uint32_t* set, uint64_t* a
         jg::DevBuf q;
         q.alloc(n * 4 + n * 32 + 64);
         auto* dset = q.as<uint32_t>();
-        auto* db = reinterpret_cast<uint64_t*>(q.as<char>() + ((n * 4 + 15) & ~15ull));
+        auto* db = reinterpret_cast<uint64_t*>(q.as<char>() + jg::round_up(n * 4, 16));
         JG_HIP(hipMemcpyAsync(dset, set, n * 4, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_set_runs, dim3(grid_for(ctx, n, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dset, n, db);
+        hipLaunchKernelGGL(k_set_runs, dim3(jg::grid_for(ctx, n, kOB, 16)), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dset, n, db);
         JG_HIP(hipGetLastError());
         std::vector<uint64_t> bounds(4 * n);
         JG_HIP(hipMemcpyAsync(bounds.data(), db, 4 * n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1268,9 +1254,9 @@ int jg_orset_lookup_all(jg_orset* s, uint64_t n, const uint32_t* set, uint64_t* 
         jg::sync_counts(s);
         char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * 12 + 64));
         auto* dset = reinterpret_cast<uint32_t*>(st);
-        auto* dcnt = reinterpret_cast<uint64_t*>(st + ((n * 4 + 15) & ~15ull));
+        auto* dcnt = reinterpret_cast<uint64_t*>(st + jg::round_up(n * 4, 16));
         JG_HIP(hipMemcpyAsync(dset, set, n * 4, hipMemcpyHostToDevice, ctx->stream));
-        const unsigned g = grid_for(ctx, n, 16);
+        const unsigned g = jg::grid_for(ctx, n, kOB, 16);
         hipLaunchKernelGGL(k_lookup_all<0>, dim3(g), dim3(kOB), 0, ctx->stream, view(s->add), view(s->rem), dset, n, dcnt, nullptr);
         JG_HIP(hipGetLastError());
         std::vector<uint64_t> cnt(n);

@@ -33,7 +33,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "orset_names.hpp"
 
 namespace {
@@ -45,13 +45,7 @@ constexpr uint32_t kNever = JG_NULL_ELEM - 1;  // "never allocated": the id no r
 constexpr uint32_t kMaxSet = 0xFFFFFFF0u;      // set ids stay below it (as jg_orset_wave_append)
 constexpr unsigned long long kNoWin = ~0ull;
 
-unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
-
-uint64_t pow2_at_least(uint64_t x) {
-    uint64_t p = 64;
-    while (p < x) p <<= 1;
-    return p;
-}
+using jg::blocks_for;
 
 // The uploaded name arrays (one staging copy): meta = is_null | op << 1 (op 0 for the read-only calls).
 struct Staged {
@@ -269,8 +263,6 @@ __global__ void k_nm_sets(Names N, const unsigned long long* __restrict__ skey, 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
-size_t up8(size_t x) { return (x + 7) & ~size_t(7); }
-
 // Argument checks of a name array (before anything changes); returns the largest set id + 1.
 uint64_t check_names(const char* fn, uint64_t n, const uint32_t* set, const uint64_t* off, const uint8_t* bytes, const uint8_t* is_null) {
     JG_REQUIRE(set && off && is_null, JG_EINVAL, "%s: NULL argument", fn);
@@ -295,7 +287,7 @@ struct Packed {
         at_cset = at_epoch + n * 4;
         at_ccnt = at_cset + nc * 4;
         at_meta = at_ccnt + nc * 4;
-        at_bytes = up8(at_meta + n);
+        at_bytes = jg::round_up(at_meta + n, 8);
         h.resize(at_bytes + off[n]);
         std::memcpy(h.data(), off, (n + 1) * 8);
         std::memcpy(h.data() + at_set, set, n * 4);
@@ -322,9 +314,11 @@ Resolved resolve_on_device(jg_orset* s, Packed& P, uint64_t n, const uint8_t* is
     std::memset(P.epoch(), 0, n * 4);
     for (uint64_t i = 0; i < n; ++i) P.meta()[i] = is_null[i] ? 1 : 0;
     const jg::NamesRef R = jg::orset_names_ref(s, 0, 0, 0);
-    const size_t stage = up8(P.h.size());
-    auto* d = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch, stage + n * 8 + up8(n * 4) + n + 64));
-    Resolved r{reinterpret_cast<uint32_t*>(d + stage + n * 8), reinterpret_cast<unsigned long long*>(d + stage), d + stage + n * 8 + up8(n * 4)};
+    Resolved r{};
+    uint8_t* d;  // the staged arrays, at the block's start
+    jg::Layout L;
+    L.add(d, P.h.size(), 8), L.add(r.q, n, 8), L.add(r.elem, n, 8), L.add(r.out, n, 8);
+    L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 64));
     JG_HIP(hipMemcpyAsync(d, P.h.data(), P.h.size(), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_nm_resolve, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, R.N, R.set_cap, R.kmask, R.salt, P.on(d), n, r.elem, r.q);
     JG_HIP(hipGetLastError());
@@ -332,10 +326,9 @@ Resolved resolve_on_device(jg_orset* s, Packed& P, uint64_t n, const uint8_t* is
 }
 
 void scan_in_place(jg_ctx* ctx, unsigned long long* d, uint64_t n) {
-    size_t tb = 0;
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d, d, (int)n, ctx->stream));
-    void* tmp = jg::scratch(ctx, ctx->scratch3, tb + 64);
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, d, d, (int)n, ctx->stream));
+    const int items = jg::cub_count(n);
+    jg::cub_run(jg::cub_in(ctx, ctx->scratch3),
+                [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, d, d, items, ctx->stream); });
 }
 
 }  // namespace
@@ -410,12 +403,13 @@ int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint
         if (total == 0) return;
         JG_REQUIRE(total < 0x7FFFFFF0ull, JG_ESTATE, "jg_orset_lookup_all_names: more than 2^31 members in one call");
         // their names: lengths through the (set, id) index, offsets by a scan
-        auto* m = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, (total + 2) * 8 + total * 9 + 64));
-        auto* dnoff = reinterpret_cast<unsigned long long*>(m);
+        unsigned long long* dnoff;
+        uint32_t *delem, *dg;
+        uint8_t* dnull;
+        jg::Layout L;
+        L.add(dnoff, total + 2, 8), L.add(delem, total, 4), L.add(dg, total, 4), L.add(dnull, total, 1);
+        L.bind(jg::scratch(ctx, ctx->scratch2, L.bytes() + 64));
         auto* dmiss = dnoff + total + 1;  // raised by a member whose id has no name
-        auto* delem = reinterpret_cast<uint32_t*>(m + (total + 2) * 8);
-        auto* dg = delem + total;
-        auto* dnull = reinterpret_cast<uint8_t*>(dg + total);
         JG_HIP(hipMemsetAsync(dnoff + total, 0, 16, ctx->stream));
         jg::orset_lookup_all_device(s, dset, n, reinterpret_cast<uint64_t*>(dmoff), delem);
         hipLaunchKernelGGL(k_nm_lens, dim3(blocks_for(total)), dim3(kBlock), 0, ctx->stream, R.N, reinterpret_cast<const uint64_t*>(dmoff), n, dset,
@@ -490,37 +484,33 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
         // every allocation first: room for the sets, the tables, the call's own block
         jg::NamesRef R = jg::orset_names_ref(s, n_sets, 0, 0);
         JG_REQUIRE(!R.open, JG_EINVAL, "jg_orset_apply_ops_names: a wave is open");
-        const uint64_t ccap = pow2_at_least(2 * n_add);
+        const uint64_t ccap = jg::pow2_at_least(2 * n_add, 64);
         // the winners' sort orders on the set's bits and the op index (an unset key, all ones, sorts last either way)
         int key_bits = 32;
         while (key_bits < 64 && (n_sets - 1) >> (key_bits - 32)) ++key_bits;
-        size_t tb_sort = 0, tb_scan = 0;
-        JG_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n, 0,
-                                                 key_bits, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(n + 1),
-                                                ctx->stream));
-        tb_sort = std::max(tb_sort, tb_scan);
-        const size_t a_stage = 0, a_cslot = up8(P.h.size()), a_nkey = a_cslot + ccap * 8, a_cnt = a_nkey + n * 8, a_len = a_cnt + (n + 1) * 8,
-                     a_wkey = a_len + (n + 1) * 8, a_skey = a_wkey + n * 8, a_st = a_skey + n * 8, a_first = a_st + 16, a_rid = a_first + up8(ccap * 4),
-                     a_slot = a_rid + up8(n * 4), a_newid = a_slot + up8(n * 4), a_elem = a_newid + up8(n * 4), a_tmp = (a_elem + up8(n * 4) + 255) & ~size_t(255),
-                     a_end = a_tmp + tb_sort + 64;
+        using ull = unsigned long long;
+        const int n_i = jg::cub_count(n, "ops"), n1_i = jg::cub_count(n + 1, "ops");
+        // the two scans and the sort share one workspace, one after the other on the stream
+        const size_t tb = std::max(jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                                       return hipcub::DeviceRadixSort::SortKeys(temp, bytes, (const ull*)nullptr, (ull*)nullptr, n_i, 0, key_bits, ctx->stream);
+                                   }),
+                                   jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                                       return hipcub::DeviceScan::ExclusiveSum(temp, bytes, (ull*)nullptr, (ull*)nullptr, n1_i, ctx->stream);
+                                   }));
+        uint8_t *dstage, *dtmp;
+        Cand C{nullptr, nullptr, ccap - 1};
+        ull *nkey, *cnt, *len, *wkey, *skey, *st;
+        uint32_t *rid, *slot, *newid, *delem;
+        jg::Layout L;
+        L.add(dstage, P.h.size(), 8), L.add(C.slot, ccap, 8), L.add(nkey, n, 8), L.add(cnt, n + 1, 8), L.add(len, n + 1, 8), L.add(wkey, n, 8);
+        L.add(skey, n, 8), L.add(st, 2, 8), L.add(C.first, ccap, 8), L.add(rid, n, 8), L.add(slot, n, 8), L.add(newid, n, 8), L.add(delem, n, 8);
+        L.add(dtmp, tb + 64);
         jg::DevBuf blk;  // the call's own block: the record side below reuses the context's scratch
-        blk.alloc(a_end);
-        uint8_t* d = blk.as<uint8_t>();
-        const Staged S = P.on(d + a_stage);
-        const Cand C{reinterpret_cast<unsigned long long*>(d + a_cslot), reinterpret_cast<uint32_t*>(d + a_first), ccap - 1};
-        auto* nkey = reinterpret_cast<unsigned long long*>(d + a_nkey);
-        auto* cnt = reinterpret_cast<unsigned long long*>(d + a_cnt);
-        auto* len = reinterpret_cast<unsigned long long*>(d + a_len);
-        auto* wkey = reinterpret_cast<unsigned long long*>(d + a_wkey);
-        auto* skey = reinterpret_cast<unsigned long long*>(d + a_skey);
-        auto* st = reinterpret_cast<unsigned long long*>(d + a_st);
-        auto* rid = reinterpret_cast<uint32_t*>(d + a_rid);
-        auto* slot = reinterpret_cast<uint32_t*>(d + a_slot);
-        auto* newid = reinterpret_cast<uint32_t*>(d + a_newid);
-        auto* delem = reinterpret_cast<uint32_t*>(d + a_elem);
-        const auto* dcset = reinterpret_cast<const uint32_t*>(d + a_stage + P.at_cset);
-        const auto* dccnt = reinterpret_cast<const uint32_t*>(d + a_stage + P.at_ccnt);
+        blk.alloc(L.bytes());
+        L.bind(blk.p);
+        const Staged S = P.on(dstage);
+        const auto* dcset = reinterpret_cast<const uint32_t*>(dstage + P.at_cset);
+        const auto* dccnt = reinterpret_cast<const uint32_t*>(dstage + P.at_ccnt);
 
         // JANUS_TRACE_APPLY (as jg_orset_apply_ops): the launches' device time beside the record side's host line
         static const bool tr = std::getenv("JANUS_TRACE_APPLY") != nullptr;
@@ -533,21 +523,21 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
 
         // resolve and intern (the table itself is only read)
         stamp(0);
-        JG_HIP(hipMemcpyAsync(d + a_stage, P.h.data(), P.h.size(), hipMemcpyHostToDevice, ctx->stream));
+        JG_HIP(hipMemcpyAsync(dstage, P.h.data(), P.h.size(), hipMemcpyHostToDevice, ctx->stream));
         stamp(1);
-        JG_HIP(hipMemsetAsync(d + a_cslot, 0, ccap * 8, ctx->stream));
-        JG_HIP(hipMemsetAsync(d + a_first, 0xFF, ccap * 4, ctx->stream));
+        JG_HIP(hipMemsetAsync(C.slot, 0, ccap * 8, ctx->stream));
+        JG_HIP(hipMemsetAsync(C.first, 0xFF, ccap * 4, ctx->stream));
         JG_HIP(hipMemsetAsync(st, 0, 16, ctx->stream));
         const dim3 grid(blocks_for(n + 1)), block(kBlock);
         hipLaunchKernelGGL(k_nm_claim, grid, block, 0, ctx->stream, R.N, R.kmask, R.salt, S, n, C, rid, nkey, slot);
         hipLaunchKernelGGL(k_nm_win, grid, block, 0, ctx->stream, S, n, C, slot, cnt, len, wkey);
         JG_HIP(hipGetLastError());
-        {
-            size_t tb = tb_sort;  // the three share one workspace, one after the other on the stream
-            JG_HIP(hipcub::DeviceScan::ExclusiveSum(d + a_tmp, tb, cnt, cnt, (int)(n + 1), ctx->stream));
-            JG_HIP(hipcub::DeviceScan::ExclusiveSum(d + a_tmp, tb, len, len, (int)(n + 1), ctx->stream));
-            JG_HIP(hipcub::DeviceRadixSort::SortKeys(d + a_tmp, tb, wkey, skey, (int)n, 0, key_bits, ctx->stream));
-        }
+        const auto tmp = jg::cub_in(dtmp, tb);
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, cnt, n1_i, ctx->stream); });
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, len, len, n1_i, ctx->stream); });
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceRadixSort::SortKeys(temp, bytes, wkey, skey, n_i, 0, key_bits, ctx->stream);
+        });
         hipLaunchKernelGGL(k_nm_assign, grid, block, 0, ctx->stream, R.N, skey, n, newid, st);
         hipLaunchKernelGGL(k_nm_ids, grid, block, 0, ctx->stream, S, n, C, rid, nkey, slot, newid, delem);
         JG_HIP(hipGetLastError());

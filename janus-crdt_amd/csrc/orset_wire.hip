@@ -35,13 +35,12 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <random>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "orset_names.hpp"
 #include "wire_cursor.hpp"
 
@@ -62,7 +61,9 @@ constexpr uint32_t kDead = 0xFFFFFFFFu;                        // id of an entry
 
 struct Tag16 { unsigned long long lo, hi; };
 
-unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
+using jg::blocks_for;
+using jg::ensure;
+using jg::grow_keep;
 
 // ---- string sinks: read_string feeds each unescaped UTF-8 byte to put(), esc() at a backslash -------
 __constant__ char kProp[4][16] = {"addSet", "removeSet", "nullAddGuid", "nullRemoveGuid"};
@@ -849,11 +850,6 @@ __global__ void k_gather_recs(const unsigned long long* __restrict__ dk, const T
 #include "orset_tables.hpp"
 #include "orset_commit.hpp"
 
-uint64_t pow2_at_least(uint64_t x) {
-    uint64_t p = 1024;
-    while (p < x) p <<= 1;
-    return p;
-}
 
 int bits_for(uint64_t x) {
     int b = 1;
@@ -1214,35 +1210,6 @@ struct jg_orset_wire {
 
 namespace {
 
-void ensure(jg::DevBuf& b, size_t bytes) {
-    if (b.bytes < bytes) b.alloc(bytes + bytes / 4 + 256);
-}
-
-// Grow to `need` bytes keeping the first `keep` bytes; the new tail is zeroed when `zero`.
-// retire: the old block goes there instead of hipFree (the element table grows wave after wave, and each
-// hipFree costs ~0.2 ms of host time on the box: six arrays per growth); freed by jg::orset_free_retired at the
-// end of the wave (node wave, synchronous merge).
-void grow_keep(jg_ctx* ctx, jg::DevBuf& b, size_t need, size_t keep, bool zero = false, std::vector<void*>* retire = nullptr) {
-    if (b.bytes >= need) return;
-    if (ctx->copy) JG_HIP(hipStreamSynchronize(ctx->copy));  // uploads still landing in the old block
-    jg::DevBuf nb;
-    nb.alloc(need + need / 2);
-    if (zero) JG_HIP(hipMemsetAsync(nb.p, 0, nb.bytes, ctx->stream));
-    keep = std::min(keep, b.p ? b.bytes : 0);
-    if (keep) JG_HIP(hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream));
-    // a retired block lives until the wave has drained: the kernels queued before this copy may still use it, and
-    // those queued after it use the new one (stream order) — no host wait in the middle of a commit (~30 us each,
-    // six arrays per names growth).  A block freed right here needs the stream idle first.
-    if (!retire) JG_HIP(hipStreamSynchronize(ctx->stream));
-    std::swap(nb.p, b.p);
-    std::swap(nb.bytes, b.bytes);
-    if (retire && nb.p) {
-        retire->push_back(nb.p);
-        nb.p = nullptr;
-        nb.bytes = 0;
-    }
-}
-
 jg_orset_wire* wire_of(jg_orset* s) {
     if (!s->wire) {
         s->wire = new jg_orset_wire();
@@ -1297,7 +1264,7 @@ void ensure_names(jg_ctx* ctx, jg_orset_wire* w, uint64_t incoming, uint64_t poo
         w->pool_cap = w->pool.bytes;
     }
     if (w->tab_cap == 0 || 2 * total > w->tab_cap) {
-        const uint64_t cap = pow2_at_least(4 * total);
+        const uint64_t cap = jg::pow2_at_least(4 * total, 1024);
         if (w->tab.p) {  // retired, not freed (see grow_keep)
             w->retired.push_back(w->tab.p);
             w->tab.p = nullptr;
@@ -1312,7 +1279,7 @@ void ensure_names(jg_ctx* ctx, jg_orset_wire* w, uint64_t incoming, uint64_t poo
         }
     }
     if (w->itab_cap == 0 || 2 * total > w->itab_cap) {  // the (set, id) index: every name, load <= 1/2
-        const uint64_t cap = pow2_at_least(4 * total);
+        const uint64_t cap = jg::pow2_at_least(4 * total, 1024);
         for (jg::DevBuf* b : {&w->ikey, &w->ival})
             if (b->p) {
                 w->retired.push_back(b->p);
@@ -1339,7 +1306,7 @@ void read_words(jg_ctx* ctx, const unsigned long long* d, unsigned long long* h,
 }
 
 // Page-locked layout of a names copy: set [n] u32 | id [n] u32 | len [n] u32 | pad | pool offset [n] u64 | pool bytes.
-size_t names_out_bytes(uint64_t n, uint64_t nb) { return ((n * 12 + 15) & ~15ull) + n * 8 + nb; }
+size_t names_out_bytes(uint64_t n, uint64_t nb) { return jg::round_up(n * 12, 16) + n * 8 + nb; }
 
 // Queue the copy of the names [g0, g1) / pool bytes [p0, p1) the last commit issued (async on ctx->stream).
 void queue_names(jg_ctx* ctx, jg_orset_wire* w) {
@@ -1372,16 +1339,11 @@ void queue_names(jg_ctx* ctx, jg_orset_wire* w) {
     JG_HIP(hipMemcpyAsync(h, w->nset.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, q));
     JG_HIP(hipMemcpyAsync(h + n * 4, w->nid.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, q));
     JG_HIP(hipMemcpyAsync(h + n * 8, w->nlen.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, q));
-    const size_t po = (n * 12 + 15) & ~15ull;
+    const size_t po = jg::round_up(n * 12, 16);
     JG_HIP(hipMemcpyAsync(h + po, w->noff.as<unsigned long long>() + w->g0, n * 8, hipMemcpyDeviceToHost, q));
     if (nb) JG_HIP(hipMemcpyAsync(h + po + n * 8, w->pool.as<uint8_t>() + w->p0, nb, hipMemcpyDeviceToHost, q));
     JG_HIP(hipEventRecord(o.ev, q));
     o.g0 = w->g0, o.g1 = w->g1, o.p0 = w->p0, o.p1 = w->p1;
-}
-
-void* cub_temp(jg_orset_wire* w, size_t bytes) {
-    ensure(w->cub, bytes);
-    return w->cub.p;
 }
 
 // id_bound sums the names every commit issued over ALL sets, so on a store with many sets it grows far past any
@@ -1392,10 +1354,11 @@ void* cub_temp(jg_orset_wire* w, size_t bytes) {
 uint64_t tight_id_bound(jg_ctx* ctx, jg_orset_wire* w) {
     if (w->set_cap == 0) return w->id_bound = 0;
     ensure(w->idmax, 16);
-    size_t temp = 0;
     const uint32_t* nx = w->next_id.as<uint32_t>();
-    JG_HIP(hipcub::DeviceReduce::Max(nullptr, temp, nx, w->idmax.as<uint32_t>(), (int)w->set_cap, ctx->stream));
-    JG_HIP(hipcub::DeviceReduce::Max(cub_temp(w, temp), temp, nx, w->idmax.as<uint32_t>(), (int)w->set_cap, ctx->stream));
+    const int n_sets = jg::cub_count(w->set_cap, "sets");
+    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceReduce::Max(temp, bytes, nx, w->idmax.as<uint32_t>(), n_sets, ctx->stream);
+    });
     jg::pin_get(ctx, 0, w->idmax.p, 4);
     jg::pin_sync(ctx);
     uint32_t mx;
@@ -1430,17 +1393,18 @@ void check_id_room(jg_ctx* ctx, jg_orset_wire* w, uint64_t incoming, uint64_t n_
 template <class K, class V>
 void sort_pairs(jg_ctx* ctx, jg_orset_wire* w, const K* kin, K* kout, const V* vin, V* vout, uint64_t n, int end_bit) {
     if (n == 0) return;
-    size_t temp = 0;
-    JG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream));
-    JG_HIP(hipcub::DeviceRadixSort::SortPairs(cub_temp(w, temp), temp, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream));
+    const int items = jg::cub_count(n, "entries");
+    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceRadixSort::SortPairs(temp, bytes, kin, kout, vin, vout, items, 0, end_bit, ctx->stream);
+    });
 }
 
 // Indices i in [0, n) with pred(i), in order, into idx; their number into *count (device).
 template <class Pred> void select_marked(jg_ctx* ctx, jg_orset_wire* w, Pred pred, uint64_t n, uint32_t* idx, unsigned long long* count) {
     hipcub::CountingInputIterator<uint32_t> it(0);
-    size_t temp = 0;
-    JG_HIP(hipcub::DeviceSelect::If(nullptr, temp, it, idx, count, (int)n, pred, ctx->stream));
-    JG_HIP(hipcub::DeviceSelect::If(cub_temp(w, temp), temp, it, idx, count, (int)n, pred, ctx->stream));
+    const int items = jg::cub_count(n, "entries");
+    jg::cub_run(jg::cub_in(w->cub),
+                [&](void* temp, size_t& bytes) { return hipcub::DeviceSelect::If(temp, bytes, it, idx, count, items, pred, ctx->stream); });
 }
 
 void grow_wave(jg_ctx* ctx, jg_orset_wire* w, uint64_t msgs, uint64_t bytes) {
@@ -1477,9 +1441,9 @@ void grow_wave(jg_ctx* ctx, jg_orset_wire* w, uint64_t msgs, uint64_t bytes) {
         grow_keep(ctx, w->off, (cap + 1) * 8, (m + 1) * 8);
         grow_keep(ctx, w->mset, cap * 4, m * 4);
     }
-    if (w->bytes.bytes < ((bytes + 15) & ~15ull) + 16) {
+    if (w->bytes.bytes < jg::round_up(bytes, 16) + 16) {
         const uint64_t cap = std::max<uint64_t>(bytes + bytes / 2, 1 << 16);
-        grow_keep(ctx, w->bytes, ((cap + 15) & ~15ull) + 16, w->wnb);  // the cursor reads aligned 16-byte windows
+        grow_keep(ctx, w->bytes, jg::round_up(cap, 16) + 16, w->wnb);  // the cursor reads aligned 16-byte windows
     }
     w->vbytes = w->bytes.as<uint8_t>();
     w->voff = w->off.as<uint64_t>();
@@ -1527,8 +1491,8 @@ void tables_begin(jg_ctx* ctx, jg_orset_wire* w, uint64_t n_msgs, uint64_t nbyte
     const bool strict = e && std::strcmp(e, "tables") == 0;
     const uint64_t want_s = w->seen_s && !strict ? std::min(bound_s, 4 * w->seen_s + 65536) : bound_s;
     const uint64_t want_r = w->seen_r && !strict ? std::min(bound_r, 4 * w->seen_r + 65536) : bound_r;
-    const uint64_t sc = std::min(lim, pow2_at_least(std::max<uint64_t>(4096, want_s)));
-    const uint64_t rc = std::min(lim, pow2_at_least(std::max<uint64_t>(4096, want_r)));
+    const uint64_t sc = std::min(lim, jg::pow2_at_least(std::max<uint64_t>(4096, want_s), 1024));
+    const uint64_t rc = std::min(lim, jg::pow2_at_least(std::max<uint64_t>(4096, want_r), 1024));
     if (w->st_alloc < sc) {  // allocations only grow; the active part is the first st_cap slots
         w->st_slot.alloc(sc * sizeof(StrSlot));
         w->st_list.alloc((sc / 8) * kLists * 4);  // sub-lists of cap / 8 (a table is at most half full)
@@ -1549,9 +1513,9 @@ void tables_begin(jg_ctx* ctx, jg_orset_wire* w, uint64_t n_msgs, uint64_t nbyte
     if (!w->ovf.p) w->ovf.alloc((1 + 2 * kLists) * kCountStride * 8);
     ensure(w->loffs, 2 * (kLists + 1) * 8);
     ensure(w->specst, sizeof w->spec_h);
-    hipLaunchKernelGGL(k_str_clear, dim3((unsigned)std::min<uint64_t>(4096, (2 * w->st_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(k_str_clear, dim3(std::min(4096u, blocks_for(2 * w->st_cap))), dim3(kBlock), 0, ctx->stream,
                        w->st_slot.as<uint4>(), w->st_cap);
-    hipLaunchKernelGGL(k_tab_clear, dim3((unsigned)std::min<uint64_t>(4096, (w->rt_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(k_tab_clear, dim3(std::min(4096u, blocks_for(w->rt_cap))), dim3(kBlock), 0, ctx->stream,
                        w->rt_slot.as<uint4>(), w->rt_cap);
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemsetAsync(w->ovf.p, 0, (1 + 2 * kLists) * kCountStride * 8, ctx->stream));  // overflow, uncounted, sub-list counts
@@ -1610,8 +1574,8 @@ void launch_tables(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
     // the element table and the sets' generation words as they stand (both only change at a commit); a wave
     // before the first commit has no table yet: every string is resolved by the commit
     const uint32_t set_lim = w->tab_cap ? (uint32_t)std::min<uint64_t>(w->set_cap, 0xFFFFFFFFull) : 0u;
-    const dim3 grid((unsigned)((m1 - m0 + kTabWaves - 1) / kTabWaves));  // one message per wave
-    const dim3 grid_m((unsigned)((m1 - m0 + kTabWaves * kMsgsPerWave - 1) / (kTabWaves * kMsgsPerWave)));  // kMsgsPerWave messages per wave
+    const dim3 grid(blocks_for(m1 - m0, kTabWaves));  // one message per wave
+    const dim3 grid_m(blocks_for(m1 - m0, kTabWaves * kMsgsPerWave));  // kMsgsPerWave messages per wave
     hipLaunchKernelGGL(k_ow_strings, grid, dim3(kBlock), 0, ctx->stream, S, w->voff, w->vmset, w->vbytes, w->ne.as<unsigned long long>(),
                        w->na.as<uint32_t>(), m0, m1, str_tab(w), w->err.as<unsigned long long>(), ovf, names_of(w), set_lim,
                        w->sid_id.as<uint32_t>(), claims_of(w));
@@ -1631,7 +1595,7 @@ void launch_parse(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
     uint8_t* slow = nullptr;
     if (!serial) {
         slow = w->slow.as<uint8_t>();
-        hipLaunchKernelGGL(k_ow_group, dim3((unsigned)((m1 - m0 + kOgWaves - 1) / kOgWaves)), dim3(kBlock), 0, ctx->stream, w->vbytes, w->voff,
+        hipLaunchKernelGGL(k_ow_group, dim3(blocks_for(m1 - m0, kOgWaves)), dim3(kBlock), 0, ctx->stream, w->vbytes, w->voff,
                            w->vmset, m0, m1, sparse_of(w), w->kmask, w->salt, w->ne.as<unsigned long long>(), w->nt.as<unsigned long long>(),
                            w->na.as<uint32_t>(), w->err.as<unsigned long long>(), slow);
         JG_HIP(hipGetLastError());
@@ -1649,7 +1613,6 @@ void launch_parse(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
 
 // JANUS_TRACE_MERGE: host times (us) from the check's read to the commit's first launch
 double g_tmark[6] = {};
-double tnow_us() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e6; }
 
 // Queued by the check of a table wave before its one read, for a commit of the whole wave from the claims'
 // counts (commit_buckets): both lists packed from offsets computed on the device, and the per-set counts
@@ -1716,7 +1679,7 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
         jg::pin_get(ctx, 64, w->ovf.p, w->lc.size() * 8);
         if (w->spec) jg::pin_get(ctx, at_spec, w->specst.p, sizeof w->spec_h);
         jg::pin_sync(ctx);
-        g_tmark[0] = tnow_us();
+        g_tmark[0] = jg::now_us();
         std::memcpy(w->lc.data(), jg::pin_at(ctx, 64), w->lc.size() * 8);
         if (w->spec) std::memcpy(w->spec_h, jg::pin_at(ctx, at_spec), sizeof w->spec_h);
         unsigned long long h[2];
@@ -1742,7 +1705,7 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
             uint64_t ns = 0;
             for (uint32_t j = 0; j < kLists; ++j) ns += w->lc[(1 + j) * kCountStride];
             check_id_room(ctx, w, ns, n);
-            g_tmark[1] = tnow_us();
+            g_tmark[1] = jg::now_us();
             if (h[0] == kNone) return JG_OK;
             unsigned long long e;
             JG_HIP(hipMemcpyAsync(&e, w->err.as<unsigned long long>() + h[0], 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1756,12 +1719,13 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
     JG_HIP(hipMemsetAsync(w->nt.as<unsigned long long>() + n, 0, 8, ctx->stream));
     ensure(w->eoff, (n + 1) * 8);
     ensure(w->toff, (n + 1) * 8);
-    size_t temp = 0;
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, w->ne.as<unsigned long long>(), w->eoff.as<unsigned long long>(), (int)(n + 1), ctx->stream));
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(cub_temp(w, temp), temp, w->ne.as<unsigned long long>(), w->eoff.as<unsigned long long>(), (int)(n + 1),
-                                            ctx->stream));
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(cub_temp(w, temp), temp, w->nt.as<unsigned long long>(), w->toff.as<unsigned long long>(), (int)(n + 1),
-                                            ctx->stream));
+    const int n_off = jg::cub_count(n + 1, "messages");
+    const auto offsets = [&](unsigned long long* cnt, unsigned long long* off) {
+        jg::cub_run(jg::cub_in(w->cub),
+                    [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, off, n_off, ctx->stream); });
+    };
+    offsets(w->ne.as<unsigned long long>(), w->eoff.as<unsigned long long>());
+    offsets(w->nt.as<unsigned long long>(), w->toff.as<unsigned long long>());
     unsigned long long tot[2];
     JG_HIP(hipMemcpyAsync(&tot[0], w->eoff.as<unsigned long long>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     JG_HIP(hipMemcpyAsync(&tot[1], w->toff.as<unsigned long long>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1783,7 +1747,7 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
     ensure(w->tref, nt * 8 + 8);
     ensure(w->tval, nt * 16 + 16);
     const Entries E = entries_of(w);
-    hipLaunchKernelGGL(k_ow_compact, dim3((unsigned)((n + kCompactMsgs - 1) / kCompactMsgs)), dim3(kBlock), 0, ctx->stream, w->voff, n, w->ne.as<unsigned long long>(),
+    hipLaunchKernelGGL(k_ow_compact, dim3(blocks_for(n, kCompactMsgs)), dim3(kBlock), 0, ctx->stream, w->voff, n, w->ne.as<unsigned long long>(),
                        w->nt.as<unsigned long long>(), w->na.as<uint32_t>(), w->eoff.as<unsigned long long>(), w->toff.as<unsigned long long>(),
                        w->vmset, w->vbytes, sparse_of(w), E, w->tref.as<unsigned long long>(), w->tval.as<Tag16>());
     JG_HIP(hipGetLastError());
@@ -1799,10 +1763,10 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
         hipLaunchKernelGGL(k_ow_head, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, w->skey.as<unsigned long long>(), ne, run_mask,
                            w->hs.as<uint32_t>());
         JG_HIP(hipGetLastError());
-        temp = 0;
-        JG_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, temp, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), (int)ne, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::InclusiveScan(cub_temp(w, temp), temp, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), (int)ne,
-                                                 ctx->stream));
+        const int n_ent = jg::cub_count(ne, "entries");
+        jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceScan::InclusiveScan(temp, bytes, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), n_ent, ctx->stream);
+        });
         JG_HIP(hipMemsetAsync(w->impure.p, 0, ne, ctx->stream));
         hipLaunchKernelGGL(k_ow_link, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes,
                            w->sval.as<uint32_t>(), w->seg.as<uint32_t>(), ne, w->impure.as<uint8_t>());
@@ -1825,10 +1789,10 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
         hipLaunchKernelGGL(k_ow_head, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, w->skey.as<unsigned long long>(), ne, ~0ull,
                            w->hs.as<uint32_t>());
         JG_HIP(hipGetLastError());
-        size_t temp = 0;
-        JG_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, temp, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), (int)ne, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::InclusiveScan(cub_temp(w, temp), temp, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), (int)ne,
-                                                 ctx->stream));
+        const int n_ent = jg::cub_count(ne, "entries");
+        jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceScan::InclusiveScan(temp, bytes, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), n_ent, ctx->stream);
+        });
         JG_HIP(hipMemsetAsync(w->impure.p, 0, ne, ctx->stream));
         hipLaunchKernelGGL(k_ow_link, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes, w->sval.as<uint32_t>(),
                            w->seg.as<uint32_t>(), ne, w->impure.as<uint8_t>());
@@ -1942,7 +1906,7 @@ bool commit_buckets(jg_orset* s, jg_orset_wire* w, const StrTab& ST, const RecTa
     if (!(claimed && w->spec)) JG_HIP(hipMemsetAsync(st, 0, 9 * 8, ctx->stream));
     static const bool trm = std::getenv("JANUS_TRACE_MERGE") != nullptr;
     if (trm) {
-        g_tmark[5] = tnow_us();
+        g_tmark[5] = jg::now_us();
         std::fprintf(stderr, "commit host: read -> check end %.0f us, -> commit %.0f, -> names %.0f, names %.0f, -> first launch %.0f\n", g_tmark[1] - g_tmark[0],
                      g_tmark[2] - g_tmark[1], g_tmark[3] - g_tmark[2], g_tmark[4] - g_tmark[3], g_tmark[5] - g_tmark[4]);
     }
@@ -2011,7 +1975,7 @@ void commit_tables(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
     jg_ctx* ctx = s->ctx;
     const uint64_t n = w->wn;
     static const bool tr = std::getenv("JANUS_TRACE_MERGE") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e6; };
+    const auto now = jg::now_us;
     double tc[5] = {tr ? now() : 0};
     g_tmark[2] = tc[0];
     uint64_t lim_off = w->wnb;
@@ -2069,7 +2033,7 @@ void commit_tables(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
 void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t ns, uint64_t nrec, uint32_t csi_lim, uint32_t t_lim,
                    uint64_t t_next, double* tc, bool tr) {
     jg_ctx* ctx = s->ctx;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e6; };
+    const auto now = jg::now_us;
     unsigned long long* st = status_words(w);
     const Sparse S = sparse_of(w);
     // room for every listed string (an upper bound of the new ones: the element tables then grow ahead of the
@@ -2232,7 +2196,7 @@ void commit_wave(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
     // tag records: keys, de-duplication, sort, union into the store
     ensure(w->rkey, nt * 8 + 8);
     ensure(w->rside, nt + 1);
-    const uint64_t tcap = pow2_at_least(2 * nt);
+    const uint64_t tcap = jg::pow2_at_least(2 * nt, 1024);
     ensure(w->dtab, tcap * 8);
     ensure(w->dmin, tcap * 4);
     for (int sd = 0; sd < 2; ++sd) {
@@ -2301,10 +2265,13 @@ void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* a
     jg_orset_wire* w = wire_of(s);
     if (!w->itab_cap || !w->tab_cap) ensure_names(ctx, w, 0, 0);  // a store that never saw a name: empty tables
     const bool lim = add_lim != nullptr;
-    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-    char* q0 = static_cast<char*>(jg::scratch(ctx, ctx->scratch, al(n * 4) + (lim ? al(2 * n * 8) : 0) + 256));
-    auto* d_sets = reinterpret_cast<uint32_t*>(q0);
-    auto* d_lim = lim ? reinterpret_cast<unsigned long long*>(q0 + al(n * 4)) : nullptr;
+    using ull = unsigned long long;
+    uint32_t* d_sets;
+    ull* d_lim;
+    jg::Layout Q;
+    Q.add(d_sets, n), Q.add(d_lim, lim ? 2 * n : 0);
+    Q.bind(jg::scratch(ctx, ctx->scratch, Q.bytes() + 256));
+    if (!lim) d_lim = nullptr;
     JG_HIP(hipMemcpyAsync(d_sets, set, n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (lim) {
         std::vector<unsigned long long> l(2 * n);
@@ -2317,41 +2284,16 @@ void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* a
     const EncRec E{G.key, G.tlo, G.thi, G.ord, G.qs};
     // the encoder's arrays, one block
     const uint64_t R1 = R + 1;
-    const uint64_t sz[] = {al(R * 4), 256, al(R * 4), al(R * 4), al(R * 4), al(R * 4), al(R * 4), 256, al(R * 8), al(R * 4), al(R * 8), al(R * 4),
-                           al(R * 4), al(R1 * 8), al(R1 * 8), al(R1 * 8), al(R1 * 8), al(4 * n * 8), al(4 * n * 4), al((n + 1) * 8), al((n + 1) * 8),
-                           al(R * 8), al(R * 4), al(R * 8), al(R * 4), al(R * 8), 256};
-    uint64_t tot = 0;
-    for (uint64_t x : sz) tot += x;
-    ensure(w->enc, tot);
-    char* p = w->enc.as<char>();
-    auto take = [&](int i) { char* r = p; p += sz[i]; return r; };
-    auto* kidx = reinterpret_cast<uint32_t*>(take(0));
-    auto* K = reinterpret_cast<unsigned long long*>(take(1));
-    auto* hf = reinterpret_cast<uint32_t*>(take(2));
-    auto* rid = reinterpret_cast<uint32_t*>(take(3));
-    auto* rstart = reinterpret_cast<uint32_t*>(take(4));
-    auto* rend = reinterpret_cast<uint32_t*>(take(5));
-    auto* rfirst = reinterpret_cast<uint32_t*>(take(6));
-    auto* nruns = reinterpret_cast<unsigned long long*>(take(7));
-    auto* rkey = reinterpret_cast<unsigned long long*>(take(8));
-    auto* rval = reinterpret_cast<uint32_t*>(take(9));
-    auto* skey = reinterpret_cast<unsigned long long*>(take(10));
-    auto* srun = reinterpret_cast<uint32_t*>(take(11));
-    auto* rrank = reinterpret_cast<uint32_t*>(take(12));
-    auto* cnt = reinterpret_cast<unsigned long long*>(take(13));
-    auto* tlen = reinterpret_cast<unsigned long long*>(take(14));
-    auto* rpos = reinterpret_cast<unsigned long long*>(take(15));
-    auto* cpos = reinterpret_cast<unsigned long long*>(take(16));
-    auto* qsec = reinterpret_cast<unsigned long long*>(take(17));
-    auto* sfirst = reinterpret_cast<uint32_t*>(take(18));
-    auto* qlen = reinterpret_cast<unsigned long long*>(take(19));
-    auto* qoff = reinterpret_cast<unsigned long long*>(take(20));
-    auto* reck = reinterpret_cast<unsigned long long*>(take(21));
-    auto* recv = reinterpret_cast<uint32_t*>(take(22));
-    auto* reck2 = reinterpret_cast<unsigned long long*>(take(23));
-    auto* srec = reinterpret_cast<uint32_t*>(take(24));
-    auto* rtags = reinterpret_cast<unsigned long long*>(take(25));
-    auto* err = reinterpret_cast<unsigned*>(take(26));
+    uint32_t *kidx, *hf, *rid, *rstart, *rend, *rfirst, *rval, *srun, *rrank, *sfirst, *recv, *srec;
+    ull *K, *nruns, *rkey, *skey, *cnt, *tlen, *rpos, *cpos, *qsec, *qlen, *qoff, *reck, *reck2, *rtags;
+    unsigned* err;
+    jg::Layout L;
+    L.add(kidx, R), L.add(K, 1), L.add(hf, R), L.add(rid, R), L.add(rstart, R), L.add(rend, R), L.add(rfirst, R), L.add(nruns, 1);
+    L.add(rkey, R), L.add(rval, R), L.add(skey, R), L.add(srun, R), L.add(rrank, R), L.add(cnt, R1), L.add(tlen, R1), L.add(rpos, R1), L.add(cpos, R1);
+    L.add(qsec, 4 * n), L.add(sfirst, 4 * n), L.add(qlen, n + 1), L.add(qoff, n + 1);
+    L.add(reck, R), L.add(recv, R), L.add(reck2, R), L.add(srec, R), L.add(rtags, R), L.add(err, 1);
+    ensure(w->enc, L.bytes());
+    L.bind(w->enc.p);
     JG_HIP(hipMemsetAsync(qsec, 0, 4 * n * 8, ctx->stream));
     JG_HIP(hipMemsetAsync(sfirst, 0xFF, 4 * n * 4, ctx->stream));
     JG_HIP(hipMemsetAsync(err, 0, 4, ctx->stream));
@@ -2360,36 +2302,35 @@ void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* a
     const Names N = names_of(w);
     const unsigned gR = blocks_for(R);
     if (R) {
-        size_t temp = 0;
+        const int n_R = jg::cub_count(R, "records"), n_R1 = jg::cub_count(R1, "records");
+        const auto tmp = jg::cub_in(w->cub);
         hipcub::CountingInputIterator<uint32_t> iota(0);
-        JG_HIP(hipcub::DeviceSelect::Flagged(nullptr, temp, iota, G.keep, kidx, K, (int)R, ctx->stream));
-        JG_HIP(hipcub::DeviceSelect::Flagged(cub_temp(w, temp), temp, iota, G.keep, kidx, K, (int)R, ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceSelect::Flagged(temp, bytes, iota, G.keep, kidx, K, n_R, ctx->stream); });
         hipLaunchKernelGGL(k_enc_heads, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, R, hf);
-        JG_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, temp, hf, rid, (int)R, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::InclusiveSum(cub_temp(w, temp), temp, hf, rid, (int)R, ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(temp, bytes, hf, rid, n_R, ctx->stream); });
         hipLaunchKernelGGL(k_enc_runs, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rstart, rend, rfirst, nruns);
         hipLaunchKernelGGL(k_enc_first_ord, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rfirst);
         hipLaunchKernelGGL(k_enc_run_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, rstart, rfirst, nruns, R, rkey, rval);
         JG_HIP(hipGetLastError());
-        JG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, rkey, skey, rval, srun, (int)R, 0, 64, ctx->stream));
-        JG_HIP(hipcub::DeviceRadixSort::SortPairs(cub_temp(w, temp), temp, rkey, skey, rval, srun, (int)R, 0, 64, ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, rkey, skey, rval, srun, n_R, 0, 64, ctx->stream);
+        });
         hipLaunchKernelGGL(k_enc_run_len, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, kidx, rstart, rend, skey, srun, nruns, R, rrank, cnt, tlen, qsec,
                            sfirst, err);
         hipLaunchKernelGGL(k_enc_rec_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rrank, R, reck, recv);
         JG_HIP(hipGetLastError());
-        JG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp, reck, reck2, recv, srec, (int)R, 0, 64, ctx->stream));
-        JG_HIP(hipcub::DeviceRadixSort::SortPairs(cub_temp(w, temp), temp, reck, reck2, recv, srec, (int)R, 0, 64, ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
+            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, reck, reck2, recv, srec, n_R, 0, 64, ctx->stream);
+        });
         JG_HIP(hipMemsetAsync(tlen + R, 0, 8, ctx->stream));
         JG_HIP(hipMemsetAsync(cnt + R, 0, 8, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, tlen, rpos, (int)R1, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(cub_temp(w, temp), temp, tlen, rpos, (int)R1, ctx->stream));
-        JG_HIP(hipcub::DeviceScan::ExclusiveSum(cub_temp(w, temp), temp, cnt, cpos, (int)R1, ctx->stream));
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, tlen, rpos, n_R1, ctx->stream); });
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, cpos, n_R1, ctx->stream); });
     }
     hipLaunchKernelGGL(k_enc_qlen, dim3(blocks_for(n + 1)), dim3(kBlock), 0, ctx->stream, qsec, n, qlen);
     JG_HIP(hipGetLastError());
-    size_t temp = 0;
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, qlen, qoff, (int)(n + 1), ctx->stream));
-    JG_HIP(hipcub::DeviceScan::ExclusiveSum(cub_temp(w, temp), temp, qlen, qoff, (int)(n + 1), ctx->stream));
+    const int n_q = jg::cub_count(n + 1, "sets");
+    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, qlen, qoff, n_q, ctx->stream); });
     JG_HIP(hipMemcpyAsync(off, qoff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     jg::pin_get(ctx, 0, err, 4);
     jg::pin_sync(ctx);  // the stream's copies above are done too
@@ -2489,9 +2430,9 @@ int orset_node_check(jg_orset* s, uint64_t n, uint64_t nbytes, uint64_t* bad, st
     // uploads are still in flight (a growing store reallocates here, not behind the last upload)
     const uint64_t* lc = s->wire->last_cnt;
     static const bool tr = std::getenv("JANUS_TRACE_MERGE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = jg::now_us();
     orset_reserve_union(s, 2 * lc[0] + 4096, 2 * lc[1] + 4096);
-    if (tr) std::fprintf(stderr, "orset_node_check: union targets reserved in %.0f us\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e6);
+    if (tr) std::fprintf(stderr, "orset_node_check: union targets reserved in %.0f us\n", jg::now_us() - t0);
     const int rc = wave_check_call(s, bad, true);
     if (rc != JG_OK) {
         char buf[1024];
@@ -2579,7 +2520,7 @@ int jg_orset_names_sync(jg_orset* s, uint64_t n_sets, const uint32_t* set, const
         auto* d_next = d_set + n_sets;
         auto* d_nset = d_next + n_sets;
         auto* d_nid = d_nset + n_names;
-        auto* d_off = reinterpret_cast<uint64_t*>(stage + (((n_sets * 8 + n_names * 8) + 15) & ~15ull));
+        auto* d_off = reinterpret_cast<uint64_t*>(stage + jg::round_up(n_sets * 8 + n_names * 8, 16));
         auto* d_clr = reinterpret_cast<uint8_t*>(d_off + n_names + 1);
         if (n_sets) {
             JG_HIP(hipMemcpyAsync(d_set, set, n_sets * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -2694,7 +2635,7 @@ int jg_orset_wave_names(jg_orset* s, uint64_t* n_names, uint64_t* n_bytes, uint3
             JG_HIP(hipEventSynchronize(o.ev));
             const uint8_t* h = o.host;
             const auto* hlen = reinterpret_cast<const uint32_t*>(h + n * 8);
-            const auto* hpo = reinterpret_cast<const unsigned long long*>(h + ((n * 12 + 15) & ~15ull));
+            const auto* hpo = reinterpret_cast<const unsigned long long*>(h + jg::round_up(n * 12, 16));
             const uint8_t* hpool = reinterpret_cast<const uint8_t*>(hpo + n);
             std::memcpy(set, h, n * 4);
             std::memcpy(id, h + n * 4, n * 4);
@@ -2759,7 +2700,7 @@ int jg_orset_names_since(jg_orset* s, uint64_t from, uint64_t* to, uint64_t* n_b
                 o.cap = need + need / 2;
             }
             uint8_t* h = o.host;
-            const size_t po = (n * 12 + 15) & ~15ull;
+            const size_t po = jg::round_up(n * 12, 16);
             JG_HIP(hipMemcpyAsync(h, w->nset.as<uint32_t>() + from, n * 4, hipMemcpyDeviceToHost, ctx->stream));
             JG_HIP(hipMemcpyAsync(h + n * 4, w->nid.as<uint32_t>() + from, n * 4, hipMemcpyDeviceToHost, ctx->stream));
             JG_HIP(hipMemcpyAsync(h + n * 8, w->nlen.as<uint32_t>() + from, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2780,7 +2721,7 @@ int jg_orset_names_since(jg_orset* s, uint64_t from, uint64_t* to, uint64_t* n_b
         if (!set) return;
         JG_REQUIRE(id && off && (bytes || o.since_bytes == 0), JG_EINVAL, "jg_orset_names_since: NULL buffer");
         const uint8_t* h = o.host;
-        const size_t po = (n * 12 + 15) & ~15ull;
+        const size_t po = jg::round_up(n * 12, 16);
         const auto* hlen = reinterpret_cast<const uint32_t*>(h + n * 8);
         const auto* hpo = reinterpret_cast<const unsigned long long*>(h + po);
         const uint8_t* hpool = reinterpret_cast<const uint8_t*>(hpo + n);

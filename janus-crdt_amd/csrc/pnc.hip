@@ -19,10 +19,9 @@
 //                    the Dictionary<Guid,int> grows into, PNCounters.cs:131-144).  Reads the old bytes once,
 //                    writes the new bytes once: (old + new) bytes at HBM rate.
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -382,13 +381,6 @@ __global__ __launch_bounds__(kBlock) void k_restride(T* __restrict__ dst, const 
     }
 }
 
-unsigned grid_for(jg_ctx* ctx, uint64_t work_items, unsigned per_cu = 8) {
-    uint64_t g = (work_items + kBlock - 1) / kBlock;
-    const uint64_t cap = (uint64_t)ctx->num_cus * per_cu;
-    if (g > cap) g = cap;
-    return g == 0 ? 1u : (unsigned)g;
-}
-
 void check_store(const jg_pnc* p, const char* fn) {
     JG_REQUIRE(p, JG_EINVAL, "%s: store is NULL", fn);
 }
@@ -415,12 +407,10 @@ void launch_merge_dense(jg_ctx* ctx, uint32_t eb, void* AP, void* AN, const void
     const uint64_t blocks = (nv + per - 1) / per;  // per array: the grid holds P's, then N's
     JG_REQUIRE(2 * blocks < 0xFFFFFFFFull, JG_EINVAL, "merge: %llu cells exceed one launch", (unsigned long long)n_cells);
     const unsigned half = blocks ? (unsigned)blocks : 1u;  // block 0 exists for the trailing cells
-    if (eb == 8)
-        hipLaunchKernelGGL(k_merge_dense<8>, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
+    jg::dispatch_eb(eb, [&](auto EB) {
+        hipLaunchKernelGGL(k_merge_dense<EB()>, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
                            (const uint4*)BN, nv, tail, half);
-    else
-        hipLaunchKernelGGL(k_merge_dense<4>, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
-                           (const uint4*)BN, nv, tail, half);
+    });
     JG_HIP(hipGetLastError());
 }
 
@@ -432,37 +422,34 @@ void launch_merge_indexed(jg_ctx* ctx, uint32_t eb, void* AP, void* AN, const vo
                           uint64_t n_rows, uint32_t R, const Groups* g = nullptr) {
     if (g && R >= 32 && ((uint64_t)R * eb) % 16 == 0) {
         JG_REQUIRE(n_rows < kNil, JG_EINVAL, "merge: %llu rows exceed one grouped launch", (unsigned long long)n_rows);
-        const unsigned gk = grid_for(ctx, n_rows, 16);
+        const unsigned gk = jg::grid_for(ctx, n_rows, kBlock, 16);
         hipLaunchKernelGGL(k_group_link, dim3(gk), dim3(kBlock), 0, ctx->stream, keys, n_rows, g->head, g->next, g->gen);
         constexpr int U = 4;  // rows in flight per wave (U = 8 measured slower, tools/tune_grouped.hip)
-        const unsigned grid = grid_for(ctx, (n_rows + U - 1) / U * 64, 16);
-        if (eb == 8)
-            hipLaunchKernelGGL((k_merge_grouped<8, U>), dim3(grid), dim3(kBlock), 0, ctx->stream, (long long*)AP, (long long*)AN,
-                               (const long long*)BP, (const long long*)BN, keys, g->head, g->next, n_rows, R, g->gen);
-        else
-            hipLaunchKernelGGL((k_merge_grouped<4, U>), dim3(grid), dim3(kBlock), 0, ctx->stream, (int*)AP, (int*)AN, (const int*)BP,
-                               (const int*)BN, keys, g->head, g->next, n_rows, R, g->gen);
+        const unsigned grid = jg::grid_for(ctx, (n_rows + U - 1) / U * 64, kBlock, 16);
+        jg::dispatch_eb(eb, [&](auto EB) {
+            using T = typename Elem<EB()>::T;
+            hipLaunchKernelGGL((k_merge_grouped<EB(), U>), dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)AP, (T*)AN, (const T*)BP, (const T*)BN,
+                               keys, g->head, g->next, n_rows, R, g->gen);
+        });
         JG_HIP(hipGetLastError());
         return;
     }
     if (R >= 32) {
-        const unsigned grid = grid_for(ctx, n_rows * 64, 16);
-        if (eb == 8)
-            hipLaunchKernelGGL(k_merge_indexed_rows<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (long long*)AP, (long long*)AN,
-                               (const long long*)BP, (const long long*)BN, keys, n_rows, R);
-        else
-            hipLaunchKernelGGL(k_merge_indexed_rows<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (int*)AP, (int*)AN, (const int*)BP,
-                               (const int*)BN, keys, n_rows, R);
+        const unsigned grid = jg::grid_for(ctx, n_rows * 64, kBlock, 16);
+        jg::dispatch_eb(eb, [&](auto EB) {
+            using T = typename Elem<EB()>::T;
+            hipLaunchKernelGGL(k_merge_indexed_rows<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)AP, (T*)AN, (const T*)BP, (const T*)BN,
+                               keys, n_rows, R);
+        });
         JG_HIP(hipGetLastError());
         return;
     }
-    const unsigned grid = grid_for(ctx, n_rows * R, 16);
-    if (eb == 8)
-        hipLaunchKernelGGL(k_merge_indexed<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (long long*)AP, (long long*)AN,
-                           (const long long*)BP, (const long long*)BN, keys, n_rows, R);
-    else
-        hipLaunchKernelGGL(k_merge_indexed<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (int*)AP, (int*)AN, (const int*)BP,
-                           (const int*)BN, keys, n_rows, R);
+    const unsigned grid = jg::grid_for(ctx, n_rows * R, kBlock, 16);
+    jg::dispatch_eb(eb, [&](auto EB) {
+        using T = typename Elem<EB()>::T;
+        hipLaunchKernelGGL(k_merge_indexed<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)AP, (T*)AN, (const T*)BP, (const T*)BN, keys,
+                           n_rows, R);
+    });
     JG_HIP(hipGetLastError());
 }
 
@@ -493,13 +480,11 @@ const Groups* groups_of(jg_pnc* p, uint64_t n_rows, Groups& g) {
 
 void launch_rows_copy(jg_ctx* ctx, uint32_t eb, void* dst, const void* src, const uint32_t* keys, uint64_t n_rows, uint32_t R,
                       int scatter) {
-    const unsigned grid = grid_for(ctx, n_rows * R, 16);
-    if (eb == 8)
-        hipLaunchKernelGGL(k_rows_copy<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (long long*)dst, (const long long*)src, keys,
-                           n_rows, R, scatter);
-    else
-        hipLaunchKernelGGL(k_rows_copy<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (int*)dst, (const int*)src, keys, n_rows, R,
-                           scatter);
+    const unsigned grid = jg::grid_for(ctx, n_rows * R, kBlock, 16);
+    jg::dispatch_eb(eb, [&](auto EB) {
+        using T = typename Elem<EB()>::T;
+        hipLaunchKernelGGL(k_rows_copy<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)dst, (const T*)src, keys, n_rows, R, scatter);
+    });
     JG_HIP(hipGetLastError());
 }
 
@@ -558,8 +543,7 @@ void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
     jg::ensure_device(ctx);
     const bool table = p->cols.p != nullptr;
     static const bool trace = std::getenv("JANUS_TRACE_RESERVE") != nullptr;  // the call's phases to stderr
-    const auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
+    const double t0 = jg::now_us();
     jg::DevBuf nP, nN, nC, nNc;  // all of them first: an allocation failure leaves the store untouched
     nP.alloc((size_t)nk * nr * eb);
     nN.alloc((size_t)nk * nr * eb);
@@ -577,11 +561,11 @@ void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
         if (table) launch_restride(ctx, 16, nC.p, p->cols.p, orr, nr, ok, nk);  // new slots all-zero (json_wave.hpp row_cache)
     }
     if (table) grow_rows(ctx, nNc.p, p->ncols.p, (size_t)ok * 4, nNc.bytes);
-    const double t1 = now();
+    const double t1 = jg::now_us();
     // the old buffers go: everything queued on them first (an async merge_batch on `stream`, the upload stream)
     JG_HIP(hipStreamSynchronize(ctx->stream));
     JG_HIP(hipStreamSynchronize(ctx->copy));
-    const double t2 = now();
+    const double t2 = jg::now_us();
     swap_buf(p->P, nP);
     swap_buf(p->N, nN);
     if (table) swap_buf(p->cols, nC), swap_buf(p->ncols, nNc);
@@ -591,7 +575,7 @@ void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
     if (trace) {
         nP.release(), nN.release(), nC.release(), nNc.release();  // the old buffers (freed here or on the way out)
         std::fprintf(stderr, "reserve %llu x %u -> %llu x %u: allocate + queue %.3f ms, copies %.3f ms, free %.3f ms\n", (unsigned long long)ok, orr,
-                     (unsigned long long)nk, nr, t1 - t0, t2 - t1, now() - t2);
+                     (unsigned long long)nk, nr, (t1 - t0) * 1e-3, (t2 - t1) * 1e-3, (jg::now_us() - t2) * 1e-3);
     }
 }
 
@@ -734,13 +718,12 @@ namespace jg {
 void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long* d_out, uint8_t* d_ovf, const uint32_t* d_at,
                        const unsigned long long* d_count, uint8_t of_code) {
     jg_ctx* ctx = p->ctx;
-    const unsigned grid = grid_for(ctx, n * 64, 16);
-    if (p->eb == 8)
-        hipLaunchKernelGGL(k_values<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const long long*)p->P.p, (const long long*)p->N.p, p->R,
-                           d_keys, n, d_out, d_ovf, d_at, d_count, of_code);
-    else
-        hipLaunchKernelGGL(k_values<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const int*)p->P.p, (const int*)p->N.p, p->R, d_keys, n,
-                           d_out, d_ovf, d_at, d_count, of_code);
+    const unsigned grid = jg::grid_for(ctx, n * 64, kBlock, 16);
+    dispatch_eb(p->eb, [&](auto EB) {
+        using T = typename Elem<EB()>::T;
+        hipLaunchKernelGGL(k_values<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const T*)p->P.p, (const T*)p->N.p, p->R, d_keys, n, d_out,
+                           d_ovf, d_at, d_count, of_code);
+    });
     JG_HIP(hipGetLastError());
 }
 }  // namespace jg
@@ -782,22 +765,22 @@ int jg_pnc_apply_ops(jg_pnc* p, uint64_t n_ops, const uint32_t* key, const uint3
                        (unsigned long long)i, key[i], col[i]);
         jg_ctx* ctx = p->ctx;
         jg::ensure_device(ctx);
-        char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch2, n_ops * 17 + 64));
-        uint32_t* dkey = (uint32_t*)st;
-        uint32_t* dcol = (uint32_t*)(st + n_ops * 4);
-        long long* ddel = (long long*)(st + ((n_ops * 8 + 15) & ~15ull));
-        uint8_t* dn = (uint8_t*)(ddel + n_ops);
+        uint32_t *dkey, *dcol;
+        long long* ddel;
+        uint8_t* dn;
+        jg::Layout L;
+        L.add(dkey, n_ops, 16), L.add(dcol, n_ops, 4), L.add(ddel, n_ops, 16), L.add(dn, n_ops, 1);
+        L.bind(jg::scratch(ctx, ctx->scratch2, L.bytes() + 64));
         JG_HIP(hipMemcpyAsync(dkey, key, n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(dcol, col, n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(ddel, delta, n_ops * 8, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync(dn, is_n, n_ops, hipMemcpyHostToDevice, ctx->stream));
-        const unsigned grid = grid_for(ctx, n_ops, 16);
-        if (p->eb == 8)
-            hipLaunchKernelGGL(k_apply_ops<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, (long long*)p->P.p, (long long*)p->N.p, dkey,
-                               dcol, ddel, dn, n_ops, p->R);
-        else
-            hipLaunchKernelGGL(k_apply_ops<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, (int*)p->P.p, (int*)p->N.p, dkey, dcol, ddel,
-                               dn, n_ops, p->R);
+        const unsigned grid = jg::grid_for(ctx, n_ops, kBlock, 16);
+        jg::dispatch_eb(p->eb, [&](auto EB) {
+            using T = typename Elem<EB()>::T;
+            hipLaunchKernelGGL(k_apply_ops<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)p->P.p, (T*)p->N.p, dkey, dcol, ddel, dn, n_ops,
+                               p->R);
+        });
         JG_HIP(hipGetLastError());
         JG_HIP(hipStreamSynchronize(ctx->stream));
     });

@@ -23,7 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "orset_names.hpp"
 #include "tpset_dict.hpp"
 #include "uid_table.hpp"
@@ -33,9 +33,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr uint32_t kNever = JG_NULL_ELEM - 1;  // "never allocated": the id no record carries (orset_names.hip)
 using ull = unsigned long long;
-
-unsigned blocks_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct QIn {  // the staged batch
     const ull *koff, *eoff;  // eoff / ebytes / flag NULL: no query carries an argument
@@ -162,26 +159,29 @@ int jg_node_query_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_
 
         // keys, elements, flags and offsets in one staging copy: koff | eoff | flag | key bytes | element bytes
         const uint64_t kb = key_off[n], eb = elems ? elem_off[n] : 0;
-        const size_t a_eoff = (n + 1) * 8, a_flag = a_eoff + (elems ? (n + 1) * 8 : 0), a_kb = (a_flag + (elems ? n : 0) + 7) & ~size_t(7),
-                     a_eb = a_kb + kb, stage = a_eb + eb;
+        QIn in{};
+        QOut o{};
+        jg::Layout L;
+        L.add(in.koff, n + 1, 8), L.add(in.eoff, elems ? n + 1 : 0, 8), L.add(in.flag, elems ? n : 0, 1);
+        L.add(in.kbytes, kb, 8), L.add(in.ebytes, eb, 1);
+        const size_t stage = L.skip(0, 8);
         std::vector<uint8_t> h(stage);
+        L.bind(h.data());  // the host image first: the same offsets as on the device
         std::memcpy(h.data(), key_off, (n + 1) * 8);
-        if (kb) std::memcpy(h.data() + a_kb, key_bytes, kb);
+        if (kb) std::memcpy(const_cast<uint8_t*>(in.kbytes), key_bytes, kb);
         if (elems) {
-            std::memcpy(h.data() + a_eoff, elem_off, (n + 1) * 8);
-            std::memcpy(h.data() + a_flag, elem_flag, n);
-            if (eb) std::memcpy(h.data() + a_eb, elem_bytes, eb);
+            std::memcpy(const_cast<ull*>(in.eoff), elem_off, (n + 1) * 8);
+            std::memcpy(const_cast<uint8_t*>(in.flag), elem_flag, n);
+            if (eb) std::memcpy(const_cast<uint8_t*>(in.ebytes), elem_bytes, eb);
         }
-        // behind it: value | oq | count | guid | prow | pat | oat | status | kind
-        const size_t a_value = up256(stage + 16), a_oq = a_value + n * 8, a_count = a_oq + n * 8, a_guid = a_count + 16,
-                     a_prow = a_guid + (guid ? n * 16 : 0), a_pat = a_prow + n * 4, a_oat = a_pat + n * 4, a_status = a_oat + n * 4, a_kind = a_status + n,
-                     a_end = a_kind + n;
-        auto* d = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch, a_end + 64));
-        const QIn in{reinterpret_cast<const ull*>(d), elems ? reinterpret_cast<const ull*>(d + a_eoff) : nullptr, d + a_kb,
-                     elems ? d + a_eb : nullptr, elems ? d + a_flag : nullptr};
-        const QOut o{reinterpret_cast<long long*>(d + a_value), d + a_status, d + a_kind, guid ? reinterpret_cast<jg_guid*>(d + a_guid) : nullptr,
-                     reinterpret_cast<uint32_t*>(d + a_prow), reinterpret_cast<uint32_t*>(d + a_pat), reinterpret_cast<ull*>(d + a_oq),
-                     reinterpret_cast<uint32_t*>(d + a_oat), reinterpret_cast<ull*>(d + a_count)};
+        // behind it (16 bytes on): value | oq | count | guid | prow | pat | oat | status | kind
+        L.skip(16);
+        L.add(o.value, n), L.add(o.oq, n, 8), L.add(o.count, 2, 8), L.add(o.guid, guid ? n : 0, 8);
+        L.add(o.prow, n, 4), L.add(o.pat, n, 4), L.add(o.oat, n, 4), L.add(o.status, n, 1), L.add(o.kind, n, 1);
+        auto* d = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch, L.bytes() + 64));
+        L.bind(d);
+        if (!elems) in.eoff = nullptr, in.ebytes = in.flag = nullptr;
+        if (!guid) o.guid = nullptr;
 
         // JANUS_TRACE_QUERY (as JANUS_TRACE_APPLY): the upload, the launches and the copies out by hipEvents
         static const bool tr = std::getenv("JANUS_TRACE_QUERY") != nullptr;
@@ -195,7 +195,7 @@ int jg_node_query_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_
         JG_HIP(hipMemcpyAsync(d, h.data(), stage, hipMemcpyHostToDevice, ctx->stream));
         stamp(1);
         JG_HIP(hipMemsetAsync(o.count, 0, 16, ctx->stream));
-        hipLaunchKernelGGL(k_q_resolve, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
+        hipLaunchKernelGGL(k_q_resolve, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
                            nd.pnc ? nd.pnc->n_keys : 0, R.N, nd.orset ? R.set_cap : 0, R.kmask, R.salt, in, n, o);
         JG_HIP(hipGetLastError());
         if (nd.pnc) jg::pnc_values_device(nd.pnc, o.prow, n, o.value, o.status, o.pat, o.count, JG_Q_OVERFLOW);

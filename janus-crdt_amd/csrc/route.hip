@@ -20,7 +20,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -245,18 +245,13 @@ void check_dev(jg_ctx* ctx, const void* p, uint64_t bytes, const char* fn, const
     }
 }
 
-unsigned grid_for(jg_ctx* ctx, uint64_t items) {
-    uint64_t g = (items + kRB - 1) / kRB, cap = (uint64_t)ctx->num_cus * 16;
-    return (unsigned)(g > cap ? cap : (g ? g : 1));
-}
-
 // Histogram + scan of one source: per-destination counts to the host, write positions in ctx scratch.
 template <class Own>
 const uint64_t* route_plan(jg_ctx* ctx, Own own, Tiles tl, uint32_t n_tiles, uint32_t world, uint64_t* counts) {
     const uint64_t m = (uint64_t)world * n_tiles;
     char* ws = static_cast<char*>(jg::scratch(ctx, ctx->scratch3, m * 4 + (m + world + 2) * 8 + 64));
     auto* hist = reinterpret_cast<uint32_t*>(ws);
-    auto* pos = reinterpret_cast<uint64_t*>(ws + ((m * 4 + 15) & ~15ull));
+    auto* pos = reinterpret_cast<uint64_t*>(ws + jg::round_up(m * 4, 16));
     auto* bounds = pos + m + 1;
     hipLaunchKernelGGL(k_route_hist<Own>, dim3(n_tiles), dim3(kRB), 0, ctx->stream, own, tl, n_tiles, hist);
     JG_HIP(hipGetLastError());
@@ -320,8 +315,7 @@ int jg_rows_route(const jg_rows* r, uint32_t world, uint64_t* counts, void* d_ke
         check_dev(ctx, d_keys, r->n_rows * 4, fn, "d_keys");
         check_dev(ctx, d_P, r->n_rows * row_bytes, fn, "d_P");
         check_dev(ctx, d_N, r->n_rows * row_bytes, fn, "d_N");
-        if (r->eb == 8) route_rows<8>(ctx, r, world, counts, d_keys, d_P, d_N);
-        else route_rows<4>(ctx, r, world, counts, d_keys, d_P, d_N);
+        jg::dispatch_eb(r->eb, [&](auto EB) { route_rows<EB()>(ctx, r, world, counts, d_keys, d_P, d_N); });
         JG_HIP(hipStreamSynchronize(ctx->stream));
     });
 }
@@ -340,7 +334,7 @@ int jg_pnc_merge_device(jg_pnc* p, uint64_t n_rows, const void* d_keys, const vo
         check_dev(ctx, d_P, n_rows * row_bytes, fn, "d_P");
         check_dev(ctx, d_N, n_rows * row_bytes, fn, "d_N");
         // every key must address the store before anything merges (all or nothing)
-        hipLaunchKernelGGL(k_check_keys, dim3(grid_for(ctx, n_rows)), dim3(kRB), 0, ctx->stream, (const uint32_t*)d_keys, n_rows, p->n_keys,
+        hipLaunchKernelGGL(k_check_keys, dim3(jg::grid_for(ctx, n_rows, kRB, 16)), dim3(kRB), 0, ctx->stream, (const uint32_t*)d_keys, n_rows, p->n_keys,
                            ctx->flags.as<unsigned>());
         JG_HIP(hipGetLastError());
         unsigned h = 0;

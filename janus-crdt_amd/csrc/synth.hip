@@ -1,7 +1,7 @@
 // synth.hip — device-side synthetic workloads (DESIGN.md §Synthetic inputs).  Counter-based, so
 // any cell / record can be recomputed on the host (the test oracle holds the same formulas in
 // oracle/capi.cpp) for size-independent parity checks at full BASELINE sizes.
-#include "jg_internal.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -47,16 +47,13 @@ __global__ __launch_bounds__(kB) void k_synth_orset(unsigned long long* __restri
     }
 }
 
-unsigned grid_for(jg_ctx* ctx, uint64_t n) {
-    uint64_t g = (n + kB - 1) / kB, cap = (uint64_t)ctx->num_cus * 16;
-    return (unsigned)(g > cap ? cap : (g ? g : 1));
-}
-
-template <class T>
-void fill_pnc(jg_ctx* ctx, void* P, void* N, uint64_t key0, uint64_t n_keys, uint32_t R, uint32_t w0, uint64_t seed) {
-    const unsigned g = grid_for(ctx, n_keys * R);
-    hipLaunchKernelGGL(k_synth_pnc<T>, dim3(g), dim3(kB), 0, ctx->stream, (T*)P, key0, n_keys, R, w0, (unsigned long long)seed);
-    hipLaunchKernelGGL(k_synth_pnc<T>, dim3(g), dim3(kB), 0, ctx->stream, (T*)N, key0, n_keys, R, w0 + 1, (unsigned long long)seed);
+void fill_pnc(jg_ctx* ctx, uint32_t eb, void* P, void* N, uint64_t key0, uint64_t n_keys, uint32_t R, uint32_t w0, uint64_t seed) {
+    const unsigned g = jg::grid_for(ctx, n_keys * R, kB, 16);
+    jg::dispatch_eb(eb, [&](auto EB) {
+        using T = std::conditional_t<EB() == 8, long long, int>;
+        hipLaunchKernelGGL(k_synth_pnc<T>, dim3(g), dim3(kB), 0, ctx->stream, (T*)P, key0, n_keys, R, w0, (unsigned long long)seed);
+        hipLaunchKernelGGL(k_synth_pnc<T>, dim3(g), dim3(kB), 0, ctx->stream, (T*)N, key0, n_keys, R, w0 + 1, (unsigned long long)seed);
+    });
     JG_HIP(hipGetLastError());
 }
 
@@ -70,8 +67,7 @@ int jg_synth_pnc_store(jg_pnc* p, uint64_t seed) {
         jg::require_writable(p, "jg_synth_pnc_store");
         JG_REQUIRE(p, JG_EINVAL, "jg_synth_pnc_store: store is NULL");
         jg::ensure_device(p->ctx);
-        if (p->eb == 8) fill_pnc<long long>(p->ctx, p->P.p, p->N.p, 0, p->n_keys, p->R, 0, seed);
-        else fill_pnc<int>(p->ctx, p->P.p, p->N.p, 0, p->n_keys, p->R, 0, seed);
+        fill_pnc(p->ctx, p->eb, p->P.p, p->N.p, 0, p->n_keys, p->R, 0, seed);
         JG_HIP(hipStreamSynchronize(p->ctx->stream));
     });
 }
@@ -81,8 +77,7 @@ int jg_synth_pnc_rows(jg_rows* r, uint64_t seed, uint64_t key0) {
         auto lk_ = jg::lock(r);  // calls on one context are serialised (shared scratch, stream)
         JG_REQUIRE(r, JG_EINVAL, "jg_synth_pnc_rows: rows is NULL");
         jg::ensure_device(r->ctx);
-        if (r->eb == 8) fill_pnc<long long>(r->ctx, r->P.p, r->N.p, key0, r->n_rows, r->R, 2, seed);
-        else fill_pnc<int>(r->ctx, r->P.p, r->N.p, key0, r->n_rows, r->R, 2, seed);  // key indices (if uploaded) are kept
+        fill_pnc(r->ctx, r->eb, r->P.p, r->N.p, key0, r->n_rows, r->R, 2, seed);  // key indices (if uploaded) are kept
         JG_HIP(hipStreamSynchronize(r->ctx->stream));
     });
 }
@@ -105,10 +100,10 @@ int jg_synth_orset(jg_orset* s, uint64_t seed, uint64_t n_groups, uint32_t elems
         s->add.next = na;
         s->rem.next = nr;
         if (na)
-            hipLaunchKernelGGL(k_synth_orset, dim3(grid_for(ctx, na)), dim3(kB), 0, ctx->stream, s->add.key.as<unsigned long long>(),
+            hipLaunchKernelGGL(k_synth_orset, dim3(jg::grid_for(ctx, na, kB, 16)), dim3(kB), 0, ctx->stream, s->add.key.as<unsigned long long>(),
                                s->add.tag.as<uint4>(), s->add.ord.as<uint32_t>(), na, elems_per_set, add_per_group, add_u0, (unsigned long long)seed);
         if (nr)
-            hipLaunchKernelGGL(k_synth_orset, dim3(grid_for(ctx, nr)), dim3(kB), 0, ctx->stream, s->rem.key.as<unsigned long long>(),
+            hipLaunchKernelGGL(k_synth_orset, dim3(jg::grid_for(ctx, nr, kB, 16)), dim3(kB), 0, ctx->stream, s->rem.key.as<unsigned long long>(),
                                s->rem.tag.as<uint4>(), s->rem.ord.as<uint32_t>(), nr, elems_per_set, rem_per_group, rem_u0, (unsigned long long)seed);
         JG_HIP(hipGetLastError());
         JG_HIP(hipStreamSynchronize(ctx->stream));

@@ -21,7 +21,7 @@
 #include <random>
 #include <vector>
 
-#include "jg_internal.hpp"
+#include "launch.hpp"
 #include "tpset_dict.hpp"
 #include "wire_cursor.hpp"
 
@@ -33,7 +33,7 @@ constexpr uint32_t kBlock = 256;
 constexpr uint32_t kTile = kBlock * 16;  // bytes of one scanner tile: 16 B per lane
 constexpr uint32_t kNullId = 0xFFFFFFFEu;  // the null element's id in add[] / rem[]
 
-unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
+using jg::blocks_for;
 
 // ---- JSON string sinks ---------------------------------------------------------------------------
 __constant__ char kMember[2][12] = {"addSet", "removeSet"};
@@ -909,18 +909,6 @@ __global__ __launch_bounds__(kBlock) void k_enc_write(Store S, uint64_t n_add, u
     }
 }
 
-// bump carving of one device block (p null: sizing run)
-struct Carve {
-    char* p;
-    size_t used = 0;
-    template <class T> T* take(size_t n) {
-        used = (used + 255) & ~(size_t)255;
-        T* r = p ? reinterpret_cast<T*>(p + used) : nullptr;
-        used += n * sizeof(T);
-        return r;
-    }
-};
-
 // well-formed UTF-8 (what a C# string encodes to): the encoder walks sequences by their lead byte
 bool valid_utf8(const uint8_t* s, uint64_t n) {
     for (uint64_t i = 0; i < n;) {
@@ -992,18 +980,17 @@ struct CandBufs {
     ull *oa, *orr, *os, *ob;
     uint8_t* result;
 };
-size_t cand_layout(Carve& cv, uint64_t C, CandBufs& B) {
+void cand_layout(jg::Layout& cv, uint64_t C, CandBufs& B) {
     uint64_t slots = 64;
     while (slots < 2 * C) slots <<= 1;
     Cands& K = B.K;
-    K.cstart = cv.take<ull>(C), K.clen = cv.take<uint32_t>(C), K.ckey = cv.take<ull>(C), K.cwhich = cv.take<uint8_t>(C);
-    K.cres = cv.take<uint32_t>(C), K.cslot = cv.take<uint32_t>(C);
-    K.prep = cv.take<uint32_t>(slots), K.pmin = cv.take<uint32_t>(2 * slots), K.newid = cv.take<uint32_t>(slots), K.nullmin = cv.take<uint32_t>(2);
+    cv.add<ull>(K.cstart, C), cv.add<uint32_t>(K.clen, C), cv.add<ull>(K.ckey, C), cv.add<uint8_t>(K.cwhich, C);
+    cv.add<uint32_t>(K.cres, C), cv.add<uint32_t>(K.cslot, C);
+    cv.add<uint32_t>(K.prep, slots), cv.add<uint32_t>(K.pmin, 2 * slots), cv.add<uint32_t>(K.newid, slots), cv.add<uint32_t>(K.nullmin, 2);
     K.pmask = slots - 1, K.n = C;
-    B.wa = cv.take<uint32_t>(C), B.wr = cv.take<uint32_t>(C), B.ws = cv.take<uint32_t>(C), B.wb = cv.take<uint32_t>(C);
-    B.oa = cv.take<ull>(C + 1), B.orr = cv.take<ull>(C + 1), B.os = cv.take<ull>(C + 1), B.ob = cv.take<ull>(C + 1);
-    B.result = cv.take<uint8_t>(C);
-    return cv.used;
+    cv.add<uint32_t>(B.wa, C), cv.add<uint32_t>(B.wr, C), cv.add<uint32_t>(B.ws, C), cv.add<uint32_t>(B.wb, C);
+    cv.add<ull>(B.oa, C + 1), cv.add<ull>(B.orr, C + 1), cv.add<ull>(B.os, C + 1), cv.add<ull>(B.ob, C + 1);
+    cv.add<uint8_t>(B.result, C);
 }
 
 uint64_t insert_candidates(jg_tpset* s, CandBufs& B, bool ops, const char* fn) {
@@ -1055,17 +1042,13 @@ void raw_candidates(jg_tpset* s, const char* fn, uint64_t n, const uint8_t* op, 
         JG_REQUIRE(valid_utf8(bytes + off[i], off[i + 1] - off[i]), JG_EINVAL, "%s: string %llu is not well-formed UTF-8", fn, (ull)i);
     }
     const uint64_t nb = off[n];
-    Carve size{nullptr};
     uint8_t* d_bytes = nullptr;
     ull* d_off = nullptr;
     uint8_t *d_op = nullptr, *d_null = nullptr;
-    auto layout = [&](Carve& cv) {
-        d_bytes = cv.take<uint8_t>(nb + 64), d_off = cv.take<ull>(n + 1), d_op = cv.take<uint8_t>(n), d_null = cv.take<uint8_t>(n);
-        cand_layout(cv, n, B);
-    };
-    layout(size);
-    Carve cv{static_cast<char*>(work(s, s->w3, size.used + 1024))};
-    layout(cv);
+    jg::Layout cv;
+    cv.add<uint8_t>(d_bytes, nb + 64), cv.add<ull>(d_off, n + 1), cv.add<uint8_t>(d_op, n), cv.add<uint8_t>(d_null, n);
+    cand_layout(cv, n, B);
+    cv.bind(work(s, s->w3, cv.bytes() + 1024));
     if (nb) JG_HIP(hipMemcpyAsync(d_bytes, bytes, nb, hipMemcpyHostToDevice, st));
     JG_HIP(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
     if (op) JG_HIP(hipMemcpyAsync(d_op, op, n, hipMemcpyHostToDevice, st));
@@ -1177,14 +1160,10 @@ int jg_tpset_lookup_all(jg_tpset* s, uint64_t from_ord, uint64_t* n, uint64_t* n
         ull *ok = nullptr, *ob = nullptr, *d_ord = nullptr, *d_off = nullptr;
         uint8_t *d_null = nullptr, *d_bytes = nullptr;
         const uint64_t maxb = s->n_bytes;
-        auto layout = [&](Carve& cv) {
-            keep = cv.take<uint32_t>(m), len = cv.take<uint32_t>(m), ok = cv.take<ull>(m + 1), ob = cv.take<ull>(m + 1);
-            d_ord = cv.take<ull>(m), d_off = cv.take<ull>(m + 1), d_null = cv.take<uint8_t>(m), d_bytes = cv.take<uint8_t>(maxb + 16);
-        };
-        Carve size{nullptr};
-        layout(size);
-        Carve cv{static_cast<char*>(work(s, s->w3, size.used + 1024))};
-        layout(cv);
+        jg::Layout cv;
+        cv.add<uint32_t>(keep, m), cv.add<uint32_t>(len, m), cv.add<ull>(ok, m + 1), cv.add<ull>(ob, m + 1);
+        cv.add<ull>(d_ord, m), cv.add<ull>(d_off, m + 1), cv.add<uint8_t>(d_null, m), cv.add<uint8_t>(d_bytes, maxb + 16);
+        cv.bind(work(s, s->w3, cv.bytes() + 1024));
         const Store S = s->view();
         hipLaunchKernelGGL(k_lookup_flag, dim3(blocks_for(m)), dim3(kBlock), 0, st, S, from, m, keep, len);
         excl_scan(s, keep, ok, m);
@@ -1242,17 +1221,13 @@ int jg_tpset_merge_json(jg_tpset* s, uint64_t n, const uint64_t* off, const uint
         uint32_t *d_cnt = nullptr, *d_tile_msg = nullptr, *d_tfn = nullptr, *d_tcnt = nullptr;
         uint16_t* d_emask = nullptr;
         MsgScan* d_ms = nullptr;
-        auto layout1 = [&](Carve& cv) {
-            d_bytes = cv.take<uint8_t>(nb + 64), d_tmp = cv.take<uint8_t>(nb + 64), d_off = cv.take<ull>(n + 1);
-            d_flat = cv.take<uint8_t>(n), d_status = cv.take<uint8_t>(n), d_cnt = cv.take<uint32_t>(2 * n), d_first = cv.take<ull>(2 * n);
-            d_cbase = cv.take<ull>(2 * n + 1), d_small = cv.take<ull>(8), d_ms = cv.take<MsgScan>(n);
-            d_tile_msg = cv.take<uint32_t>(T), d_tile_at = cv.take<ull>(T), d_tile0 = cv.take<ull>(n + 1), d_tfn = cv.take<uint32_t>(T);
-            d_tstate = cv.take<uint8_t>(T), d_tcnt = cv.take<uint32_t>(T), d_tbase = cv.take<ull>(T + 1), d_emask = cv.take<uint16_t>(T * kBlock);
-        };
-        Carve size1{nullptr};
-        layout1(size1);
-        Carve cv1{static_cast<char*>(work(s, s->w1, size1.used + 1024))};
-        layout1(cv1);
+        jg::Layout cv;
+        cv.add<uint8_t>(d_bytes, nb + 64), cv.add<uint8_t>(d_tmp, nb + 64), cv.add<ull>(d_off, n + 1);
+        cv.add<uint8_t>(d_flat, n), cv.add<uint8_t>(d_status, n), cv.add<uint32_t>(d_cnt, 2 * n), cv.add<ull>(d_first, 2 * n);
+        cv.add<ull>(d_cbase, 2 * n + 1), cv.add<ull>(d_small, 8), cv.add<MsgScan>(d_ms, n);
+        cv.add<uint32_t>(d_tile_msg, T), cv.add<ull>(d_tile_at, T), cv.add<ull>(d_tile0, n + 1), cv.add<uint32_t>(d_tfn, T);
+        cv.add<uint8_t>(d_tstate, T), cv.add<uint32_t>(d_tcnt, T), cv.add<ull>(d_tbase, T + 1), cv.add<uint16_t>(d_emask, T * kBlock);
+        cv.bind(work(s, s->w1, cv.bytes() + 1024));
         ull* d_bad = d_small;       // [0] first bad message
         ull* d_stat = d_small + 1;  // [0..1] messages / bytes the scanner took
         ull* d_lim = d_small + 3;   // [0..2] k_limit
@@ -1279,10 +1254,9 @@ int jg_tpset_merge_json(jg_tpset* s, uint64_t n, const uint64_t* off, const uint
             excl_scan(s, d_tcnt, d_tbase, T);
             JG_HIP(hipGetLastError());
             E = pin_read(ctx, d_tbase + T);
-            Carve size2{nullptr};
-            size2.take<ull>(E + 1), size2.take<uint32_t>(E + 1);
-            Carve cv2{static_cast<char*>(work(s, s->w2, size2.used + 1024))};
-            d_epos = cv2.take<ull>(E + 1), d_emsg = cv2.take<uint32_t>(E + 1);
+            jg::Layout cv2;
+            cv2.add<ull>(d_epos, E + 1), cv2.add<uint32_t>(d_emsg, E + 1);
+            cv2.bind(work(s, s->w2, cv2.bytes() + 1024));
             hipLaunchKernelGGL(k_emit, dim3((unsigned)T), dim3(kBlock), 0, st, d_tile_msg, d_tile_at, d_emask, d_tbase, d_epos, d_emsg);
             if (E) hipLaunchKernelGGL(k_strings, dim3(blocks_for(E)), dim3(kBlock), 0, st, d_bytes, d_off, d_epos, d_emsg, E, d_ms);
             hipLaunchKernelGGL(k_walk, dim3(gm), dim3(kBlock), 0, st, d_bytes, d_off, n, d_ms, d_tbase, d_tile0, d_epos, d_flat, d_cnt, d_first, d_stat);
@@ -1304,14 +1278,10 @@ int jg_tpset_merge_json(jg_tpset* s, uint64_t n, const uint64_t* off, const uint
         if (C) {
             CandBufs B{};
             ull* d_cpos = nullptr;
-            auto layout3 = [&](Carve& cv) {
-                d_cpos = cv.take<ull>(C);
-                cand_layout(cv, C, B);
-            };
-            Carve size3{nullptr};
-            layout3(size3);
-            Carve cv3{static_cast<char*>(work(s, s->w3, size3.used + 1024))};
-            layout3(cv3);
+            jg::Layout cv3;
+            cv3.add<ull>(d_cpos, C);
+            cand_layout(cv3, C, B);
+            cv3.bind(work(s, s->w3, cv3.bytes() + 1024));
             B.K.tmp = d_tmp;
             if (E) hipLaunchKernelGGL(k_place, dim3(blocks_for(E)), dim3(kBlock), 0, st, d_epos, d_emsg, E, d_flat, d_cnt, d_first, d_cbase, C, d_cpos, B.K.cwhich);
             hipLaunchKernelGGL(k_serial_emit, dim3(gm), dim3(kBlock), 0, st, d_bytes, d_off, n, d_flat, d_status, d_cnt, d_first, d_cbase, C, d_cpos,
@@ -1354,10 +1324,9 @@ int jg_tpset_encode_json(jg_tpset* s, uint64_t* n_bytes, uint8_t* out, uint64_t 
         }
         uint32_t* len = nullptr;
         ull* eo = nullptr;
-        Carve size{nullptr};
-        size.take<uint32_t>(ne + 1), size.take<ull>(ne + 2);
-        Carve cv{static_cast<char*>(work(s, s->w3, size.used + 1024))};
-        len = cv.take<uint32_t>(ne + 1), eo = cv.take<ull>(ne + 2);
+        jg::Layout cv;
+        cv.add<uint32_t>(len, ne + 1), cv.add<ull>(eo, ne + 2);
+        cv.bind(work(s, s->w3, cv.bytes() + 1024));
         const Store S = s->view();
         JG_HIP(hipEventRecord(s->ev0, st));
         hipLaunchKernelGGL(k_enc_len, dim3(blocks_for(ne)), dim3(kBlock), 0, st, S, s->n_add, s->n_rem, len);
@@ -1546,14 +1515,14 @@ struct ItemBufs {
     uint32_t *added, *jrn;
     ull *oa, *oj;
 };
-void items_layout(Carve& cv, uint64_t n, ItemBufs& B) {
+void items_layout(jg::Layout& cv, uint64_t n, ItemBufs& B) {
     uint64_t slots = 64;
     while (slots < 2 * n) slots <<= 1;
     Items& I = B.I;
-    I.sid = cv.take<uint32_t>(n), I.klen = cv.take<uint32_t>(n), I.rlen = cv.take<uint32_t>(n), I.slot = cv.take<uint32_t>(n), I.prep = cv.take<uint32_t>(slots), I.pmin = cv.take<uint32_t>(slots);
-    I.glo = cv.take<ull>(n), I.ghi = cv.take<ull>(n), I.key = cv.take<ull>(n), I.status = cv.take<uint8_t>(n), I.valid = cv.take<uint8_t>(n);
+    cv.add<uint32_t>(I.sid, n), cv.add<uint32_t>(I.klen, n), cv.add<uint32_t>(I.rlen, n), cv.add<uint32_t>(I.slot, n), cv.add<uint32_t>(I.prep, slots), cv.add<uint32_t>(I.pmin, slots);
+    cv.add<ull>(I.glo, n), cv.add<ull>(I.ghi, n), cv.add<ull>(I.key, n), cv.add<uint8_t>(I.status, n), cv.add<uint8_t>(I.valid, n);
     I.pmask = slots - 1, I.n = n;
-    B.added = cv.take<uint32_t>(n), B.jrn = cv.take<uint32_t>(n), B.oa = cv.take<ull>(n + 1), B.oj = cv.take<ull>(n + 1);
+    cv.add<uint32_t>(B.added, n), cv.add<uint32_t>(B.jrn, n), cv.add<ull>(B.oa, n + 1), cv.add<ull>(B.oj, n + 1);
 }
 // the items are filled: resolve them against the dictionary in order, append the journal (journal = false: none).
 // Returns the journal records appended; added_out (host, optional) = each item's TryAdd bool.
@@ -1595,10 +1564,9 @@ uint64_t on_next(jg_keyspace* ks) {
     const uint64_t n = s->n_add - ks->seen;
     if (n == 0) return 0;
     ItemBufs B{};
-    Carve size{nullptr};
-    items_layout(size, n, B);
-    Carve cv{static_cast<char*>(work(s, ks->wk, size.used + 1024))};
+    jg::Layout cv;
     items_layout(cv, n, B);
+    cv.bind(work(s, ks->wk, cv.bytes() + 1024));
     hipLaunchKernelGGL(k_ks_parse, dim3(blocks_for(n)), dim3(kBlock), 0, ks->ctx->stream, s->view(), ks->seen, B.I);
     const uint64_t tj = dict_insert(ks, B, true, nullptr);
     ks->seen = s->n_add;
@@ -1692,14 +1660,10 @@ int jg_keyspace_create_keys(jg_keyspace* ks, uint64_t n, const uint64_t* off, co
         ull* d_eoff = nullptr;
         uint32_t* d_klen = nullptr;
         jg_guid* d_guid = nullptr;
-        auto layout = [&](Carve& cv) {
-            d_ent = cv.take<uint8_t>(ent.size() + 16), d_eoff = cv.take<ull>(n + 1), d_klen = cv.take<uint32_t>(n), d_guid = cv.take<jg_guid>(n);
-            items_layout(cv, n, B);
-        };
-        Carve size{nullptr};
-        layout(size);
-        Carve cv{static_cast<char*>(work(s, ks->wk, size.used + 1024))};
-        layout(cv);
+        jg::Layout cv;
+        cv.add<uint8_t>(d_ent, ent.size() + 16), cv.add<ull>(d_eoff, n + 1), cv.add<uint32_t>(d_klen, n), cv.add<jg_guid>(d_guid, n);
+        items_layout(cv, n, B);
+        cv.bind(work(s, ks->wk, cv.bytes() + 1024));
         JG_HIP(hipMemcpyAsync(d_ent, ent.data(), ent.size(), hipMemcpyHostToDevice, st));
         JG_HIP(hipMemcpyAsync(d_eoff, eoff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
         JG_HIP(hipMemcpyAsync(d_klen, klen.data(), n * 4, hipMemcpyHostToDevice, st));
@@ -1762,14 +1726,10 @@ int jg_keyspace_new_keys(jg_keyspace* ks, uint64_t from, uint64_t* to, uint64_t*
         ull *ob = nullptr, *d_off = nullptr;
         uint8_t *d_bytes = nullptr, *d_status = nullptr;
         jg_guid* d_guid = nullptr;
-        auto layout = [&](Carve& cv) {
-            ob = cv.take<ull>(n + 1), d_off = cv.take<ull>(n + 1), d_guid = cv.take<jg_guid>(n), d_status = cv.take<uint8_t>(n);
-            d_bytes = cv.take<uint8_t>(s->n_bytes + 16);
-        };
-        Carve size{nullptr};
-        layout(size);
-        Carve cv{static_cast<char*>(work(s, ks->wk, size.used + 1024))};
-        layout(cv);
+        jg::Layout cv;
+        cv.add<ull>(ob, n + 1), cv.add<ull>(d_off, n + 1), cv.add<jg_guid>(d_guid, n), cv.add<uint8_t>(d_status, n);
+        cv.add<uint8_t>(d_bytes, s->n_bytes + 16);
+        cv.bind(work(s, ks->wk, cv.bytes() + 1024));
         excl_scan(s, ks->jlen.as<uint32_t>() + from, ob, n);
         if (!query)
             hipLaunchKernelGGL(k_ks_journal, dim3(blocks_for(n)), dim3(kBlock), 0, st, s->view(), from, n, ks->jsid.as<uint32_t>(), ks->jlen.as<uint32_t>(),
@@ -1799,13 +1759,9 @@ int jg_keyspace_lookup(jg_keyspace* ks, uint64_t n, const uint64_t* off, const u
         uint8_t *d_keys = nullptr, *d_found = nullptr;
         ull* d_off = nullptr;
         jg_guid* d_guid = nullptr;
-        auto layout = [&](Carve& cv) {
-            d_keys = cv.take<uint8_t>(off[n] + 16), d_off = cv.take<ull>(n + 1), d_guid = cv.take<jg_guid>(n), d_found = cv.take<uint8_t>(n);
-        };
-        Carve size{nullptr};
-        layout(size);
-        Carve cv{static_cast<char*>(work(s, ks->wk, size.used + 1024))};
-        layout(cv);
+        jg::Layout cv;
+        cv.add<uint8_t>(d_keys, off[n] + 16), cv.add<ull>(d_off, n + 1), cv.add<jg_guid>(d_guid, n), cv.add<uint8_t>(d_found, n);
+        cv.bind(work(s, ks->wk, cv.bytes() + 1024));
         if (off[n]) JG_HIP(hipMemcpyAsync(d_keys, key_bytes, off[n], hipMemcpyHostToDevice, st));
         JG_HIP(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_ks_lookup, dim3(blocks_for(n)), dim3(kBlock), 0, st, s->view(), ks->dict(), d_keys, d_off, n, d_guid, d_found);

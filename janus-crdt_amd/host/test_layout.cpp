@@ -1,0 +1,161 @@
+// test_layout.cpp — csrc/layout.hpp on the CPU (no device code): the layout builder, pow2_at_least and the checked
+// narrowings blocks_for / cub_count.  Prints one "ok <check>" line per check and "PASS" at the end; exits 1 at the
+// first failure.  tests/test_layout.py runs it.
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "layout.hpp"
+
+namespace jg {
+struct Error {
+    int code;
+    std::string msg;
+};
+// the library's fail() (ctx.hip) throws its Error; so does this one
+void fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    throw Error{code, buf};
+}
+}  // namespace jg
+
+namespace {
+
+int g_checks = 0;
+#define CHECK(cond)                                                               \
+    do {                                                                          \
+        if (!(cond)) {                                                            \
+            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
+            std::exit(1);                                                         \
+        }                                                                         \
+        ++g_checks;                                                               \
+    } while (0)
+
+template <class F> int code_of(F&& f) {
+    try {
+        f();
+    } catch (const jg::Error& e) {
+        return e.code;
+    }
+    return JG_OK;
+}
+
+struct Placed {
+    size_t off, bytes, align;
+};
+
+// every combination of the counts and alignments, each as a 1-, 4- and 16-byte element, in one block
+void test_layout() {
+    struct E16 { uint64_t a, b; };
+    const uint64_t counts[] = {0, 1, (1ull << 31) + 5};
+    const size_t aligns[] = {8, 16, 256};
+    jg::Layout L;
+    std::vector<Placed> placed;
+    uint8_t* p1[9];
+    uint32_t* p4[9];
+    E16* p16[9];
+    int k = 0;
+    CHECK(L.bytes() == 0);
+    for (uint64_t c : counts)
+        for (size_t a : aligns) {
+            placed.push_back({L.add(p1[k], c, a), (size_t)c, a});
+            placed.push_back({L.add(p4[k], c, a), (size_t)c * 4, a});
+            placed.push_back({L.add(p16[k], c, a), (size_t)c * 16, a});
+            ++k;
+        }
+    const size_t total = L.bytes();
+    size_t prev_end = 0;
+    for (const Placed& p : placed) {
+        CHECK(p.off % p.align == 0);        // aligned as asked
+        CHECK(p.off >= prev_end);           // in order, no overlap with the array before
+        CHECK(p.off - prev_end < p.align);  // nothing but padding between them: a zero-count array takes no bytes
+        CHECK(p.off + p.bytes <= total);    // the total covers it (a zero-count array's pointer is inside the block)
+        prev_end = p.off + p.bytes;
+    }
+    CHECK(total >= prev_end && total - prev_end < 256 && total % 256 == 0);
+
+    // bound to a base: typed pointers at the offsets; a zero-count array yields a usable (in-block, aligned) pointer;
+    // bytes no array names are skipped; binding again moves every pointer
+    uint32_t* a;
+    uint64_t* z;
+    uint8_t* b;
+    jg::Layout M;
+    CHECK(M.add(a, 3, 8) == 0 && M.skip(5) == 12 && M.add(z, 0, 256) == 256 && M.add(b, 1, 16) == 256);
+    alignas(256) static unsigned char block[2][1024];
+    CHECK(M.bytes() == 512);
+    M.bind(block[0]);
+    CHECK((void*)a == (void*)block[0] && (unsigned char*)z == block[0] + 256 && b == block[0] + 256);
+    a[2] = 7, b[0] = 9;
+    CHECK(block[0][8] == 7 && block[0][256] == 9);
+    M.bind(block[1]);
+    CHECK((void*)a == (void*)block[1] && b == block[1] + 256);
+
+    // the default alignment is 256; a size that overflows size_t fails, and so does a 33rd array
+    uint8_t* d;
+    uint64_t* big;
+    jg::Layout D;
+    D.add(d, 1);
+    CHECK(D.add(d, 1) == 256);
+    CHECK(code_of([&] { D.add(big, ~0ull / 4); }) == JG_EINVAL);
+    CHECK(code_of([&] { for (int i = 0; i < 40; ++i) D.add(d, 1); }) == JG_EINVAL);
+    std::printf("ok layout\n");
+}
+
+void test_round_pow2() {
+    CHECK(jg::round_up(0, 256) == 0 && jg::round_up(1, 256) == 256 && jg::round_up(256, 256) == 256 && jg::round_up(257, 8) == 264);
+    for (uint64_t floor : {64ull, 1024ull, 4096ull}) {
+        CHECK(jg::pow2_at_least(0, floor) == floor);
+        CHECK(jg::pow2_at_least(floor, floor) == floor);             // at its floor
+        CHECK(jg::pow2_at_least(floor + 1, floor) == 2 * floor);
+        CHECK(jg::pow2_at_least(1ull << 20, floor) == 1ull << 20);   // at a power of two
+        CHECK(jg::pow2_at_least((1ull << 20) + 1, floor) == 1ull << 21);  // and one past it
+    }
+    std::printf("ok pow2_at_least\n");
+}
+
+void test_blocks_for() {
+    for (unsigned block : {64u, 256u, 512u}) {
+        CHECK(jg::blocks_for(0, block) == 1);  // clamped: one workgroup whose threads all fail their bounds check
+        CHECK(jg::blocks_for(1, block) == 1);
+        CHECK(jg::blocks_for(block, block) == 1);
+        CHECK(jg::blocks_for(block + 1, block) == 2);
+    }
+    CHECK(jg::blocks_for(257) == 2);  // the default block is 256
+    const uint64_t most = (uint64_t)INT32_MAX * 256;
+    CHECK(jg::blocks_for(most) == (unsigned)INT32_MAX);
+    CHECK(code_of([&] { jg::blocks_for(most + 1); }) == JG_EINVAL);        // 2^31 workgroups: fails
+    CHECK(code_of([&] { jg::blocks_for((1ull << 40) * 256); }) == JG_EINVAL);  // would wrap to 0 in 32 bits
+    CHECK(code_of([&] { jg::blocks_for(~0ull); }) == JG_EINVAL);           // n + block - 1 would wrap in 64 bits
+    std::printf("ok blocks_for\n");
+}
+
+void test_cub_count() {
+    CHECK(jg::cub_count(0) == 0);
+    CHECK(jg::cub_count((uint64_t)INT32_MAX) == INT32_MAX);
+    CHECK(code_of([&] { jg::cub_count((uint64_t)INT32_MAX + 1); }) == JG_EINVAL);
+    std::string msg;
+    try {
+        jg::cub_count(1ull << 32, "ops");
+    } catch (const jg::Error& e) {
+        msg = e.msg;
+    }
+    CHECK(msg.find("4294967296 ops") != std::string::npos);  // the message names the count
+    std::printf("ok cub_count\n");
+}
+
+}  // namespace
+
+int main() {
+    test_layout();
+    test_round_pow2();
+    test_blocks_for();
+    test_cub_count();
+    std::printf("PASS %d checks\n", g_checks);
+    return 0;
+}

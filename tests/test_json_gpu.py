@@ -776,3 +776,35 @@ def test_apply_ops_rewind_matches_walk(ctx, eb, n_keys, n_ops):
         got = [int(x) & mask for x in M[:, 0]]
         assert got == [int(t) & mask for t in tot[which]]
     pr.close()
+
+
+def _small_store(ctx):
+    """4 keys x 2 replicas with both columns interned and non-zero counters."""
+    rng = np.random.default_rng(4242)
+    gs = random_guids(rng, 5)
+    pr = Pair(ctx, 4, 2, 8, gs[:4])
+    keys = np.arange(4, dtype=np.uint32)
+    msgs = [encode_pnc([gs[k], gs[4]], [k + 1, 10 + k], [2 * k, 3]) for k in range(4)]
+    assert pr.oracle(keys, msgs)[0] is None
+    pr.s.merge_json(keys, msgs)
+    pr.check()
+    return pr
+
+
+def test_merge_json_empty_wave(ctx):
+    """jg_pnc_merge_json with n == 0 (no messages, off = [0]): JG_OK, no open wave left behind, the store unchanged."""
+    pr = _small_store(ctx)
+    pr.s.merge_json(np.zeros(0, np.uint32), [])
+    pr.check()
+    pr.s.merge_json(np.zeros(0, np.uint32), [])  # and again: the first left no wave open
+    pr.check()
+    pr.close()
+
+
+def test_encode_json_empty_batch(ctx):
+    """jg_pnc_encode_json with n == 0, as a size query and with an output buffer: JG_OK, off[0] = 0, no state
+    returned, the store unchanged."""
+    pr = _small_store(ctx)
+    assert pr.s.encode_json(np.zeros(0, np.uint32)) == []
+    pr.check()
+    pr.close()
