@@ -148,6 +148,21 @@ int jg_rows_create(jg_ctx* ctx, uint64_t n_rows, uint32_t n_replicas, uint32_t e
 int jg_rows_destroy(jg_rows* rows);
 int jg_rows_upload(jg_rows* rows, const uint32_t* key_idx, const void* P, const void* N);
 int jg_pnc_merge_batch(jg_pnc* pnc, const jg_rows* rows, int async);
+/* The dense merge filter of an int64 store (additive entry points, JG_ABI_VERSION stays 10).  A dense identity
+ * merge (jg_pnc_merge_batch of a batch without key indices, jg_pnc_merge_rows with key_idx NULL) needs the
+ * store's own cells only to learn whether the received one is larger, and counters overwhelmingly fit 32 bits, so
+ * a run of such merges reads a library-private int32 copy of P and N (clamped to the int32 range; a cell at a
+ * clamp value is read from the store itself) instead of the 8-byte cells.  The second consecutive dense identity
+ * merge with no other write to the store in between allocates and builds the copy (4 more bytes of device memory
+ * per cell of P and of N; one more pass of writes in that call), the ones after it read it; any other write to
+ * the store (rows, ops, keyed merges, wire-format applies, jg_pnc_reserve, node waves, exchanges) drops it at no
+ * cost and the next dense merges start over.  Results are bit-identical with the filter on or off; an int32 store
+ * never uses it; if the copy does not fit on the device the store keeps merging without it and returns no error.
+ * on != 0 (the default) allows the filter, 0 frees the copy and pins the store to the unfiltered merge (the call
+ * waits for the context's queued work first). */
+int jg_pnc_set_dense_filter(jg_pnc* pnc, int on);
+/* *state = 0: off or cold (no valid copy), 1: armed (the next dense identity merge builds it), 2: valid. */
+int jg_pnc_dense_filter_state(jg_pnc* pnc, int* state);
 
 /* ---------------------------------------------------------------------------------------------
  * PN-Counter replica table + wire-format apply (csrc/json.hip).  The store keeps, per key, the

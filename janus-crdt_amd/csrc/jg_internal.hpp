@@ -135,7 +135,23 @@ struct jg_pnc {
     uint32_t R;
     uint32_t eb;  // elem bytes (4 | 8)
     uint32_t max_R = 0;  // jg_pnc_set_max_replicas: a row-capacity failure widens R up to this (0: fixed shape)
-    jg::DevBuf P, N;
+    // The counters, [n_keys x R] of eb bytes each.  Reached through the accessors only: ro_P / ro_N for launches and
+    // copies that read, rw_P / rw_N for everything that may write, which drops the dense merge's shadow (below).
+    // The filtered dense merge itself (pnc.hip), which keeps the shadow exact, is the one user of the raw fields.
+    jg::DevBuf P_, N_;
+    const void* ro_P() const { return P_.p; }
+    const void* ro_N() const { return N_.p; }
+    void* rw_P() { filt = kFiltCold; return P_.p; }
+    void* rw_N() { filt = kFiltCold; return N_.p; }
+    // Dense merge filter (eb == 8 only): sP / sN = clamp32 of every cell of P / N, int32 [n_keys x R],
+    // a cache the dense identity merge reads instead of P / N.  cold: no valid shadow (the buffers may be kept);
+    // armed: the last write to the store was a dense identity merge; valid: the shadow is exact.  Host state under
+    // the context lock; launches are stream-ordered, so a flag cleared here holds for every later launch.
+    enum : uint8_t { kFiltCold = 0, kFiltArmed = 1, kFiltValid = 2 };
+    jg::DevBuf sP, sN;
+    uint8_t filt = kFiltCold;
+    bool filt_on = true;      // jg_pnc_set_dense_filter
+    bool filt_nomem = false;  // the shadow did not fit on the device at this shape: not asked for again until it changes
     // replica table (json.hip): [n_keys x R] 16-byte Guids + [n_keys] column counts, first use only
     jg::DevBuf cols, ncols;
     // grouped indexed merge (k_group_*): per-key list head of the batch being merged (gen << 32 | row,

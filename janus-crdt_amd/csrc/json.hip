@@ -900,7 +900,7 @@ void launch_scan(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
     const int G = json_group();
     const bool fuse = p->fuse;
     jg::dispatch_eb(p->eb, [&](auto EB) {
-        launch_scan_g<EB()>(G, p->ctx->stream, bytes, off, rows, m0, m1, t, w.status, w.deferred, w.emit, w.eguid, w.slow, p->P.p, p->N.p, fuse);
+        launch_scan_g<EB()>(G, p->ctx->stream, bytes, off, rows, m0, m1, t, w.status, w.deferred, w.emit, w.eguid, w.slow, p->rw_P(), p->rw_N(), fuse);
     });
     JG_HIP(hipGetLastError());
     p->scan_hi = std::max(p->scan_hi, m1);
@@ -914,7 +914,7 @@ void undo_applied(jg_pnc* p, const uint32_t* rows) {
     const Table t = table_of(p);
     const unsigned g = blocks_for(n * kEmitLanes);
     jg::dispatch_eb(p->eb, [&](auto EB) {
-        hipLaunchKernelGGL(k_undo_applied<EB()>, dim3(g), dim3(kBlock), 0, p->ctx->stream, p->wemit.as<uint8_t>(), rows, n, t.R, p->P.p, p->N.p);
+        hipLaunchKernelGGL(k_undo_applied<EB()>, dim3(g), dim3(kBlock), 0, p->ctx->stream, p->wemit.as<uint8_t>(), rows, n, t.R, p->rw_P(), p->rw_N());
     });
     JG_HIP(hipGetLastError());
 }
@@ -949,8 +949,8 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
         // whose pass B runs unguarded): only the slow list's launch is left.
         const bool fused = p->fuse;
         jg::dispatch_eb(p->eb, [&](auto EB) {
-            if (!fused) hipLaunchKernelGGL(k_apply_emit<EB()>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, w.status);
-            hipLaunchKernelGGL(k_apply_slow<EB()>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, w.slow, t, p->P.p, p->N.p, w.status);
+            if (!fused) hipLaunchKernelGGL(k_apply_emit<EB()>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->rw_P(), p->rw_N(), w.status);
+            hipLaunchKernelGGL(k_apply_slow<EB()>, dim3(64), dim3(kBlock), 0, ctx->stream, bytes, off, rows, w.slow, t, p->rw_P(), p->rw_N(), w.status);
         });
         JG_HIP(hipGetLastError());
         const Status st = read_status(ctx, w.status);
@@ -997,7 +997,7 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
     // parser (slow: not in the compact form; with JANUS_JSON_GROUP=1 also the deferred ones).  max is
     // order-free.
     jg::dispatch_eb(p->eb, [&](auto EB) {
-        hipLaunchKernelGGL(k_apply_emit<EB()>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->P.p, p->N.p, nullptr);
+        hipLaunchKernelGGL(k_apply_emit<EB()>, dim3(ge), dim3(kBlock), 0, ctx->stream, w.emit, rows, n, t.R, p->rw_P(), p->rw_N(), nullptr);
     });
     JG_HIP(hipGetLastError());
     const unsigned long long* lists[2] = {st.n_deferred ? sorted_deferred : nullptr, w.slow};
@@ -1006,7 +1006,7 @@ void finish_wave(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uin
         if (!counts[l]) continue;
         const unsigned gl = blocks_for(counts[l]);
         jg::dispatch_eb(p->eb, [&](auto EB) {
-            hipLaunchKernelGGL(k_apply_list<EB()>, dim3(gl), dim3(kBlock), 0, ctx->stream, bytes, off, rows, lists[l], counts[l], t, p->P.p, p->N.p, w.status);
+            hipLaunchKernelGGL(k_apply_list<EB()>, dim3(gl), dim3(kBlock), 0, ctx->stream, bytes, off, rows, lists[l], counts[l], t, p->rw_P(), p->rw_N(), w.status);
         });
         JG_HIP(hipGetLastError());
     }
@@ -1480,7 +1480,7 @@ void encode_rows(jg_pnc* p, uint64_t n, const uint32_t* key_idx, uint32_t col, c
     }
     const unsigned g = blocks_for(n);
     jg::dispatch_eb(p->eb, [&](auto EB) {
-        hipLaunchKernelGGL((k_encode<EB(), 0>), dim3(g), dim3(kBlock), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
+        hipLaunchKernelGGL((k_encode<EB(), 0>), dim3(g), dim3(kBlock), 0, ctx->stream, rows, n, t, p->ro_P(), p->ro_N(), len, nullptr, col, ddp, ddn);
     });
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemsetAsync(len + n, 0, 8, ctx->stream));
@@ -1494,7 +1494,7 @@ void encode_rows(jg_pnc* p, uint64_t n, const uint32_t* key_idx, uint32_t col, c
     auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, off[n] + 64));
     const unsigned g1 = blocks_for(n, kEncLanes);  // the write pass: one wave per workgroup
     jg::dispatch_eb(p->eb, [&](auto EB) {
-        hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, rows, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
+        hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, rows, n, t, p->ro_P(), p->ro_N(), doff, dout, col, ddp, ddn);
     });
     JG_HIP(hipGetLastError());
     if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(doff), n, sha);  // each state's SHA-256 (ComputeDigest's first level)
@@ -1538,7 +1538,7 @@ int jg_pnc_apply_ops_rewind(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         // Increment / Decrement (k_apply_ops with every op on column col)
         const unsigned g = blocks_for(n);
         jg::dispatch_eb(p->eb, [&](auto EB) {
-            hipLaunchKernelGGL(k_apply_ops_col<EB()>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
+            hipLaunchKernelGGL(k_apply_ops_col<EB()>, dim3(g), dim3(kBlock), 0, ctx->stream, p->rw_P(), p->rw_N(), dkey, col, ddel, disn, n, p->R);
         });
         JG_HIP(hipGetLastError());
         if (n_need == 0) {
@@ -1626,7 +1626,7 @@ int jg_pnc_apply_ops_encode(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         JG_HIP(hipGetLastError());
         // the snapshots' lengths from the rows as they stand (nothing applied yet), their offsets to the host
         jg::dispatch_eb(p->eb, [&](auto EB) {
-            hipLaunchKernelGGL((k_encode<EB(), 0>), dim3(g), dim3(kBlock), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, len, nullptr, col, ddp, ddn);
+            hipLaunchKernelGGL((k_encode<EB(), 0>), dim3(g), dim3(kBlock), 0, ctx->stream, dkey, n, t, p->ro_P(), p->ro_N(), len, nullptr, col, ddp, ddn);
         });
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemsetAsync(len + n, 0, 8, ctx->stream));
@@ -1639,8 +1639,8 @@ int jg_pnc_apply_ops_encode(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, off[n] + 64));
         const unsigned g1 = blocks_for(n, kEncLanes);  // the write pass: one wave per workgroup
         jg::dispatch_eb(p->eb, [&](auto EB) {
-            hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, dkey, n, t, p->P.p, p->N.p, doff, dout, col, ddp, ddn);
-            hipLaunchKernelGGL(k_apply_ops_col<EB()>, dim3(g), dim3(kBlock), 0, ctx->stream, p->P.p, p->N.p, dkey, col, ddel, disn, n, p->R);
+            hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(g1), dim3(kEncLanes), 0, ctx->stream, dkey, n, t, p->ro_P(), p->ro_N(), doff, dout, col, ddp, ddn);
+            hipLaunchKernelGGL(k_apply_ops_col<EB()>, dim3(g), dim3(kBlock), 0, ctx->stream, p->rw_P(), p->rw_N(), dkey, col, ddel, disn, n, p->R);
         });
         JG_HIP(hipGetLastError());
         if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(doff), n, sha);

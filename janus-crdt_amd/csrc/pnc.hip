@@ -10,6 +10,12 @@
 //                    re-delivered batch).  Two halves of one grid: P's workgroups, then N's (two read streams
 //                    at a time); kDenseVecs 16-B vectors of A and of B per lane, non-temporal.  This is
 //                    PNCounter.Merge (PNCounters.cs:131-144).
+//   k_merge_filtered (pnc_filter_kernels.hpp) the same merge of an int64 store by its 32-bit shadow sP / sN = clamp32(P / N):
+//                    reads sA.P sA.N B.P B.N, 24 B per cell, and A itself only for lines that hold a cell at a clamp
+//                    value; writes the raised lines of A with their 64 B of shadow.  From the third consecutive dense
+//                    identity merge on (merge_dense_store: cold -> armed -> valid; k_merge_build writes the shadow
+//                    at the second); every other writer of P / N takes them through jg_pnc::rw_P / rw_N, which
+//                    drops the shadow.
 //   k_merge_indexed  scatter-max of received rows into their keys (atomicMax: rows may repeat a
 //                    key inside one committed batch, SafeCRDTManager.cs:122-146).
 //   k_apply_ops      Increment/Decrement (PNCounters.cs:97-112): wrapping atomic adds.
@@ -22,6 +28,7 @@
 #include <cstdlib>
 
 #include "launch.hpp"
+#include "pnc_filter_kernels.hpp"
 
 namespace {
 
@@ -414,6 +421,100 @@ void launch_merge_dense(jg_ctx* ctx, uint32_t eb, void* AP, void* AN, const void
     JG_HIP(hipGetLastError());
 }
 
+// ---- the dense merge by the 32-bit shadow (int64 stores; pnc_filter_kernels.hpp) -------------------
+// The filtered kernel's shape: kFiltCells cells per lane and unit (2: an 8-B shadow load beside one 16-B vector of B,
+// 8 lanes to a 128-B line of A; 4: a 16-B shadow load beside two vectors of B, 4 lanes to a line), kFiltVecs units per
+// lane, kFiltBlock lanes per workgroup.  Measured against the other shapes in tools/tune_pnc.hip `filter`
+// (profiles/r09/tune_pnc_filter.txt): every shape reads a merged batch in 2.23 - 2.28 ms against k_merge_dense's
+// 2.88 ms; the 4-cell shapes are the fastest there by 0.02 ms but 0.4 ms slower than k_merge_dense when every line
+// changes (4 lanes store a 128-B line of A in two instructions each); of the 2-cell shapes this one is at or ahead of
+// k_merge_dense on all three patterns and the fastest on the merged batch.
+constexpr int kFiltCells = 2;
+constexpr int kFiltVecs = 1;
+constexpr int kFiltBlock = 512;
+constexpr int kBuildBlock = 256;
+
+unsigned halves_for(uint64_t n_units, uint64_t per, uint64_t n_cells) {
+    const uint64_t blocks = (n_units + per - 1) / per;  // per array: the grid holds P's, then N's
+    JG_REQUIRE(2 * blocks < 0xFFFFFFFFull, JG_EINVAL, "merge: %llu cells exceed one launch", (unsigned long long)n_cells);
+    return blocks ? (unsigned)blocks : 1u;  // a half's first block exists for the trailing cells
+}
+
+void launch_merge_filtered(jg_pnc* p, const void* BP, const void* BN, uint64_t n_cells) {
+    const uint64_t n_units = n_cells / kFiltCells;
+    const uint32_t tail = (uint32_t)(n_cells - n_units * kFiltCells);
+    const unsigned half = halves_for(n_units, (uint64_t)kFiltVecs * kFiltBlock, n_cells);
+    hipLaunchKernelGGL((jg::filt::k_merge_filtered<kFiltCells, kFiltVecs, kFiltBlock>), dim3(2 * half), dim3(kFiltBlock), 0, p->ctx->stream,
+                       p->P_.as<long long>(), p->N_.as<long long>(), p->sP.as<int>(), p->sN.as<int>(), (const long long*)BP,
+                       (const long long*)BN, n_units, tail, half);
+    JG_HIP(hipGetLastError());
+}
+
+// The build launch over the batch's cells, then the clamp pass over the store's cells behind the batch.
+void launch_merge_build(jg_pnc* p, const void* BP, const void* BN, uint64_t n_cells) {
+    jg_ctx* ctx = p->ctx;
+    const uint64_t n_units = n_cells / 2;
+    const uint32_t tail = (uint32_t)(n_cells - n_units * 2);
+    const unsigned half = halves_for(n_units, kBuildBlock, n_cells);
+    hipLaunchKernelGGL(jg::filt::k_merge_build<kBuildBlock>, dim3(2 * half), dim3(kBuildBlock), 0, ctx->stream, p->P_.as<long long>(),
+                       p->N_.as<long long>(), p->sP.as<int>(), p->sN.as<int>(), (const long long*)BP, (const long long*)BN, n_units, tail, half);
+    const uint64_t all = p->n_keys * p->R;
+    if (n_cells < all) {
+        const unsigned g = jg::grid_for(ctx, all - n_cells, 256, 16);
+        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(g), dim3(256), 0, ctx->stream, p->P_.as<long long>(), p->sP.as<int>(), n_cells, all);
+        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(g), dim3(256), 0, ctx->stream, p->N_.as<long long>(), p->sN.as<int>(), n_cells, all);
+    }
+    JG_HIP(hipGetLastError());
+}
+
+// The shadow's buffers for the store's shape (kept across cold spells).  false: no room on the device; remembered
+// until the shape changes (pnc_grow), so a store that does not fit does not ask the allocator on every merge.
+bool shadow_ready(jg_pnc* p) {
+    const size_t bytes = (size_t)p->n_keys * p->R * 4;
+    if (p->sP.p && p->sN.p && p->sP.bytes >= bytes && p->sN.bytes >= bytes) return true;
+    if (p->filt_nomem) return false;
+    try {
+        p->sP.alloc(bytes);
+        p->sN.alloc(bytes);
+    } catch (const jg::Error&) {
+        p->sP.release();
+        p->sN.release();
+        p->filt_nomem = true;
+        (void)hipGetLastError();  // the failed allocation's code must not surface at the next launch check
+        jg::clear_error();
+        return false;
+    }
+    return true;
+}
+
+void drop_shadow(jg_pnc* p) {
+    p->sP.release();
+    p->sN.release();
+    p->filt = jg_pnc::kFiltCold;
+    p->filt_nomem = false;
+}
+
+// A dense identity merge of n_rows rows into the store: the one writer that does not go through rw_P / rw_N.
+// int32 stores and stores with the filter off run k_merge_dense and stay cold.  An int64 store runs it while cold
+// (and becomes armed: nothing else has written since this merge), the build launch while armed (and becomes valid),
+// the filtered kernel while valid.
+void merge_dense_store(jg_pnc* p, const void* BP, const void* BN, uint64_t n_rows) {
+    jg_ctx* ctx = p->ctx;
+    const uint64_t n_cells = n_rows * p->R;
+    if (p->eb == 8 && p->filt_on) {
+        if (p->filt == jg_pnc::kFiltValid) return launch_merge_filtered(p, BP, BN, n_cells);
+        if (p->filt == jg_pnc::kFiltArmed && shadow_ready(p)) {
+            launch_merge_build(p, BP, BN, n_cells);
+            p->filt = jg_pnc::kFiltValid;
+            return;
+        }
+        launch_merge_dense(ctx, 8, p->P_.p, p->N_.p, BP, BN, n_cells);
+        p->filt = jg_pnc::kFiltArmed;
+        return;
+    }
+    launch_merge_dense(ctx, p->eb, p->rw_P(), p->rw_N(), BP, BN, n_cells);
+}
+
 // The store's per-key list heads (generation-tagged) and a next[] link per received row (grown to the
 // largest batch); gen = this batch's generation.
 struct Groups { unsigned long long* head; uint32_t* next; unsigned long long gen; };
@@ -523,7 +624,7 @@ void swap_buf(jg::DevBuf& a, jg::DevBuf& b) {
 
 void jg::pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t* d_keys, uint64_t n_rows) {
     Groups g;
-    launch_merge_indexed(p->ctx, p->eb, p->P.p, p->N.p, BP, BN, d_keys, n_rows, p->R, groups_of(p, n_rows, g));
+    launch_merge_indexed(p->ctx, p->eb, p->rw_P(), p->rw_N(), BP, BN, d_keys, n_rows, p->R, groups_of(p, n_rows, g));
 }
 
 // The store grown in place to [n_keys x n_replicas] (never shrunk).  Every new buffer is allocated before anything
@@ -552,12 +653,12 @@ void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
         nNc.alloc((size_t)nk * 4);
     }
     if (nr == orr) {
-        grow_rows(ctx, nP.p, p->P.p, (size_t)ok * orr * eb, nP.bytes);
-        grow_rows(ctx, nN.p, p->N.p, (size_t)ok * orr * eb, nN.bytes);
+        grow_rows(ctx, nP.p, p->ro_P(), (size_t)ok * orr * eb, nP.bytes);
+        grow_rows(ctx, nN.p, p->ro_N(), (size_t)ok * orr * eb, nN.bytes);
         if (table) grow_rows(ctx, nC.p, p->cols.p, (size_t)ok * orr * 16, nC.bytes);
     } else {
-        launch_restride(ctx, eb, nP.p, p->P.p, orr, nr, ok, nk);
-        launch_restride(ctx, eb, nN.p, p->N.p, orr, nr, ok, nk);
+        launch_restride(ctx, eb, nP.p, p->ro_P(), orr, nr, ok, nk);
+        launch_restride(ctx, eb, nN.p, p->ro_N(), orr, nr, ok, nk);
         if (table) launch_restride(ctx, 16, nC.p, p->cols.p, orr, nr, ok, nk);  // new slots all-zero (json_wave.hpp row_cache)
     }
     if (table) grow_rows(ctx, nNc.p, p->ncols.p, (size_t)ok * 4, nNc.bytes);
@@ -566,10 +667,11 @@ void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
     JG_HIP(hipStreamSynchronize(ctx->stream));
     JG_HIP(hipStreamSynchronize(ctx->copy));
     const double t2 = jg::now_us();
-    swap_buf(p->P, nP);
-    swap_buf(p->N, nN);
+    swap_buf(p->P_, nP);
+    swap_buf(p->N_, nN);
     if (table) swap_buf(p->cols, nC), swap_buf(p->ncols, nNc);
     if (nk != ok) p->head.release();  // the grouped merge's heads follow n_keys: first use recreates them (groups_of)
+    drop_shadow(p);  // the dense merge's shadow follows the shape (both streams have drained: nothing reads it)
     p->n_keys = nk;
     p->R = nr;
     if (trace) {
@@ -609,10 +711,10 @@ int jg_pnc_create(jg_ctx* ctx, uint64_t n_keys, uint32_t n_replicas, uint32_t el
         p->ctx = ctx; p->n_keys = n_keys; p->R = n_replicas; p->eb = elem_bytes;
         try {
             const size_t bytes = (size_t)n_keys * n_replicas * elem_bytes;
-            p->P.alloc(bytes);
-            p->N.alloc(bytes);
-            JG_HIP(hipMemsetAsync(p->P.p, 0, bytes, ctx->stream));  // PNCounter(): every replica absent = 0
-            JG_HIP(hipMemsetAsync(p->N.p, 0, bytes, ctx->stream));
+            p->P_.alloc(bytes);
+            p->N_.alloc(bytes);
+            JG_HIP(hipMemsetAsync(p->rw_P(), 0, bytes, ctx->stream));  // PNCounter(): every replica absent = 0
+            JG_HIP(hipMemsetAsync(p->rw_N(), 0, bytes, ctx->stream));
             JG_HIP(hipStreamSynchronize(ctx->stream));
         } catch (...) {
             delete p;
@@ -661,6 +763,28 @@ int jg_pnc_set_max_replicas(jg_pnc* p, uint32_t max_replicas) {
     });
 }
 
+int jg_pnc_set_dense_filter(jg_pnc* p, int on) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
+        check_store(p, "jg_pnc_set_dense_filter");
+        p->filt_on = on != 0;
+        if (!p->filt_on) {
+            jg::ensure_device(p->ctx);
+            JG_HIP(hipStreamSynchronize(p->ctx->stream));  // an asynchronous merge may still read the shadow
+            drop_shadow(p);
+        }
+    });
+}
+
+int jg_pnc_dense_filter_state(jg_pnc* p, int* state) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
+        check_store(p, "jg_pnc_dense_filter_state");
+        JG_REQUIRE(state, JG_EINVAL, "jg_pnc_dense_filter_state: NULL output");
+        *state = p->filt_on ? p->filt : 0;
+    });
+}
+
 int jg_pnc_write_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, const void* P, const void* N) {
     return jg::guard([&] {
         auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
@@ -673,15 +797,15 @@ int jg_pnc_write_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, const
         const size_t bytes = (size_t)n_rows * p->R * p->eb;
         if (!key_idx) {
             JG_REQUIRE(n_rows <= p->n_keys, JG_EINVAL, "jg_pnc_write_rows: %llu rows > n_keys", (unsigned long long)n_rows);
-            JG_HIP(hipMemcpyAsync(p->P.p, P, bytes, hipMemcpyHostToDevice, ctx->stream));
-            JG_HIP(hipMemcpyAsync(p->N.p, N, bytes, hipMemcpyHostToDevice, ctx->stream));
+            JG_HIP(hipMemcpyAsync(p->rw_P(), P, bytes, hipMemcpyHostToDevice, ctx->stream));
+            JG_HIP(hipMemcpyAsync(p->rw_N(), N, bytes, hipMemcpyHostToDevice, ctx->stream));
         } else {
             const uint32_t* dk = upload_keys(ctx, key_idx, n_rows, p->n_keys, "jg_pnc_write_rows");
             void* st = jg::scratch(ctx, ctx->scratch2, 2 * bytes);
             JG_HIP(hipMemcpyAsync(st, P, bytes, hipMemcpyHostToDevice, ctx->stream));
             JG_HIP(hipMemcpyAsync((char*)st + bytes, N, bytes, hipMemcpyHostToDevice, ctx->stream));
-            launch_rows_copy(ctx, p->eb, p->P.p, st, dk, n_rows, p->R, 1);
-            launch_rows_copy(ctx, p->eb, p->N.p, (char*)st + bytes, dk, n_rows, p->R, 1);
+            launch_rows_copy(ctx, p->eb, p->rw_P(), st, dk, n_rows, p->R, 1);
+            launch_rows_copy(ctx, p->eb, p->rw_N(), (char*)st + bytes, dk, n_rows, p->R, 1);
         }
         JG_HIP(hipStreamSynchronize(ctx->stream));
     });
@@ -698,13 +822,13 @@ int jg_pnc_read_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, void* 
         const size_t bytes = (size_t)n_rows * p->R * p->eb;
         if (!key_idx) {
             JG_REQUIRE(n_rows <= p->n_keys, JG_EINVAL, "jg_pnc_read_rows: %llu rows > n_keys", (unsigned long long)n_rows);
-            JG_HIP(hipMemcpyAsync(P, p->P.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            JG_HIP(hipMemcpyAsync(N, p->N.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            JG_HIP(hipMemcpyAsync(P, p->ro_P(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+            JG_HIP(hipMemcpyAsync(N, p->ro_N(), bytes, hipMemcpyDeviceToHost, ctx->stream));
         } else {
             const uint32_t* dk = upload_keys(ctx, key_idx, n_rows, p->n_keys, "jg_pnc_read_rows");
             void* st = jg::scratch(ctx, ctx->scratch2, 2 * bytes);
-            launch_rows_copy(ctx, p->eb, st, p->P.p, dk, n_rows, p->R, 0);
-            launch_rows_copy(ctx, p->eb, (char*)st + bytes, p->N.p, dk, n_rows, p->R, 0);
+            launch_rows_copy(ctx, p->eb, st, p->ro_P(), dk, n_rows, p->R, 0);
+            launch_rows_copy(ctx, p->eb, (char*)st + bytes, p->ro_N(), dk, n_rows, p->R, 0);
             JG_HIP(hipMemcpyAsync(P, st, bytes, hipMemcpyDeviceToHost, ctx->stream));
             JG_HIP(hipMemcpyAsync(N, (char*)st + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
         }
@@ -721,7 +845,7 @@ void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long*
     const unsigned grid = jg::grid_for(ctx, n * 64, kBlock, 16);
     dispatch_eb(p->eb, [&](auto EB) {
         using T = typename Elem<EB()>::T;
-        hipLaunchKernelGGL(k_values<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const T*)p->P.p, (const T*)p->N.p, p->R, d_keys, n, d_out,
+        hipLaunchKernelGGL(k_values<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const T*)p->ro_P(), (const T*)p->ro_N(), p->R, d_keys, n, d_out,
                            d_ovf, d_at, d_count, of_code);
     });
     JG_HIP(hipGetLastError());
@@ -747,8 +871,8 @@ int jg_pnc_merge_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, const
         JG_HIP(hipMemcpyAsync(st, P, bytes, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemcpyAsync((char*)st + bytes, N, bytes, hipMemcpyHostToDevice, ctx->stream));
         Groups g;
-        if (dk) launch_merge_indexed(ctx, p->eb, p->P.p, p->N.p, st, (char*)st + bytes, dk, n_rows, p->R, groups_of(p, n_rows, g));
-        else launch_merge_dense(ctx, p->eb, p->P.p, p->N.p, st, (char*)st + bytes, n_rows * p->R);
+        if (dk) launch_merge_indexed(ctx, p->eb, p->rw_P(), p->rw_N(), st, (char*)st + bytes, dk, n_rows, p->R, groups_of(p, n_rows, g));
+        else merge_dense_store(p, st, (char*)st + bytes, n_rows);
         JG_HIP(hipStreamSynchronize(ctx->stream));
     });
 }
@@ -778,7 +902,7 @@ int jg_pnc_apply_ops(jg_pnc* p, uint64_t n_ops, const uint32_t* key, const uint3
         const unsigned grid = jg::grid_for(ctx, n_ops, kBlock, 16);
         jg::dispatch_eb(p->eb, [&](auto EB) {
             using T = typename Elem<EB()>::T;
-            hipLaunchKernelGGL(k_apply_ops<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)p->P.p, (T*)p->N.p, dkey, dcol, ddel, dn, n_ops,
+            hipLaunchKernelGGL(k_apply_ops<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)p->rw_P(), (T*)p->rw_N(), dkey, dcol, ddel, dn, n_ops,
                                p->R);
         });
         JG_HIP(hipGetLastError());
@@ -876,11 +1000,11 @@ int jg_pnc_merge_batch(jg_pnc* p, const jg_rows* r, int async) {
             JG_REQUIRE(r->max_key < p->n_keys, JG_EINVAL, "jg_pnc_merge_batch: batch addresses key %u >= n_keys %llu", r->max_key,
                        (unsigned long long)p->n_keys);
             Groups g;
-            launch_merge_indexed(ctx, p->eb, p->P.p, p->N.p, r->P.p, r->N.p, r->keys.as<uint32_t>(), r->n_rows, p->R, groups_of(p, r->n_rows, g));
+            launch_merge_indexed(ctx, p->eb, p->rw_P(), p->rw_N(), r->P.p, r->N.p, r->keys.as<uint32_t>(), r->n_rows, p->R, groups_of(p, r->n_rows, g));
         } else {
             JG_REQUIRE(r->n_rows <= p->n_keys, JG_EINVAL, "jg_pnc_merge_batch: identity batch of %llu rows > n_keys",
                        (unsigned long long)r->n_rows);
-            launch_merge_dense(ctx, p->eb, p->P.p, p->N.p, r->P.p, r->N.p, r->n_rows * p->R);
+            merge_dense_store(p, r->P.p, r->N.p, r->n_rows);
         }
         if (!async) JG_HIP(hipStreamSynchronize(ctx->stream));
     });

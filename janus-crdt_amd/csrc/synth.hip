@@ -67,7 +67,7 @@ int jg_synth_pnc_store(jg_pnc* p, uint64_t seed) {
         jg::require_writable(p, "jg_synth_pnc_store");
         JG_REQUIRE(p, JG_EINVAL, "jg_synth_pnc_store: store is NULL");
         jg::ensure_device(p->ctx);
-        fill_pnc(p->ctx, p->eb, p->P.p, p->N.p, 0, p->n_keys, p->R, 0, seed);
+        fill_pnc(p->ctx, p->eb, p->rw_P(), p->rw_N(), 0, p->n_keys, p->R, 0, seed);
         JG_HIP(hipStreamSynchronize(p->ctx->stream));
     });
 }

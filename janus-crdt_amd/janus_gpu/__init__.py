@@ -47,6 +47,7 @@ EXPORTS = [
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
     "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
+    "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -173,6 +174,8 @@ _SIGS = {
     "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
+    "jg_pnc_set_dense_filter": ([_vp, C.c_int], C.c_int),
+    "jg_pnc_dense_filter_state": ([_vp, C.POINTER(C.c_int)], C.c_int),
 }
 GUID_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])  # jg_guid
 
@@ -360,6 +363,17 @@ class PNCStore:
         """Let a call that runs out of columns widen the store up to max_replicas (0 = fixed shape)."""
         _check(load().jg_pnc_set_max_replicas(self._h, max_replicas))
         self._elastic = max_replicas > 0
+
+    # ---- dense merge filter (jg_pnc_set_dense_filter / jg_pnc_dense_filter_state) ----
+    def set_dense_filter(self, on: bool) -> None:
+        """Allow (default) or forbid the int32 shadow that runs of dense identity merges read instead of P and N."""
+        _check(load().jg_pnc_set_dense_filter(self._h, 1 if on else 0))
+
+    def dense_filter_state(self) -> int:
+        """0 off or cold, 1 armed (the next dense identity merge builds the shadow), 2 valid."""
+        st = C.c_int(-1)
+        _check(load().jg_pnc_dense_filter_state(self._h, C.byref(st)))
+        return int(st.value)
 
     def _widened(self, rc, bad_msg=None) -> None:
         # after a call that may have widened the store: n_keys / R size read_rows' and columns' buffers

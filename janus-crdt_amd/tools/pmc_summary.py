@@ -85,6 +85,20 @@ def dense_split(path, counter, kernel="k_merge_dense<8>"):
     return {"first": v[:1], "steady": v[1:]}
 
 
+def filter_split(path, counter):
+    """The dense merge's counter values (bytes) of an int64 store that merges by its 32-bit shadow, in dispatch order:
+    the first launch after the synthesis is k_merge_dense<8> as ever, the second builds the shadow (k_merge_build),
+    the later ones are the filtered kernel's (k_merge_filtered): the steady state the bench times."""
+    with open(path) as f:
+        rows = sorted((r for r in csv.DictReader(f) if r["Counter_Name"] == counter), key=lambda r: int(r["Dispatch_Id"]))
+    out = {"first": [], "build": [], "steady": []}
+    for r in rows:
+        for kernel, key in (("k_merge_dense<8>", "first"), ("k_merge_build<", "build"), ("k_merge_filtered<", "steady")):
+            if kernel in r["Kernel_Name"]:
+                out[key].append(float(r["Counter_Value"]) * 1024)
+    return out
+
+
 def durations(trace_dir):
     """Kernel durations (ns) per short name from a --kernel-trace run."""
     out = collections.defaultdict(list)
@@ -182,6 +196,13 @@ def main():
     # the dense merge's steady launches (the batch already merged: reads only) apart from the first one after the
     # synthesis (practically every line written back); pnc_merge_dense is the steady figure, what the bench times
     ds = {c: dense_split(d / f"pmc_{c}" / "run_counter_collection.csv", c) for c in ("FETCH_SIZE", "WRITE_SIZE")}
+    fs = {c: filter_split(d / f"pmc_{c}" / "run_counter_collection.csv", c) for c in ("FETCH_SIZE", "WRITE_SIZE")}
+    if fs["FETCH_SIZE"]["steady"] and fs["WRITE_SIZE"]["steady"]:  # the steady launches are the filtered kernel's
+        ds = fs
+        if fs["FETCH_SIZE"]["build"] and fs["WRITE_SIZE"]["build"]:
+            fb, wb = fs["FETCH_SIZE"]["build"][0], fs["WRITE_SIZE"]["build"][0]
+            res["pnc_merge_dense_build_launch"] = 2 * fb + wb
+            res["pnc_merge_dense_build"] = {"fetch_size_bytes": fb, "write_size_bytes": wb, "read_bytes": 2 * fb}
     if ds["FETCH_SIZE"]["steady"] and ds["WRITE_SIZE"]["steady"]:
         f, w = statistics.median(ds["FETCH_SIZE"]["steady"]), statistics.median(ds["WRITE_SIZE"]["steady"])
         res["pnc_merge_dense"] = 2 * f + w

@@ -2,6 +2,8 @@
 // C2 shape (10M keys x 64 replicas, int64), one process, hipEvents per launch, median of rounds.
 // `tune_pnc <rounds> elide`: the store-elision sweep instead (granularity x share of cells changed per launch).
 // `tune_pnc <rounds> steady`: the read-only steady state bench.py times (data x cadence, then the read-side shapes).
+// `tune_pnc <rounds> filter`: the merge by the 32-bit shadow (csrc/pnc_filter_kernels.hpp, the library's own kernels
+// in several shapes) and its build launch beside the parent's kernel.
 // Build: make -C janus-crdt_amd build/tune_pnc (hipcc -O3 --offload-arch=gfx950) ; run on the GPU box.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +13,8 @@
 #include <cstdlib>
 #include <string>
 #include <vector>
+
+#include "pnc_filter_kernels.hpp"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::printf("%s: %s\n", #x, hipGetErrorString(e)); std::exit(1); } } while (0)
 
@@ -587,6 +591,151 @@ int steady_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int roun
     return ok ? 0 : 1;
 }
 
+// ---- the merge by the 32-bit shadow (`tune_pnc <rounds> filter`) ------------------------------------------------
+// The bench's data (k_synth_pnc's cells, A merged once) throughout.  0 %: launches back to back on the merged batch
+// (bench.py's protocol).  One column per key and 100 %: each timed launch behind an untimed fill of B that raises the
+// pattern's cells above everything A holds and, for a kernel that reads the shadow, an untimed clamp pass that makes
+// the shadow exact for what the launches before it left in A (the variants share A).  The parent (the halves grid of
+// k_merge_dense) runs first and last: the difference of its two medians is the A/A spread.
+
+// B for one timed launch: the synthetic received cell, or where the pattern raises it a value above every earlier one
+// that still fits 32 bits (0x7FFE0000 + gen, gen < 2^16; the 6e-5 of the cells whose own value is larger stay).
+// mode 1: one column per key, P only; mode 2: every cell of P and N.
+__global__ __launch_bounds__(256) void k_fill_f(v2* BP, v2* BN, unsigned long long nv, int mode, long long gen) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nv) return;
+    v2 p = {synth_cell(2 * i, 2), synth_cell(2 * i + 1, 2)}, n = {synth_cell(2 * i, 3), synth_cell(2 * i + 1, 3)};
+    const long long up = 0x7FFE0000ll + gen;
+    if (mode == 1) {
+        const unsigned long long key = i >> 5, c = (i & 31) * 2;  // 32 vectors = 64 cells per key
+        const unsigned col = mix(key) & 63;
+        if (col == c) p.x = up;
+        if (col == c + 1) p.y = up;
+    } else if (mode == 2) {
+        p = v2{up, up}, n = v2{up, up};
+    }
+    BP[i] = p;
+    BN[i] = n;
+}
+
+// Counts the cells whose shadow is not the clamp of the cell (a filtered launch that left the shadow behind A).
+__global__ __launch_bounds__(256) void k_count_shadow(const long long* A, const int* S, unsigned long long n, unsigned* bad) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && S[i] != jg::filt::clamp32(A[i])) atomicAdd(bad, 1u);
+}
+
+struct FVariant {
+    const char* name;
+    bool shadow;  // reads (and keeps) SP / SN
+    void (*launch)(v2*, v2*, int*, int*, const v2*, const v2*, unsigned long long, hipStream_t);
+};
+
+void LF_parent(v2* ap, v2* an, int*, int*, const v2* bp, const v2* bn, unsigned long long n_cells, hipStream_t s) {
+    L_rhalves<1, 256>(ap, an, bp, bn, n_cells / 2, s, 0);
+}
+template <int CPL, int VECS, int BLOCK>
+void LF(v2* ap, v2* an, int* sp, int* sn, const v2* bp, const v2* bn, unsigned long long n_cells, hipStream_t s) {
+    const unsigned long long nu = n_cells / CPL;
+    const unsigned half = blocks_of(nu, (unsigned long long)VECS * BLOCK);
+    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CPL, VECS, BLOCK>), dim3(2 * half), dim3(BLOCK), 0, s, (long long*)ap, (long long*)an, sp, sn,
+                       (const long long*)bp, (const long long*)bn, nu, (unsigned)(n_cells - nu * CPL), half);
+}
+void LF_build(v2* ap, v2* an, int* sp, int* sn, const v2* bp, const v2* bn, unsigned long long n_cells, hipStream_t s) {
+    const unsigned long long nu = n_cells / 2;
+    const unsigned half = blocks_of(nu, 256);
+    hipLaunchKernelGGL(jg::filt::k_merge_build<256>, dim3(2 * half), dim3(256), 0, s, (long long*)ap, (long long*)an, sp, sn, (const long long*)bp,
+                       (const long long*)bn, nu, (unsigned)(n_cells - nu * 2), half);
+}
+
+int filter_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int rounds) {
+    const unsigned long long n_cells = nv * 2;
+    hipStream_t s;
+    CK(hipStreamCreate(&s));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    if (rounds > 500) rounds = 500;  // the generation stays below 2^16 (k_fill_f)
+    int *SP, *SN;
+    CK(hipMalloc(&SP, n_cells * 4)); CK(hipMalloc(&SN, n_cells * 4));
+    unsigned* bad;  // [0] cells of A behind B, [1] cells whose shadow is not their clamp
+    CK(hipMalloc(&bad, 8));
+    CK(hipMemsetAsync(bad, 0, 8, s));
+    const unsigned g256 = (unsigned)((nv + 255) / 256), gc = (unsigned)((n_cells + 255) / 256);
+    const std::vector<FVariant> vs = {
+        {"parent (halves U1 B256)", false, LF_parent},
+        {"filtered 2 cells U1 B256", true, LF<2, 1, 256>},
+        {"filtered 2 cells U2 B256", true, LF<2, 2, 256>},
+        {"filtered 2 cells U4 B256", true, LF<2, 4, 256>},
+        {"filtered 2 cells U1 B512", true, LF<2, 1, 512>},
+        {"filtered 4 cells U1 B256", true, LF<4, 1, 256>},
+        {"filtered 4 cells U2 B256", true, LF<4, 2, 256>},
+        {"filtered 4 cells U1 B512", true, LF<4, 1, 512>},
+        {"build launch (2 cells B256)", true, LF_build},
+        {"parent (again)", false, LF_parent},
+    };
+    const size_t nvar = vs.size();
+    const auto clamp_all = [&] {
+        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(num_cus * 16), dim3(256), 0, s, (const long long*)AP, SP, 0ull, n_cells);
+        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(num_cus * 16), dim3(256), 0, s, (const long long*)AN, SN, 0ull, n_cells);
+    };
+    const auto check = [&](const FVariant& v) {
+        hipLaunchKernelGGL(k_count_behind, dim3(g256), dim3(256), 0, s, AP, AN, BP, BN, nv, bad);
+        if (v.shadow) {
+            hipLaunchKernelGGL(k_count_shadow, dim3(gc), dim3(256), 0, s, (const long long*)AP, SP, n_cells, bad + 1);
+            hipLaunchKernelGGL(k_count_shadow, dim3(gc), dim3(256), 0, s, (const long long*)AN, SN, n_cells, bad + 1);
+        }
+    };
+    const auto launch = [&](const FVariant& v) { v.launch(AP, AN, SP, SN, BP, BN, n_cells, s); };
+    // the bench's data: A merged once, its shadow exact
+    hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, AP, AN, nv, 0u);
+    hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, BP, BN, nv, 2u);
+    launch(vs[0]);
+    clamp_all();
+    std::vector<std::vector<float>> t0(nvar), t1(nvar), t2(nvar);
+    for (int r = -1; r < rounds; ++r)  // 0 %: 5 untimed launches, a fence, 20 launches between one event pair
+        for (size_t k = 0; k < nvar; ++k) {
+            for (int i = 0; i < 5; ++i) launch(vs[k]);
+            CK(hipStreamSynchronize(s));
+            CK(hipEventRecord(e0, s));
+            for (int i = 0; i < 20; ++i) launch(vs[k]);
+            CK(hipEventRecord(e1, s));
+            CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (r >= 0) t0[k].push_back(ms / 20);
+            else check(vs[k]);
+        }
+    long long gen = 0;
+    for (int pat = 1; pat <= 2; ++pat)
+        for (int r = -1; r < rounds; ++r)
+            for (size_t k = 0; k < nvar; ++k) {
+                hipLaunchKernelGGL(k_fill_f, dim3(g256), dim3(256), 0, s, BP, BN, nv, pat, ++gen);
+                if (vs[k].shadow) clamp_all();
+                CK(hipEventRecord(e0, s));
+                launch(vs[k]);
+                CK(hipEventRecord(e1, s));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                if (r >= 0) (pat == 1 ? t1 : t2)[k].push_back(ms);
+                else check(vs[k]);
+            }
+    std::printf("C2 shape: 10M keys x 64 replicas, int64, the bench's cells (A merged once); median of %d rounds, ms per launch\n", rounds);
+    std::printf("%-30s %22s %22s %22s\n", "", "0 % (back to back)", "one column per key", "100 %");
+    std::printf("%-30s %22s %22s %22s\n", "variant", "", "(behind a fill)", "(behind a fill)");
+    for (size_t k = 0; k < nvar; ++k) std::printf("%-30s %22.3f %22.3f %22.3f\n", vs[k].name, median(t0[k]), median(t1[k]), median(t2[k]));
+    const float aa[3] = {std::fabs(median(t0[0]) - median(t0[nvar - 1])), std::fabs(median(t1[0]) - median(t1[nvar - 1])),
+                         std::fabs(median(t2[0]) - median(t2[nvar - 1]))};
+    std::printf("%-30s %22.3f %22.3f %22.3f\n", "A/A spread (parent twice)", aa[0], aa[1], aa[2]);
+    std::printf("%-30s %22.3f %22.3f %22.3f\n", "parent, min of rounds", *std::min_element(t0[0].begin(), t0[0].end()),
+                *std::min_element(t1[0].begin(), t1[0].end()), *std::min_element(t2[0].begin(), t2[0].end()));
+    std::printf("%-30s %22.3f %22.3f %22.3f\n", "parent, max of rounds", *std::max_element(t0[0].begin(), t0[0].end()),
+                *std::max_element(t1[0].begin(), t1[0].end()), *std::max_element(t2[0].begin(), t2[0].end()));
+    unsigned h[2] = {0, 0};
+    CK(hipMemcpy(h, bad, 8, hipMemcpyDeviceToHost));
+    const bool ok = h[0] == 0 && h[1] == 0;
+    std::printf("vectors of A left behind B over every variant and pattern: %u; cells whose shadow is not their clamp: %u%s\n", h[0], h[1],
+                ok ? " (ok)" : " (WRONG)");
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     const unsigned long long n_cells = 10000000ull * 64, nv = n_cells / 2;
     hipDeviceProp_t prop;
@@ -595,6 +744,7 @@ int main(int argc, char** argv) {
     v2 *AP, *AN, *BP, *BN;
     CK(hipMalloc(&AP, nv * 16)); CK(hipMalloc(&AN, nv * 16)); CK(hipMalloc(&BP, nv * 16)); CK(hipMalloc(&BN, nv * 16));
     if (argc > 2 && std::string(argv[2]) == "elide") return elide_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
+    if (argc > 2 && std::string(argv[2]) == "filter") return filter_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
     if (argc > 2 && std::string(argv[2]) == "steady") return steady_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
     CK(hipMemset(AP, 1, nv * 16)); CK(hipMemset(AN, 2, nv * 16)); CK(hipMemset(BP, 3, nv * 16)); CK(hipMemset(BN, 0, nv * 16));
     std::vector<Variant> vs = {
