@@ -215,7 +215,7 @@ struct jg_stream_soa {
     ~jg_stream_soa();
 };
 
-struct jg_orset_wire;  // orset_wire.hip: element table + open payload wave (first use only)
+struct jg_orset_wire;  // orset_wave.hpp: element table + open payload wave (first use only)
 namespace jg {
 void orset_wire_free(jg_orset_wire* w);
 void orset_wire_free_retired(jg_orset_wire* w);

@@ -1,5 +1,5 @@
-// orset_commit.hpp — the OR-Set wave commit from the tables, by set buckets (included by orset_wire.hip
-// after orset_tables.hpp).
+// orset_commit.hpp — the OR-Set wave commit from the tables, by set buckets (kernels with internal linkage:
+// included by orset_wire.hip only).
 //
 // A committed wave (ORSet.Merge of every state before the cut, ORSet.cs:253-283) needs two orders:
 //   strings  the wave's new element strings get ids per set in first-insertion order (the add/remove
@@ -25,6 +25,10 @@
 //                 into the dense stream the union reads (position = bucket offset + rank).
 // A bucket larger than the LDS sort holds (kCbMax) sends the wave to the radix path (commit_tables' own).
 #pragma once
+
+#include "orset_tables.hpp"
+
+namespace {
 
 constexpr uint32_t kCbMax = 2048;  // items of one set / (side, set) the LDS sorts hold
 constexpr int kCbBlock = 256;      // the largest workgroup of k_cb_strings / k_cb_records
@@ -373,3 +377,5 @@ __global__ __launch_bounds__(kCbBlock) void k_cb_records(Sparse S, StrTab T, Rec
         oo[o0 + r] = mint[x];
     }
 }
+
+}  // namespace

@@ -1,4 +1,5 @@
-// orset_group.hpp — pass 1 of orset_wire.hip with one WAVE per ORSetMsg (included by orset_wire.hip only).
+// orset_group.hpp — pass 1 of orset_wire.hip with one WAVE per ORSetMsg (kernels with internal linkage: included by
+// orset_wire.hip only).
 //
 // k_ow_parse gives each ~1.2 KB state to one thread, which walks it byte by byte through dependent window
 // loads: a wave's 64 lanes then touch 64 payloads ~1.2 KB apart on every load, and the pass runs at ~75 GB/s
@@ -26,6 +27,10 @@
 // with identical outputs, and never reports an error itself.  Writes are bounded by the message's own
 // sparse regions, so a message that turns out slow overwrites nothing of another's.
 #pragma once
+
+#include "orset_wave.hpp"
+
+namespace {
 
 constexpr uint32_t kOgBytes = 4096;            // LDS bytes per message: payload + its 16-B alignment offset
 constexpr uint32_t kOgWin = kOgBytes / 16;     // windows per message
@@ -283,3 +288,5 @@ __global__ void k_ow_reject_slow(const uint8_t* __restrict__ slow, uint64_t m0, 
     na[m] = 0;
     err[m] = kKindInval;
 }
+
+}  // namespace

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "launch.hpp"
+#include "orset_layouts.hpp"
 #include "orset_names.hpp"
 
 namespace {
@@ -313,14 +314,15 @@ Resolved resolve_on_device(jg_orset* s, Packed& P, uint64_t n, const uint8_t* is
     jg_ctx* ctx = s->ctx;
     std::memset(P.epoch(), 0, n * 4);
     for (uint64_t i = 0; i < n; ++i) P.meta()[i] = is_null[i] ? 1 : 0;
-    const jg::NamesRef R = jg::orset_names_ref(s, 0, 0, 0);
+    jg::ElemTable& T = *jg::orset_elem_table(s, true);
+    T.ensure_names(ctx, 0, 0);
     Resolved r{};
     uint8_t* d;  // the staged arrays, at the block's start
     jg::Layout L;
     L.add(d, P.h.size(), 8), L.add(r.q, n, 8), L.add(r.elem, n, 8), L.add(r.out, n, 8);
     L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 64));
     JG_HIP(hipMemcpyAsync(d, P.h.data(), P.h.size(), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_nm_resolve, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, R.N, R.set_cap, R.kmask, R.salt, P.on(d), n, r.elem, r.q);
+    hipLaunchKernelGGL(k_nm_resolve, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, T.view(), T.set_cap, T.kmask, T.salt, P.on(d), n, r.elem, r.q);
     JG_HIP(hipGetLastError());
     return r;
 }
@@ -331,7 +333,212 @@ void scan_in_place(jg_ctx* ctx, unsigned long long* d, uint64_t n) {
                 [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, d, d, items, ctx->stream); });
 }
 
+// ---- the table itself (jg::ElemTable): rebuilds after growth, jg_orset_names_sync's updates ---------------------
+__global__ void k_names_rebuild(Names N, uint64_t n_names) {
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g < n_names && N.gen[g] == N.set_gen[N.set[g]]) tab_insert(N, N.key[g], (uint32_t)g);
+}
+
+__global__ void k_itab_rebuild(Names N, uint64_t n_names) {
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g < n_names) itab_insert(N, N.set[g], N.id[g], (uint32_t)g);
+}
+
+__global__ void k_sets_update(Names N, const uint32_t* __restrict__ set, const uint32_t* __restrict__ next, const uint8_t* __restrict__ cleared, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (cleared[i]) N.set_gen[set[i]] += 1;
+    N.next_id[set[i]] = next[i];
+}
+
+__global__ void k_names_put(Names N, uint64_t g0, uint64_t pool0, const uint32_t* __restrict__ nset, const uint32_t* __restrict__ nid,
+                            const uint64_t* __restrict__ off, uint64_t n, uint64_t kmask, uint64_t salt) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t g = g0 + i;
+    const uint32_t set = nset[i], len = (uint32_t)(off[i + 1] - off[i]);
+    const uint8_t* b = N.pool + pool0 + off[i];
+    uint64_t h = kFnvBasis;
+    for (uint32_t k = 0; k < len; ++k) h = (h ^ b[k]) * kFnvPrime;
+    const uint64_t key = name_key(set, h, salt) & kmask;
+    N.set[g] = set;
+    N.id[g] = nid[i];
+    N.gen[g] = N.set_gen[set];
+    N.len[g] = len;
+    N.off[g] = pool0 + off[i];
+    N.key[g] = key;
+    tab_insert(N, key, (uint32_t)g);
+    itab_insert(N, set, nid[i], (uint32_t)g);
+}
+
+// The page-locked staging (layout: jg::NamesStaging, orset_layouts.hpp) with room for `need` bytes.
+void names_reserve(jg::ElemTable::NamesOut& o, size_t need) {
+    if (o.cap >= need) return;
+    if (o.ev) JG_HIP(hipEventSynchronize(o.ev));  // no earlier copy may still land in the old block
+    if (o.host) JG_HIP(hipHostFree(o.host));
+    o.host = nullptr;
+    o.cap = 0;
+    void* p = nullptr;
+    JG_HIP(hipHostMalloc(&p, need + need / 2, hipHostMallocDefault));
+    o.host = static_cast<uint8_t*>(p);
+    o.cap = need + need / 2;
+}
+
+// The copies of L.n names from `from` on and the nb pool bytes from pool0 on into the staging, queued on q.
+void names_stage(jg::ElemTable& T, const jg::NamesStaging& L, uint64_t from, uint64_t pool0, uint64_t nb, hipStream_t q) {
+    uint8_t* h = T.nout.host;
+    JG_HIP(hipMemcpyAsync(h + L.set, T.nset.as<uint32_t>() + from, L.n * 4, hipMemcpyDeviceToHost, q));
+    JG_HIP(hipMemcpyAsync(h + L.id, T.nid.as<uint32_t>() + from, L.n * 4, hipMemcpyDeviceToHost, q));
+    JG_HIP(hipMemcpyAsync(h + L.len, T.nlen.as<uint32_t>() + from, L.n * 4, hipMemcpyDeviceToHost, q));
+    JG_HIP(hipMemcpyAsync(h + L.pool_off, T.noff.as<unsigned long long>() + from, L.n * 8, hipMemcpyDeviceToHost, q));
+    if (nb) JG_HIP(hipMemcpyAsync(h + L.pool, T.pool.as<uint8_t>() + pool0, nb, hipMemcpyDeviceToHost, q));
+}
+
+// Names [from, to), whose bytes lie in the pool range [pool0, pool1), in the staging as a pull (a queued wave-names
+// copy is gone): staged on ctx->stream and waited for, unless the staging holds exactly that pull already.
+void names_stage_now(jg_ctx* ctx, jg::ElemTable& T, uint64_t from, uint64_t to, uint64_t pool0, uint64_t pool1, const char* who) {
+    auto& o = T.nout;
+    if (o.since_from == from && o.since_to == to && o.since_pool0 == pool0 && o.since_pool1 == pool1) return;
+    const jg::NamesStaging L(to - from, pool1 - pool0);
+    if (o.ev) JG_HIP(hipEventSynchronize(o.ev));
+    o.g0 = o.g1 = 0;
+    names_reserve(o, L.bytes);
+    names_stage(T, L, from, pool0, pool1 - pool0, ctx->stream);
+    JG_HIP(hipStreamSynchronize(ctx->stream));
+    const auto* hlen = reinterpret_cast<const uint32_t*>(o.host + L.len);
+    const auto* hat = reinterpret_cast<const uint64_t*>(o.host + L.pool_off);
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < L.n; ++i) {
+        const uint64_t at = hat[i], len = hlen[i];
+        JG_REQUIRE(at >= pool0 && at + len <= pool1, JG_ESTATE, "%s: name %llu's bytes lie outside the pool range of its log position", who,
+                   (unsigned long long)(from + i));
+        sum += len;
+    }
+    o.since_from = from, o.since_to = to, o.since_pool0 = pool0, o.since_pool1 = pool1, o.since_bytes = sum;
+}
+
+// Queue the copy of the names [g0, g1) / pool bytes [p0, p1) the last commit issued (async on ctx->stream).
+void queue_names(jg_ctx* ctx, jg::ElemTable& T) {
+    auto& o = T.nout;
+    o.g0 = o.g1 = 0;
+    o.since_from = UINT64_MAX;  // the staging is about to hold this commit's names
+    const uint64_t n = T.g1 - T.g0, nb = T.p1 - T.p0;
+    if (n == 0) return;
+    const jg::NamesStaging L(n, nb);
+    names_reserve(o, L.bytes);
+    if (!o.ev) JG_HIP(hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
+    // on the copy queue (idle once a wave's uploads are in), behind the commit's kernels: the record sorts and
+    // the union behind them on ctx->stream do not wait for these copies.  The names arrays are only ever
+    // appended to past g1 / p1 or reallocated, and a reallocation (grow_keep) syncs the copy queue first.
+    hipStream_t q = ctx->copy ? ctx->copy : ctx->stream;
+    if (q != ctx->stream) {
+        JG_HIP(hipEventRecord(o.ev, ctx->stream));
+        JG_HIP(hipStreamWaitEvent(q, o.ev, 0));
+    }
+    names_stage(T, L, T.g0, T.p0, nb, q);
+    JG_HIP(hipEventRecord(o.ev, q));
+    o.g0 = T.g0, o.g1 = T.g1, o.p0 = T.p0, o.p1 = T.p1;
+}
+
 }  // namespace
+
+namespace jg {
+
+ElemTable::~ElemTable() {
+    for (void* p : retired) (void)hipFree(p);
+    if (nout.ev) (void)hipEventSynchronize(nout.ev);
+    if (nout.host) (void)hipHostFree(nout.host);
+    if (nout.ev) (void)hipEventDestroy(nout.ev);
+}
+
+Names ElemTable::view() const {
+    return Names{tab.as<unsigned long long>(), tab_cap ? tab_cap - 1 : 0, nset.as<uint32_t>(), nid.as<uint32_t>(), ngen.as<uint32_t>(), nlen.as<uint32_t>(),
+                 noff.as<unsigned long long>(), nkey.as<unsigned long long>(), pool.as<uint8_t>(), set_gen.as<uint32_t>(), next_id.as<uint32_t>(),
+                 ikey.as<unsigned long long>(), ival.as<uint32_t>(), itab_cap ? itab_cap - 1 : 0};
+}
+
+void ElemTable::ensure_sets(jg_ctx* ctx, uint64_t n_sets) {
+    if (n_sets <= set_cap) return;
+    const uint64_t cap = std::max<uint64_t>(n_sets + n_sets / 2, 1024);
+    grow_keep(ctx, set_gen, cap * 4, set_cap * 4, true, &retired);
+    grow_keep(ctx, next_id, cap * 4, set_cap * 4, true, &retired);
+    set_cap = set_gen.bytes / 4;
+}
+
+void ElemTable::ensure_names(jg_ctx* ctx, uint64_t incoming, uint64_t pool_bytes) {
+    const uint64_t total = n_names + incoming;
+    JG_REQUIRE(total < 0xFFFFFFF0ull, JG_ESTATE, "OR-Set element table: more than 2^32 names");
+    if (total > name_cap) {
+        const uint64_t cap = std::max<uint64_t>(total + total / 2, 4096);
+        // the per-name arrays: {buffer, element size}
+        const std::pair<DevBuf*, size_t> arrays[] = {{&nset, 4}, {&nid, 4}, {&ngen, 4}, {&nlen, 4}, {&noff, 8}, {&nkey, 8}};
+        for (const auto& [b, size] : arrays) grow_keep(ctx, *b, cap * size, n_names * size, false, &retired);
+        name_cap = std::min({nset.bytes / 4, nid.bytes / 4, ngen.bytes / 4, nlen.bytes / 4, noff.bytes / 8, nkey.bytes / 8});
+    }
+    if (pool_used + pool_bytes > pool_cap) {  // x1.5: a pool grown to the exact need grew again every wave
+        grow_keep(ctx, pool, std::max<uint64_t>({pool_used + pool_bytes, pool_cap + pool_cap / 2, 1 << 20}), pool_used, false, &retired);
+        pool_cap = pool.bytes;
+    }
+    // a hash table outgrown: its block retired, not freed (see grow_keep), a new one zeroed and filled again
+    const auto regrow = [&](DevBuf& b, size_t bytes, bool zero) {
+        if (b.p) retired.push_back(b.p);
+        b.p = nullptr;
+        b.bytes = 0;
+        b.alloc(bytes);
+        if (zero) JG_HIP(hipMemsetAsync(b.p, 0, bytes, ctx->stream));
+    };
+    if (tab_cap == 0 || 2 * total > tab_cap) {
+        tab_cap = pow2_at_least(4 * total, 1024);
+        regrow(tab, tab_cap * 8, true);
+        if (n_names) hipLaunchKernelGGL(k_names_rebuild, dim3(blocks_for(n_names)), dim3(kBlock), 0, ctx->stream, view(), n_names);
+        JG_HIP(hipGetLastError());
+    }
+    if (itab_cap == 0 || 2 * total > itab_cap) {  // the (set, id) index: every name, load <= 1/2
+        itab_cap = pow2_at_least(4 * total, 1024);
+        regrow(ikey, itab_cap * 8, true);
+        regrow(ival, itab_cap * 4, false);
+        if (n_names) hipLaunchKernelGGL(k_itab_rebuild, dim3(blocks_for(n_names)), dim3(kBlock), 0, ctx->stream, view(), n_names);
+        JG_HIP(hipGetLastError());
+    }
+}
+
+// id_bound sums the names every commit issued over ALL sets, so on a store with many sets it grows far past any
+// one set's next id and would refuse waves every set still has room for.  Before refusing, the
+// bound is tightened to the exact largest per-set next id (one device max over the sets, one round trip); the
+// check then asks whether that set plus every name of the wave could pass 2^32 - 2 — still conservative (all
+// names counted against the fullest set), exact in the case that matters (a set near its limit).
+uint64_t ElemTable::tight_id_bound(jg_ctx* ctx, DevBuf& cub_temp) {
+    if (set_cap == 0) return id_bound = 0;
+    ensure(idmax, 16);
+    const uint32_t* nx = next_id.as<uint32_t>();
+    const int n_sets = cub_count(set_cap, "sets");
+    cub_run(cub_in(cub_temp), [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceReduce::Max(temp, bytes, nx, idmax.as<uint32_t>(), n_sets, ctx->stream);
+    });
+    pin_get(ctx, 0, idmax.p, 4);
+    pin_sync(ctx);
+    uint32_t mx;
+    std::memcpy(&mx, pin_at(ctx, 0), 4);
+    return id_bound = mx;
+}
+
+void ElemTable::names_added(uint64_t n, uint64_t pool_used_now, uint64_t next_id_bound) {
+    id_bound = std::max(id_bound, next_id_bound);
+    n_names += n;
+    pool_used = pool_used_now;
+    if (!marks.empty() && marks.back().first == n_names) return;
+    marks.emplace_back(n_names, pool_used);
+    if (marks.size() > 4096) marks.erase(marks.begin(), marks.begin() + 2048);
+}
+
+void ElemTable::issue_names(jg_ctx* ctx, uint64_t n_new, uint64_t pool_used_now) {
+    names_added(n_new, pool_used_now, id_bound + n_new);
+    g1 = n_names;
+    p1 = pool_used;
+    queue_names(ctx, *this);
+}
+
+}  // namespace jg
 
 extern "C" {
 
@@ -388,7 +595,8 @@ int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint
         jg_ctx* ctx = s->ctx;
         jg::ensure_device(ctx);
         jg::sync_counts(s);
-        const jg::NamesRef R = jg::orset_names_ref(s, 0, 0, 0);
+        jg::ElemTable& T = *jg::orset_elem_table(s, true);
+        T.ensure_names(ctx, 0, 0);
         // the members: jg_orset_lookup_all's count pass, offsets by a device scan, its write pass
         auto* st = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch, (n + 1) * 8 + n * 4 + 64));
         auto* dmoff = reinterpret_cast<unsigned long long*>(st);
@@ -412,7 +620,7 @@ int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint
         auto* dmiss = dnoff + total + 1;  // raised by a member whose id has no name
         JG_HIP(hipMemsetAsync(dnoff + total, 0, 16, ctx->stream));
         jg::orset_lookup_all_device(s, dset, n, reinterpret_cast<uint64_t*>(dmoff), delem);
-        hipLaunchKernelGGL(k_nm_lens, dim3(blocks_for(total)), dim3(kBlock), 0, ctx->stream, R.N, reinterpret_cast<const uint64_t*>(dmoff), n, dset,
+        hipLaunchKernelGGL(k_nm_lens, dim3(blocks_for(total)), dim3(kBlock), 0, ctx->stream, T.view(), reinterpret_cast<const uint64_t*>(dmoff), n, dset,
                            delem, total, dg, dnoff, dnull, dmiss);
         JG_HIP(hipGetLastError());
         scan_in_place(ctx, dnoff, total + 1);
@@ -429,7 +637,7 @@ int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint
                    (unsigned long long)nb, (unsigned long long)cap_elems, (unsigned long long)cap_bytes);
         if (nb) {
             auto* dbytes = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch3, nb + 64));
-            hipLaunchKernelGGL(k_nm_copy, dim3(blocks_for(nb)), dim3(kBlock), 0, ctx->stream, R.N, dnoff, dg, total, nb, dbytes);
+            hipLaunchKernelGGL(k_nm_copy, dim3(blocks_for(nb)), dim3(kBlock), 0, ctx->stream, T.view(), dnoff, dg, total, nb, dbytes);
             JG_HIP(hipGetLastError());
             JG_HIP(hipMemcpyAsync(bytes, dbytes, nb, hipMemcpyDeviceToHost, ctx->stream));
         }
@@ -482,8 +690,10 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
         for (uint64_t i = 0; i < n; ++i) P.meta()[i] = (uint8_t)((is_null[i] ? 1 : 0) | op[i] << 1);
 
         // every allocation first: room for the sets, the tables, the call's own block
-        jg::NamesRef R = jg::orset_names_ref(s, n_sets, 0, 0);
-        JG_REQUIRE(!R.open, JG_EINVAL, "jg_orset_apply_ops_names: a wave is open");
+        jg::ElemTable& T = *jg::orset_elem_table(s, true);
+        T.ensure_sets(ctx, n_sets);
+        T.ensure_names(ctx, 0, 0);
+        JG_REQUIRE(!jg::orset_wave_open(s), JG_EINVAL, "jg_orset_apply_ops_names: a wave is open");
         const uint64_t ccap = jg::pow2_at_least(2 * n_add, 64);
         // the winners' sort orders on the set's bits and the op index (an unset key, all ones, sorts last either way)
         int key_bits = 32;
@@ -529,7 +739,7 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
         JG_HIP(hipMemsetAsync(C.first, 0xFF, ccap * 4, ctx->stream));
         JG_HIP(hipMemsetAsync(st, 0, 16, ctx->stream));
         const dim3 grid(blocks_for(n + 1)), block(kBlock);
-        hipLaunchKernelGGL(k_nm_claim, grid, block, 0, ctx->stream, R.N, R.kmask, R.salt, S, n, C, rid, nkey, slot);
+        hipLaunchKernelGGL(k_nm_claim, grid, block, 0, ctx->stream, T.view(), T.kmask, T.salt, S, n, C, rid, nkey, slot);
         hipLaunchKernelGGL(k_nm_win, grid, block, 0, ctx->stream, S, n, C, slot, cnt, len, wkey);
         JG_HIP(hipGetLastError());
         const auto tmp = jg::cub_in(dtmp, tb);
@@ -538,7 +748,7 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
         jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
             return hipcub::DeviceRadixSort::SortKeys(temp, bytes, wkey, skey, n_i, 0, key_bits, ctx->stream);
         });
-        hipLaunchKernelGGL(k_nm_assign, grid, block, 0, ctx->stream, R.N, skey, n, newid, st);
+        hipLaunchKernelGGL(k_nm_assign, grid, block, 0, ctx->stream, T.view(), skey, n, newid, st);
         hipLaunchKernelGGL(k_nm_ids, grid, block, 0, ctx->stream, S, n, C, rid, nkey, slot, newid, delem);
         JG_HIP(hipGetLastError());
         stamp(2);
@@ -551,7 +761,7 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
         const auto* hw = static_cast<const uint64_t*>(jg::pin_at(ctx, 0));
         const uint64_t n_new = hw[0], new_bytes = hw[1], over = hw[2], id_bound = hw[3];
         JG_REQUIRE(!over, JG_ESTATE, "jg_orset_apply_ops_names: a set has no element ids left");
-        if (n_new) R = jg::orset_names_ref(s, n_sets, n_new, new_bytes);  // growing rebuilds, it changes no content
+        if (n_new) T.ensure_names(ctx, n_new, new_bytes);  // growing rebuilds, it changes no content
 
         // the record side over the ids: jg_orset_apply_ops' walk and union; the table is unchanged if it refuses
         jg::orset_apply_ops_ids(s, n, set, elem.data(), op, tag_lo, tag_hi, result, add_lim, rem_lim);
@@ -560,12 +770,12 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
         // the table: what jg_orset_names_sync would have been told
         stamp(3);
         if (n_new || nc) {
-            if (n_new) hipLaunchKernelGGL(k_nm_put, grid, block, 0, ctx->stream, R.N, R.n_names, R.pool_used, S, n, cnt, len, nkey, newid);
-            hipLaunchKernelGGL(k_nm_sets, dim3(blocks_for(std::max(n, nc))), block, 0, ctx->stream, R.N, skey, n, dcset, dccnt, nc);
+            if (n_new) hipLaunchKernelGGL(k_nm_put, grid, block, 0, ctx->stream, T.view(), T.n_names, T.pool_used, S, n, cnt, len, nkey, newid);
+            hipLaunchKernelGGL(k_nm_sets, dim3(blocks_for(std::max(n, nc))), block, 0, ctx->stream, T.view(), skey, n, dcset, dccnt, nc);
             JG_HIP(hipGetLastError());
             stamp(4);
             JG_HIP(hipStreamSynchronize(ctx->stream));
-            jg::orset_names_appended(s, n_new, new_bytes, id_bound);
+            T.names_added(n_new, T.pool_used + new_bytes, id_bound);
         }
         if (tr) {
             float up = 0, res = 0, put = 0;
@@ -577,6 +787,109 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
             for (hipEvent_t e : ev)
                 if (e) (void)hipEventDestroy(e);
         }
+    });
+}
+
+int jg_orset_names_sync(jg_orset* s, uint64_t n_sets, const uint32_t* set, const uint32_t* next_id, const uint8_t* cleared, uint64_t n_names,
+                        const uint32_t* name_set, const uint32_t* name_id, const uint64_t* off, const uint8_t* bytes) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
+        jg::require_writable(s, "jg_orset_names_sync");
+        JG_REQUIRE(s, JG_EINVAL, "jg_orset_names_sync: store is NULL");
+        JG_REQUIRE((n_sets == 0 || (set && next_id && cleared)) && (n_names == 0 || (name_set && name_id && off && bytes)), JG_EINVAL,
+                   "jg_orset_names_sync: NULL argument");
+        JG_REQUIRE(n_names == 0 || off[0] == 0, JG_EINVAL, "jg_orset_names_sync: off[0] must be 0");
+        jg_ctx* ctx = s->ctx;
+        jg::ensure_device(ctx);
+        jg::ElemTable& T = *jg::orset_elem_table(s, true);
+        JG_REQUIRE(!jg::orset_wave_open(s), JG_EINVAL, "jg_orset_names_sync: a wave is open");
+        uint64_t mx = 0, idb = 0;
+        for (uint64_t i = 0; i < n_sets; ++i) mx = std::max<uint64_t>(mx, (uint64_t)set[i] + 1), idb = std::max<uint64_t>(idb, next_id[i]);
+        for (uint64_t i = 0; i < n_names; ++i) {
+            JG_REQUIRE(off[i + 1] >= off[i] && off[i + 1] - off[i] < 0x7FFFFFFFull, JG_EINVAL, "jg_orset_names_sync: bad offsets at name %llu",
+                       (unsigned long long)i);
+            JG_REQUIRE(name_id[i] < JG_NULL_ELEM - 1, JG_EINVAL, "jg_orset_names_sync: id %u out of range", name_id[i]);
+            mx = std::max<uint64_t>(mx, (uint64_t)name_set[i] + 1);
+        }
+        if (mx == 0) return;
+        T.ensure_sets(ctx, mx);
+        const uint64_t nb = n_names ? off[n_names] : 0;
+        T.ensure_names(ctx, n_names, nb);
+        uint32_t *d_set, *d_next, *d_nset, *d_nid;
+        uint64_t* d_off;
+        uint8_t* d_clr;
+        jg::Layout L;
+        L.add(d_set, n_sets, 4), L.add(d_next, n_sets, 4), L.add(d_nset, n_names, 4), L.add(d_nid, n_names, 4);
+        L.add(d_off, n_names + 1, 16), L.add(d_clr, n_sets, 1);
+        L.bind(jg::scratch(ctx, ctx->scratch, L.bytes() + 64));
+        if (n_sets) {
+            JG_HIP(hipMemcpyAsync(d_set, set, n_sets * 4, hipMemcpyHostToDevice, ctx->stream));
+            JG_HIP(hipMemcpyAsync(d_next, next_id, n_sets * 4, hipMemcpyHostToDevice, ctx->stream));
+            JG_HIP(hipMemcpyAsync(d_clr, cleared, n_sets, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_sets_update, dim3(blocks_for(n_sets)), dim3(kBlock), 0, ctx->stream, T.view(), d_set, d_next, d_clr, n_sets);
+            JG_HIP(hipGetLastError());
+        }
+        if (n_names) {
+            JG_HIP(hipMemcpyAsync(d_nset, name_set, n_names * 4, hipMemcpyHostToDevice, ctx->stream));
+            JG_HIP(hipMemcpyAsync(d_nid, name_id, n_names * 4, hipMemcpyHostToDevice, ctx->stream));
+            JG_HIP(hipMemcpyAsync(d_off, off, (n_names + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+            if (nb) JG_HIP(hipMemcpyAsync(T.pool.as<uint8_t>() + T.pool_used, bytes, nb, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_names_put, dim3(blocks_for(n_names)), dim3(kBlock), 0, ctx->stream, T.view(), T.n_names, T.pool_used, d_nset, d_nid,
+                               d_off, n_names, T.kmask, T.salt);
+            JG_HIP(hipGetLastError());
+        }
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+        T.names_added(n_names, T.pool_used + nb, idb);
+    });
+}
+
+int jg_orset_wave_names(jg_orset* s, uint64_t* n_names, uint64_t* n_bytes, uint32_t* set, uint32_t* id, uint64_t* off, uint8_t* bytes) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
+        JG_REQUIRE(s && n_names && n_bytes, JG_EINVAL, "jg_orset_wave_names: NULL argument");
+        jg::ElemTable* T = jg::orset_elem_table(s, false);
+        const uint64_t n = T ? T->g1 - T->g0 : 0, nb = T ? T->p1 - T->p0 : 0;
+        *n_names = n;
+        *n_bytes = nb;
+        if (!set || n == 0) return;
+        JG_REQUIRE(id && off && (bytes || nb == 0), JG_EINVAL, "jg_orset_wave_names: NULL buffer");
+        jg_ctx* ctx = s->ctx;
+        jg::ensure_device(ctx);
+        const auto& o = T->nout;
+        // queued by the commit: wait for that copy; or the staging was reused since (a names_since pull): staged again
+        if (o.g0 != o.g1 && o.g0 == T->g0 && o.g1 == T->g1 && o.p0 == T->p0 && o.p1 == T->p1) JG_HIP(hipEventSynchronize(o.ev));
+        else names_stage_now(ctx, *T, T->g0, T->g1, T->p0, T->p1, "jg_orset_wave_names");
+        jg::NamesStaging(n, nb).copy_out(o.host, T->p0, set, id, off, bytes);
+    });
+}
+
+int jg_orset_names_since(jg_orset* s, uint64_t from, uint64_t* to, uint64_t* n_bytes, uint32_t* set, uint32_t* id, uint64_t* off, uint8_t* bytes) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(s);
+        JG_REQUIRE(s && to && n_bytes, JG_EINVAL, "jg_orset_names_since: NULL argument");
+        jg::ElemTable* T = jg::orset_elem_table(s, false);
+        const uint64_t total = T ? T->n_names : 0;
+        JG_REQUIRE(from <= total, JG_EINVAL, "jg_orset_names_since: from %llu past the %llu names held", (unsigned long long)from,
+                   (unsigned long long)total);
+        *to = total;
+        *n_bytes = 0;
+        const uint64_t n = total - from;
+        if (n == 0) return;
+        jg_ctx* ctx = s->ctx;
+        jg::ensure_device(ctx);
+        // A commit's new names take their pool bytes by atomics (not in name order), so the bytes of names
+        // [from, total) lie in the pool range that starts at the last mark at or before `from` (every name
+        // past a mark was made after it) and ends at pool_used.  One queue of copies into page-locked
+        // staging, one wait; kept for the second call of a size query + fill.
+        uint64_t pool0 = 0;
+        for (auto it = T->marks.rbegin(); it != T->marks.rend(); ++it)
+            if (it->first <= from) { pool0 = it->second; break; }
+        names_stage_now(ctx, *T, from, total, pool0, T->pool_used, "jg_orset_names_since");
+        const auto& o = T->nout;
+        *n_bytes = o.since_bytes;
+        if (!set) return;
+        JG_REQUIRE(id && off && (bytes || o.since_bytes == 0), JG_EINVAL, "jg_orset_names_since: NULL buffer");
+        jg::NamesStaging(n, o.since_pool1 - o.since_pool0).copy_out(o.host, o.since_pool0, set, id, off, bytes);
     });
 }
 

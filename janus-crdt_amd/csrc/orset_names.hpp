@@ -1,10 +1,14 @@
-// orset_names.hpp — the OR-Set element table's layout and probes, shared by the wave path (orset_wire.hip, which
-// owns and grows the table) and the by-name entry points (orset_names.hip).
+// orset_names.hpp — the OR-Set element table's layout and probes, and its host owner jg::ElemTable (orset_names.hip),
+// used by the wave path (orset_wire.hip), the by-name entry points (orset_names.hip), the encoder (orset_encode.hip)
+// and the reads by key name (query.hip).
 //
 // Element table (per store, first use): open addressing over 64-bit words (hash high half << 32 | name
 // index + 1; 0 = empty), names as (set, id, Clear generation, length, pool offset, hash), bytes in a pool.
 // A name is live while its generation equals its set's (a Clear bumps the set's generation).
 #pragma once
+
+#include <utility>
+#include <vector>
 
 #include "jg_internal.hpp"
 
@@ -86,17 +90,55 @@ __device__ __forceinline__ uint32_t tab_find(const Names& N, uint64_t key, uint3
 }  // namespace jgn
 
 namespace jg {
-// orset_wire.hip, for orset_names.hip.  The store's element table (created empty at first use) with room for
-// n_sets set ids, `incoming` more names and `pool_bytes` more pool bytes; growing rebuilds, it changes no content.
-struct NamesRef {
-    jgn::Names N;
-    uint64_t kmask, salt;         // name_key's mask (tests narrow it) and per-store salt
-    uint64_t n_names, pool_used;  // names in the log, pool bytes in use
-    uint64_t set_cap;             // sets set_gen / next_id hold
-    bool open;                    // a wave is open on the store
+// The store's element table on the host (orset_names.hip): the buffers Names views, their caps and counts, the names
+// log's marks, the range the last commit issued and its page-locked copy.  A member of jg_orset_wire (orset_wave.hpp),
+// created empty at the store's first use; growing rebuilds, it changes no content.
+struct ElemTable {
+    DevBuf tab, nset, nid, ngen, nlen, noff, nkey, pool, set_gen, next_id;
+    uint64_t tab_cap = 0, n_names = 0, name_cap = 0, pool_used = 0, pool_cap = 0, set_cap = 0;
+    DevBuf ikey, ival;  // (set, id) -> name index (Names::ikey), every name issued
+    uint64_t itab_cap = 0;
+    // an upper bound of every set's next element id (names_sync's next ids, plus every name a commit issued since);
+    // a fast check only: when it would refuse a wave it is first tightened to the exact max (tight_id_bound)
+    uint64_t id_bound = 0;
+    DevBuf idmax;  // the device max of next_id (tight_id_bound)
+    // string-hash mask: all bits; tests narrow it (JANUS_TEST_NAME_HASH_BITS) to force collisions
+    uint64_t kmask = ~0ull;
+    uint64_t salt = 0;  // name_key's per-store salt (random, drawn at first use)
+    // (names held, pool bytes used) after each commit / names_sync: where a names_since pull starts in the pool
+    std::vector<std::pair<uint64_t, uint64_t>> marks;
+    // ids issued by the last commit: names [g0, g1), pool bytes [p0, p1)
+    uint64_t g0 = 0, g1 = 0, p0 = 0, p1 = 0;
+    // the names a commit issued, copied into page-locked memory right behind the commit (one queue of copies,
+    // no wait): jg_orset_wave_names then waits on `ev` instead of staging them again (~0.6 ms of every
+    // ORSetWorkload wave, the host mirror reads them after each wave); layout: jg::NamesStaging
+    struct NamesOut {
+        uint8_t* host = nullptr;
+        size_t cap = 0;
+        hipEvent_t ev = nullptr;
+        uint64_t g0 = 0, g1 = 0, p0 = 0, p1 = 0;  // what the queued copy holds (g0 == g1: nothing queued)
+        // or what stage_now staged: names [since_from, since_to), pool [since_pool0, since_pool1)
+        uint64_t since_from = UINT64_MAX, since_to = 0, since_pool0 = 0, since_pool1 = 0, since_bytes = 0;
+    } nout;
+    std::vector<void*> retired;  // blocks the table outgrew (grow_keep), freed at the next idle point
+    ~ElemTable();
+
+    jgn::Names view() const;
+    void ensure_sets(jg_ctx* ctx, uint64_t n_sets);
+    // Room for `incoming` more names with `pool_bytes` more pool bytes; the table keeps load <= 1/2 (a
+    // rebuild keeps live names only).  (0, 0) on a store that never saw a name: empty tables.
+    void ensure_names(jg_ctx* ctx, uint64_t incoming, uint64_t pool_bytes);
+    uint64_t tight_id_bound(jg_ctx* ctx, DevBuf& cub_temp);
+    // n more names hold the log's next indices, the pool is used up to pool_used_now and no set's next id passes
+    // next_id_bound: a names_since pull can start here
+    void names_added(uint64_t n, uint64_t pool_used_now, uint64_t next_id_bound);
+    // A commit issued n_new names (in (set, first entry) order; the check ruled out running past 2^32 - 2): the
+    // issued range ends behind them, their page-locked copy is queued and the log marked.
+    void issue_names(jg_ctx* ctx, uint64_t n_new, uint64_t pool_used_now);
+    void no_names_issued() { g0 = g1 = n_names, p0 = p1 = pool_used; }  // the issued range: empty, at the log's end
 };
-NamesRef orset_names_ref(jg_orset* s, uint64_t n_sets, uint64_t incoming, uint64_t pool_bytes);
-// n names / nb pool bytes were appended behind n_names / pool_used (in log order) by kernels queued on the
-// context's stream, which the caller has synchronised; next ids grew to at most id_bound
-void orset_names_appended(jg_orset* s, uint64_t n, uint64_t nb, uint64_t id_bound);
+// orset_wire.hip: the store's table (nullptr while the store has no wire state, unless `create`), and whether a wave
+// is open on the store
+ElemTable* orset_elem_table(jg_orset* s, bool create);
+bool orset_wave_open(const jg_orset* s);
 }  // namespace jg

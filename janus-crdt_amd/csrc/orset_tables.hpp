@@ -1,5 +1,5 @@
-// orset_tables.hpp — the OR-Set wave's string and record tables, filled chunk by chunk (included by
-// orset_wire.hip only).
+// orset_tables.hpp — the OR-Set wave's string and record tables, filled chunk by chunk (kernels with internal
+// linkage: included by orset_wire.hip only).
 //
 // A wave's commit needs, for every element string of every set, the first entry that names it (its id is
 // issued in first-insertion order, ORSet.cs:255-279 / the Dictionaries' order), and, for every distinct tag
@@ -29,6 +29,10 @@
 // like messages).
 #pragma once
 
+#include "orset_wave.hpp"
+
+namespace {
+
 constexpr uint32_t kNoSid = 0xFFFFFFFFu;
 constexpr uint32_t kUnresolved = 0xFFFFFFFEu;  // sid_id of a string not looked up at claim time (ids stay below it)
 constexpr uint32_t kProbeCap = 256;  // probes before a table insert gives up (the wave falls back)
@@ -37,7 +41,7 @@ constexpr int kTabWaves = kBlock / 64;
 // The slots a table's inserts claimed, appended as they are claimed, so the commit walks these instead of the
 // whole table: kLists sub-lists of sub_cap entries (list j = the appending wave's message index % kLists, count n[j]) —
 // one counter took every wave's append and serialised the insert kernels (360 us per 32k-state chunk).
-constexpr uint32_t kLists = 16;
+using jg::kLists;  // 16 (orset_layouts.hpp: the bucket commit's arrays are sized by it)
 constexpr uint32_t kCountStride = 32;  // counters 256 B apart: atomics on one L2 line serialise
 // One slot per table entry: a probe's word and the field every probe that hits then updates share one line
 // (round 3 kept them in separate arrays: two scattered lines per entry / tag reference).
@@ -193,13 +197,7 @@ __device__ __forceinline__ void run_bytes(bool active, uint32_t key, unsigned lo
 // place in its (side, set) bucket.  place[slot] = {place or kDead, set | side << 31}.  A claim the counts cannot
 // hold (a set at or past cap, a string not looked up) raises *uncounted and the commit counts from the lists
 // (k_cb_count); so does a commit with a limit (claims past it are counted here).
-inline constexpr uint64_t cb_al(uint64_t b) { return (b + 255) & ~255ull; }
-// the four count arrays of cap + 1 entries: new strings, records (two sides) per set, then the strings' bytes
-inline constexpr uint64_t cb_counts_bytes(uint64_t cap) { return 3 * cb_al((cap + 1) * 4) + cb_al((cap + 1) * 8); }
-// places and bucket orders for every entry the two tables' lists can hold (orset_wire.hip buckets_of)
-inline constexpr uint64_t cb_items_bytes(uint64_t st_cap, uint64_t rt_cap) {
-    return 3 * cb_al((st_cap / 8) * kLists * 4 + 4) + 4 * cb_al((rt_cap / 8) * kLists * 4 + 4);
-}
+// (the four count arrays are one block: jg::carve_claims, orset_layouts.hpp)
 struct Claims {
     uint32_t* scnt;              // [cap + 1] new strings per set
     unsigned long long* sbytes;  // [cap + 1] their bytes
@@ -558,3 +556,5 @@ __global__ void k_ow_snext_ids(const unsigned long long* __restrict__ snk, uint6
     if (k + 1 < ns && snk[k + 1] != kNone && (uint32_t)(snk[k + 1] >> 32) == set) return;  // not the set's last new string
     N.next_id[set] += (uint32_t)(k + 1 - set_begin(snk, ns, set));
 }
+
+}  // namespace

@@ -29,41 +29,22 @@
 //                   lose their repeats through a hash table (a full-state message repeats most of its
 //                   set's records), are radix-sorted by (key, tag) and unioned into the store (orset.hip).
 //
-// Element table (per store, first use): open addressing over 64-bit words (hash high half << 32 | name
-// index + 1; 0 = empty), names as (set, id, Clear generation, length, pool offset, hash), bytes in a pool.
-// A name is live while its generation equals its set's (a Clear bumps the set's generation).
+// The element table (jg::ElemTable, a member of jg_orset_wire) is described and owned by orset_names.hpp / .hip.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <random>
-#include <vector>
 
-#include "launch.hpp"
-#include "orset_names.hpp"
-#include "wire_cursor.hpp"
+#include "orset_wave.hpp"    // the shared constants and types, jg_orset_wire
+#include "orset_group.hpp"   // k_ow_group: pass 1 with one wave per message
+#include "orset_tables.hpp"  // the wave's string and record tables, the radix commit's kernels from them
+#include "orset_commit.hpp"  // the bucket commit
 
 namespace {
 
-using namespace jgn;  // the element table's layout and probes (orset_names.hpp)
-
 using jgw::Cursor;
-using jgw::hexv;
 using jgw::GuidSink;
 using jgw::read_string;
-using jgw::put_utf8;
-
-constexpr int kBlock = 256;
-constexpr unsigned long long kNone = ~0ull;
-constexpr unsigned long long kKindState = 1, kKindInval = 2;  // error word = position << 2 | kind
-constexpr uint32_t kDead = 0xFFFFFFFFu;                        // id of an entry at or beyond the limit
-
-struct Tag16 { unsigned long long lo, hi; };
-
-using jg::blocks_for;
-using jg::ensure;
-using jg::grow_keep;
 
 // ---- string sinks: read_string feeds each unescaped UTF-8 byte to put(), esc() at a backslash -------
 __constant__ char kProp[4][16] = {"addSet", "removeSet", "nullAddGuid", "nullRemoveGuid"};
@@ -356,28 +337,6 @@ template <bool W, class V> __device__ __forceinline__ bool parse_orset(Cursor& c
     return true;
 }
 
-// Pass 1 writes each message's entries and tags into SPARSE regions addressed by its byte offset, so
-// no prefix over the wave is needed before parsing: an entry needs >= 5 payload bytes after an 11-byte
-// `{"addSet":{` prefix and a tag >= 38 bytes, so message m's entries fit in slots [ceil(off/4),
-// ceil(off_next/4)) and its tags in [ceil(off/32), ceil(off_next/32)) whatever the payload holds.
-// check() compacts them in commit order (k_ow_compact).
-constexpr uint64_t kEntryDiv = 4, kTagDiv = 32;
-
-struct Sparse {  // entry slots: sort key, string offset, length | side << 31, error position, the string's
-                 // first 8 bytes (zero past its end); tag slots
-    unsigned long long* key;
-    unsigned long long* noff;
-    unsigned long long* pfx;
-    uint32_t* meta;
-    uint32_t* pos;
-    uint32_t* set;             // the message's set
-    uint32_t* sid;             // the string's slot in the wave's string table (k_ow_strings)
-    unsigned long long* tref;  // null << 63 | side << 62 | the entry's parse-order ordinal in its message
-    Tag16* tval;
-    unsigned long long* trk;   // the record's identity without its tag (k_ow_rkeys): sid << 1 | side, or
-                               // 1 << 63 | set << 1 | side for a null tag set
-};
-
 struct ParseVis {
     Sparse S;
     uint64_t base, es, ts, kmask, salt;  // message byte offset; first entry / tag slot
@@ -450,8 +409,6 @@ __global__ __launch_bounds__(kBlock) void k_ow_parse(uint8_t* __restrict__ bytes
     na[m] = v.n_add | (v.rem_first ? 0x80000000u : 0u);
     err[m] = e;
 }
-
-#include "orset_group.hpp"
 
 __global__ void k_ow_rebase(uint64_t* __restrict__ off, uint64_t n, uint64_t base) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -579,44 +536,6 @@ __global__ void k_ow_first_bad(const unsigned long long* __restrict__ err, uint6
     if (m < n && err[m] != kNone) atomicMin(status, (unsigned long long)m);
 }
 
-// ---- element table (layout and probes: orset_names.hpp) -----------------------------------------------
-__global__ void k_names_rebuild(Names N, uint64_t n_names) {
-    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (g < n_names && N.gen[g] == N.set_gen[N.set[g]]) tab_insert(N, N.key[g], (uint32_t)g);
-}
-
-__global__ void k_itab_rebuild(Names N, uint64_t n_names) {
-    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (g < n_names) itab_insert(N, N.set[g], N.id[g], (uint32_t)g);
-}
-
-__global__ void k_sets_update(Names N, const uint32_t* __restrict__ set, const uint32_t* __restrict__ next, const uint8_t* __restrict__ cleared, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    if (cleared[i]) N.set_gen[set[i]] += 1;
-    N.next_id[set[i]] = next[i];
-}
-
-__global__ void k_names_put(Names N, uint64_t g0, uint64_t pool0, const uint32_t* __restrict__ nset, const uint32_t* __restrict__ nid,
-                            const uint64_t* __restrict__ off, uint64_t n, uint64_t kmask, uint64_t salt) {
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t g = g0 + i;
-    const uint32_t set = nset[i], len = (uint32_t)(off[i + 1] - off[i]);
-    const uint8_t* b = N.pool + pool0 + off[i];
-    uint64_t h = kFnvBasis;
-    for (uint32_t k = 0; k < len; ++k) h = (h ^ b[k]) * kFnvPrime;
-    const uint64_t key = name_key(set, h, salt) & kmask;
-    N.set[g] = set;
-    N.id[g] = nid[i];
-    N.gen[g] = N.set_gen[set];
-    N.len[g] = len;
-    N.off[g] = pool0 + off[i];
-    N.key[g] = key;
-    tab_insert(N, key, (uint32_t)g);
-    itab_insert(N, set, nid[i], (uint32_t)g);
-}
-
 // commit: each live group head looks its string up; new strings are marked (set << 32 | entry) at their
 // sorted index.  Marks, not a wave-aggregated counter: every wave that met a new string took a returning
 // atomic on one address, which serialised the grid there.
@@ -647,17 +566,6 @@ __global__ void k_ow_gather_new(const unsigned long long* __restrict__ newk, con
                                 const unsigned long long* __restrict__ count, unsigned long long* __restrict__ out) {
     const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j < *count) out[j] = newk[idx[j]];
-}
-
-__device__ __forceinline__ uint64_t set_begin(const unsigned long long* snk, uint64_t n, uint32_t set) {
-    uint64_t lo = 0, hi = n;
-    const unsigned long long x = (unsigned long long)set << 32;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (snk[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // New strings sorted by (set, first entry): the r-th new string of a set takes next_id + r.
@@ -722,10 +630,6 @@ __global__ void k_ow_rec_keys(Entries E, const uint32_t* __restrict__ mset, cons
     }
     rkey[t] = live ? ((unsigned long long)mset[m] << 32 | id) : kNone;
     rside[t] = (uint8_t)side;
-}
-
-__device__ __forceinline__ uint64_t rec_hash(unsigned long long k, const Tag16& g, uint32_t side) {
-    return mix64(k ^ mix64(g.lo + side) ^ (g.hi * 0x9E3779B97F4A7C15ull));
 }
 
 // Distinct records: insert-if-absent into an open-addressing table of record indices (exact compare on a
@@ -847,255 +751,10 @@ __global__ void k_gather_recs(const unsigned long long* __restrict__ dk, const T
     oo[i] = mint[(uint64_t)ds[p] * mstride];  // mstride: 1 (dedup table's array) or 4 (the record table's 16-byte slots)
 }
 
-#include "orset_tables.hpp"
-#include "orset_commit.hpp"
-
-
 int bits_for(uint64_t x) {
     int b = 1;
     while (b < 32 && (1ull << b) <= x) ++b;
     return b;
-}
-
-
-// ---- ORSetMsg.Encode on the device (jg_orset_encode_json; ORSet.cs:56-69, 305-308) ----------------------------
-// {"addSet":{"<e>":[<tags>],...},"removeSet":{...},"nullAddGuid":[<tags>],"nullRemoveGuid":[<tags>]} in
-// System.Text.Json's compact form: addSet elements in ascending element id (the add Dictionary's insertion
-// order), removeSet elements by their first tombstone's ord (when the element entered the remove Dictionary),
-// ties by id, tags by (ord, tag) (HashSet<Guid> insertion order), the null element's tags in the two lists.
-// Runs = the kept records of one (query, side, element); sections: 0 addSet, 1 removeSet, 2 nullAddGuid,
-// 3 nullRemoveGuid; seg = query * 4 + section.
-constexpr uint32_t kEncFixed = 65;                           // the five fixed texts of one ORSetMsg
-__constant__ const uint32_t kEncBefore[4] = {11, 26, 43, 63};  // fixed bytes before each section
-
-// JavaScriptEncoder.Default for a UTF-8 element string (host/wire.cpp escape): its escaped length, or its bytes.
-template <bool WRITE>
-__device__ uint32_t enc_escape(const uint8_t* s, uint32_t len, uint8_t* o) {
-    const char* HX = "0123456789ABCDEF";
-    uint32_t n = 0;
-    auto unit = [&](uint32_t u) {
-        if (WRITE) {
-            o[n] = '\\', o[n + 1] = 'u', o[n + 2] = HX[u >> 12 & 15], o[n + 3] = HX[u >> 8 & 15], o[n + 4] = HX[u >> 4 & 15], o[n + 5] = HX[u & 15];
-        }
-        n += 6;
-    };
-    for (uint32_t i = 0; i < len;) {
-        const uint32_t c = s[i];
-        if (c >= 0x80) {
-            const uint32_t k = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : 2;
-            uint32_t cp = c & (k == 4 ? 0x07 : k == 3 ? 0x0F : 0x1F);
-            for (uint32_t q = 1; q < k && i + q < len; ++q) cp = cp << 6 | (s[i + q] & 0x3F);
-            i += k;
-            if (cp >= 0x10000) {
-                unit(0xD800 | (cp - 0x10000) >> 10);
-                unit(0xDC00 | ((cp - 0x10000) & 0x3FF));
-            } else {
-                unit(cp);
-            }
-            continue;
-        }
-        ++i;
-        char e = 0;
-        if (c == '\\') e = '\\';
-        else if (c == '\b') e = 'b';
-        else if (c == '\t') e = 't';
-        else if (c == '\n') e = 'n';
-        else if (c == '\f') e = 'f';
-        else if (c == '\r') e = 'r';
-        if (e) {
-            if (WRITE) o[n] = '\\', o[n + 1] = e;
-            n += 2;
-        } else if (c < 0x20 || c == 0x7F || c == '"' || c == '&' || c == '\'' || c == '+' || c == '<' || c == '>' || c == '`') {
-            unit(c);
-        } else {
-            if (WRITE) o[n] = (uint8_t)c;
-            ++n;
-        }
-    }
-    return n;
-}
-
-__device__ __forceinline__ void enc_put(uint8_t* o, const char* s) {
-    while (*s) *o++ = (uint8_t)*s++;
-}
-
-// "<Guid D>" (38 bytes): b3 b2 b1 b0 - b5 b4 - b7 b6 - b8 b9 - b10..b15, lower-case hex
-__device__ __forceinline__ void enc_guid(uint8_t* o, unsigned long long lo, unsigned long long hi) {
-    const char* hx = "0123456789abcdef";
-    const int order[16] = {3, 2, 1, 0, 5, 4, 7, 6, 8, 9, 10, 11, 12, 13, 14, 15};
-    int p = 0;
-    o[p++] = '"';
-    for (int k = 0; k < 16; ++k) {
-        if (k == 4 || k == 6 || k == 8 || k == 10) o[p++] = '-';
-        const uint32_t b = (uint32_t)((order[k] < 8 ? lo >> (8 * order[k]) : hi >> (8 * (order[k] - 8))) & 0xFF);
-        o[p++] = hx[b >> 4];
-        o[p++] = hx[b & 15];
-    }
-    o[p] = '"';
-}
-
-struct EncRec {  // the gathered records (jg::orset_gather_sets)
-    const unsigned long long *key, *tlo, *thi;
-    const uint32_t *ord, *qs;
-};
-
-// run heads over the kept records kidx[0..K) (K on the device); positions >= K are padding
-__global__ void k_enc_heads(EncRec G, const uint32_t* __restrict__ kidx, const unsigned long long* __restrict__ K, uint64_t R, uint32_t* __restrict__ hf) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= R) return;
-    uint32_t h = 0;
-    if (j < *K) {
-        const uint32_t r = kidx[j];
-        h = j == 0 || G.key[kidx[j - 1]] != G.key[r] || G.qs[kidx[j - 1]] != G.qs[r];
-    }
-    hf[j] = h;
-}
-
-// per run (rid[j] - 1 = the run of kept record j): its first kept record, end, query / side / key; first ord reset
-__global__ void k_enc_runs(EncRec G, const uint32_t* __restrict__ kidx, const unsigned long long* __restrict__ K, const uint32_t* __restrict__ rid,
-                           uint32_t* __restrict__ rstart, uint32_t* __restrict__ rend, uint32_t* __restrict__ rfirst, unsigned long long* __restrict__ nruns) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const uint64_t k = *K;
-    if (j >= k) return;
-    const uint32_t run = rid[j] - 1;
-    if (j == 0 || rid[j - 1] != rid[j]) {
-        rstart[run] = (uint32_t)j;
-        rfirst[run] = 0xFFFFFFFFu;
-        if (j > 0) rend[run - 1] = (uint32_t)j;
-    }
-    if (j + 1 == k) {
-        rend[run] = (uint32_t)k;
-        *nruns = run + 1;
-    }
-}
-
-__global__ void k_enc_first_ord(EncRec G, const uint32_t* __restrict__ kidx, const unsigned long long* __restrict__ K, const uint32_t* __restrict__ rid,
-                                uint32_t* __restrict__ rfirst) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= *K) return;
-    const uint32_t o = G.ord[kidx[j]], run = rid[j] - 1;
-    if (rfirst[run] > o) atomicMin(rfirst + run, o);
-}
-
-__device__ __forceinline__ uint32_t enc_section(uint32_t qs, unsigned long long key) {
-    return ((uint32_t)key == JG_NULL_ELEM ? 2u : 0u) + (qs & 1u);
-}
-
-// run sort keys: seg << 32 | (removeSet ? first ord : 0), stable over runs in (query, side, id) order; padding ~0
-__global__ void k_enc_run_keys(EncRec G, const uint32_t* __restrict__ kidx, const uint32_t* __restrict__ rstart, const uint32_t* __restrict__ rfirst,
-                               const unsigned long long* __restrict__ nruns, uint64_t R, unsigned long long* __restrict__ rkey, uint32_t* __restrict__ rval) {
-    const uint64_t run = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (run >= R) return;
-    unsigned long long k = ~0ull;
-    if (run < *nruns) {
-        const uint32_t r = kidx[rstart[run]];
-        const uint32_t qs = G.qs[r], sec = enc_section(qs, G.key[r]);
-        const unsigned long long seg = (unsigned long long)(qs >> 1) * 4 + sec;
-        k = seg << 32 | (sec == 1 ? rfirst[run] : 0u);
-    }
-    rkey[run] = k;
-    rval[run] = (uint32_t)run;
-}
-
-// per run in output order (rank): its rank, record count, text length; the per-(query, section) bytes and first rank
-__global__ void k_enc_run_len(EncRec G, Names N, const uint32_t* __restrict__ kidx, const uint32_t* __restrict__ rstart, const uint32_t* __restrict__ rend,
-                              const unsigned long long* __restrict__ skey, const uint32_t* __restrict__ srun, const unsigned long long* __restrict__ nruns,
-                              uint64_t R, uint32_t* __restrict__ rrank, unsigned long long* __restrict__ cnt, unsigned long long* __restrict__ tlen,
-                              unsigned long long* __restrict__ qsec, uint32_t* __restrict__ sfirst, unsigned* __restrict__ err) {
-    const uint64_t rank = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (rank >= R) return;
-    if (rank >= *nruns) {
-        cnt[rank] = 0;
-        tlen[rank] = 0;
-        return;
-    }
-    const uint32_t run = srun[rank];
-    rrank[run] = (uint32_t)rank;
-    const uint32_t c = rend[run] - rstart[run];
-    const unsigned long long key = G.key[kidx[rstart[run]]];
-    const uint32_t seg = (uint32_t)(skey[rank] >> 32), sec = seg & 3;
-    unsigned long long len = 38ull * c + (c - 1);
-    if (sec < 2) {
-        const uint32_t g = itab_find(N, (uint32_t)(key >> 32), (uint32_t)key);
-        if (g == kNoName) {
-            atomicOr(err, 1u);
-        } else {
-            len += 1 + enc_escape<false>(N.pool + N.off[g], N.len[g], nullptr) + 3 + 1;
-            if (rank > 0 && (uint32_t)(skey[rank - 1] >> 32) == seg) len += 1;  // ',' before a later element
-        }
-    }
-    cnt[rank] = c;
-    tlen[rank] = len;
-    atomicAdd(qsec + seg, len);
-    if (sfirst[seg] > rank) atomicMin(sfirst + seg, (uint32_t)rank);
-}
-
-// record sort keys: output rank of its run << 32 | ord (stable: the store's tag order breaks ord ties); padding ~0
-__global__ void k_enc_rec_keys(EncRec G, const uint32_t* __restrict__ kidx, const unsigned long long* __restrict__ K, const uint32_t* __restrict__ rid,
-                               const uint32_t* __restrict__ rrank, uint64_t R, unsigned long long* __restrict__ key, uint32_t* __restrict__ val) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= R) return;
-    key[j] = j < *K ? (unsigned long long)rrank[rid[j] - 1] << 32 | G.ord[kidx[j]] : ~0ull;
-    val[j] = (uint32_t)j;
-}
-
-__global__ void k_enc_qlen(const unsigned long long* __restrict__ qsec, uint64_t n, unsigned long long* __restrict__ qlen) {
-    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q < n) qlen[q] = kEncFixed + qsec[4 * q] + qsec[4 * q + 1] + qsec[4 * q + 2] + qsec[4 * q + 3];
-    if (q == n) qlen[q] = 0;
-}
-
-// where a section's text starts in query q's state
-__device__ __forceinline__ unsigned long long enc_sec_at(const unsigned long long* qoff, const unsigned long long* qsec, uint32_t q, uint32_t sec) {
-    unsigned long long p = qoff[q] + kEncBefore[sec];
-    for (uint32_t s = 0; s < sec; ++s) p += qsec[4 * q + s];
-    return p;
-}
-
-__global__ void k_enc_fixed(const unsigned long long* __restrict__ qoff, const unsigned long long* __restrict__ qsec, uint64_t n, uint8_t* __restrict__ out) {
-    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= n) return;
-    uint8_t* o = out + qoff[q];
-    enc_put(o, "{\"addSet\":{");
-    enc_put(out + enc_sec_at(qoff, qsec, (uint32_t)q, 1) - 15, "},\"removeSet\":{");
-    enc_put(out + enc_sec_at(qoff, qsec, (uint32_t)q, 2) - 17, "},\"nullAddGuid\":[");
-    enc_put(out + enc_sec_at(qoff, qsec, (uint32_t)q, 3) - 20, "],\"nullRemoveGuid\":[");
-    enc_put(out + qoff[q + 1] - 2, "]}");
-}
-
-// each run's element header / closing bracket; rtags[rank] = where its first tag goes
-__global__ void k_enc_run_text(EncRec G, Names N, const uint32_t* __restrict__ kidx, const uint32_t* __restrict__ rstart,
-                               const unsigned long long* __restrict__ skey, const uint32_t* __restrict__ srun, const unsigned long long* __restrict__ nruns,
-                               const unsigned long long* __restrict__ rpos, const unsigned long long* __restrict__ tlen, const uint32_t* __restrict__ sfirst,
-                               const unsigned long long* __restrict__ qoff, const unsigned long long* __restrict__ qsec, unsigned long long* __restrict__ rtags,
-                               uint8_t* __restrict__ out) {
-    const uint64_t rank = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (rank >= *nruns) return;
-    const uint32_t seg = (uint32_t)(skey[rank] >> 32), sec = seg & 3, q = seg >> 2;
-    unsigned long long p = enc_sec_at(qoff, qsec, q, sec) + (rpos[rank] - rpos[sfirst[seg]]);
-    if (sec < 2) {
-        const unsigned long long key = G.key[kidx[rstart[srun[rank]]]];
-        const uint32_t g = itab_find(N, (uint32_t)(key >> 32), (uint32_t)key);
-        if (rank > 0 && (uint32_t)(skey[rank - 1] >> 32) == seg) out[p++] = ',';
-        out[p++] = '"';
-        p += enc_escape<true>(N.pool + N.off[g], N.len[g], out + p);
-        out[p++] = '"', out[p++] = ':', out[p++] = '[';
-        out[enc_sec_at(qoff, qsec, q, sec) + (rpos[rank] - rpos[sfirst[seg]]) + tlen[rank] - 1] = ']';
-    }
-    rtags[rank] = p;
-}
-
-// each record's tag text: ',' before every tag but a run's first
-__global__ void k_enc_rec_text(EncRec G, const uint32_t* __restrict__ kidx, const unsigned long long* __restrict__ K, const uint32_t* __restrict__ srec,
-                               const uint32_t* __restrict__ rid, const uint32_t* __restrict__ rrank, const unsigned long long* __restrict__ cpos,
-                               const unsigned long long* __restrict__ rtags, uint8_t* __restrict__ out) {
-    const uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= *K) return;
-    const uint32_t j = srec[p], rank = rrank[rid[j] - 1], r = kidx[j];
-    const unsigned long long k = p - cpos[rank];
-    unsigned long long at = rtags[rank] + 39 * k;
-    if (k) out[at - 1] = ',';
-    enc_guid(out + at, G.tlo[r], G.thi[r]);
 }
 
 }  // namespace
@@ -1119,95 +778,6 @@ __global__ void k_id_room_check(const uint32_t* __restrict__ next_id, const unsi
         if (cnt[st] && (uint64_t)next_id[st] + cnt[st] > (uint64_t)JG_NULL_ELEM - 1) atomicOr(over, 1ull);
 }
 
-// Element table + open wave of one store.
-struct jg_orset_wire {
-    // element table
-    jg::DevBuf tab, nset, nid, ngen, nlen, noff, nkey, pool, set_gen, next_id;
-    uint64_t tab_cap = 0, n_names = 0, name_cap = 0, pool_used = 0, pool_cap = 0, set_cap = 0;
-    jg::DevBuf ikey, ival;  // (set, id) -> name index (Names::ikey), every name issued
-    uint64_t itab_cap = 0;
-    // an upper bound of every set's next element id (names_sync's next ids, plus every name a commit issued since);
-    // a fast check only: when it would refuse a wave it is first tightened to the exact max (tight_id_bound)
-    uint64_t id_bound = 0;
-    jg::DevBuf idmax;  // the device max of next_id (tight_id_bound)
-    jg::DevBuf idcnt;  // per-set entry counts of the wave + two flag words (check_id_room's per-set tier)
-    // open wave: payload, offsets, set per message, per-message counts / errors
-    jg::DevBuf bytes, off, mset, ne, nt, na, err, eoff, toff, slow;  // slow: k_ow_group's per-message flags
-    // the wave's payload / offsets / set ids: the buffers above (jg_orset_wave_*), or a node's
-    // (csrc/node.hip: every kind's messages uploaded once, set id kSkipIdx for another kind's)
-    uint8_t* vbytes = nullptr;
-    uint64_t* voff = nullptr;
-    uint32_t* vmset = nullptr;
-    bool external = false;
-    uint64_t wn = 0, wnb = 0, cap_msgs = 0, cap_bytes = 0;
-    uint32_t max_set = 0;
-    bool open = false, checked = false, any_set = false;
-    uint64_t first_bad = kNone, n_ent = 0, n_tag = 0;
-    // entries, groups, tags, records
-    jg::DevBuf ekey, eval, enoff, emsg, emeta, epos, epfx, eset, skey, sval, hs, seg, impure, label, gid, eid;
-    jg::DevBuf sp_key, sp_noff, sp_pfx, sp_meta, sp_pos, sp_set, sp_sid, sp_tref, sp_tval, sp_trk;  // pass 1's sparse regions (by byte offset)
-    jg::DevBuf tref, tval, rkey, rside, dtab, dmin, dk[2], dt[2], ds[2], rk, rk2, perm[2], perm2[2];
-    jg::DevBuf newk, newv, snk, snv, status, cub;
-    jg::DevBuf cnk, fsel, fslot, fidx;  // commit: compacted new-string keys; dedup marks, slots, compacted indices
-    jg_orset* recs = nullptr;  // a committed wave's records, sorted (the merge source), reused
-    // ids issued by the last commit: names [g0, g1), pool bytes [p0, p1)
-    uint64_t g0 = 0, g1 = 0, p0 = 0, p1 = 0;
-    // string-hash mask: all bits; tests narrow it (JANUS_TEST_NAME_HASH_BITS) to force collisions
-    uint64_t kmask = ~0ull;
-    uint64_t salt = 0;  // name_key's per-store salt (random, drawn at first use)
-    // key bits the entry sort orders on; tests narrow it (JANUS_TEST_ENTRY_SORT_BITS) so runs mix full keys
-    int sort_bits = 32;
-    uint64_t resorts = 0;  // waves whose entries were sorted again on full keys (a long impure run)
-    // the wave's string and record tables (orset_tables.hpp), filled after each chunk's parse; `tables` =
-    // they are being filled this wave, `tables_ok` = the check found them complete (no overflow)
-    jg::DevBuf st_slot, st_list, rt_slot, rt_list, sid_id, ovf;  // 16-byte table slots (orset_tables.hpp); ovf: overflow word, sub-list counts
-    jg::DevBuf st_packed, rt_packed, loffs;  // the sub-lists packed for the commit
-    jg::DevBuf cb;                           // the bucket commit's places and bucket orders (orset_commit.hpp)
-    // the bucket counts the tables' claimants take (Claims, orset_tables.hpp): zeroed per wave for cb_cap sets,
-    // and one place per string / record slot
-    jg::DevBuf cbc, splace, rplace;
-    uint64_t cb_cap = 0;
-    uint64_t waves_claimed = 0;  // bucket commits whose counts came from the claims (tests read them)
-    // the check queued the commit's first steps ahead of its one read (lists packed, the claims' counts scanned:
-    // spec_h = k_cb_scan's eight status words), for a commit of the whole wave from the tables
-    bool spec = false;
-    unsigned long long spec_h[9] = {};  // [8]: k_cb_scatter_claimed's bound flag (orset_commit.hpp)
-    jg::DevBuf specst;
-    uint64_t waves_bucketed = 0;             // table commits that took the bucket path (tests read them)
-    uint64_t st_cap = 0, rt_cap = 0;     // slots in use this wave (a power of two, <= the allocations)
-    uint64_t st_alloc = 0, rt_alloc = 0, seen_s = 0, seen_r = 0;  // allocated slots; the last checked wave's distinct strings / records
-    bool tables = false, tables_ok = false;
-    std::vector<unsigned long long> lc;  // host copy of ovf (overflow word, sub-list counts) taken by the check
-    uint64_t waves_fast = 0, waves_sorted = 0;  // commits from the tables / by the sort path (tests read them)
-    uint64_t last_cnt[2] = {0, 0};  // distinct records (add, tombstone) the last commit merged: the next wave's estimate
-    // (names held, pool bytes used) after each commit / names_sync: where a names_since pull starts in the pool
-    std::vector<std::pair<uint64_t, uint64_t>> marks;
-    void mark() {
-        if (!marks.empty() && marks.back().first == n_names) return;
-        marks.emplace_back(n_names, pool_used);
-        if (marks.size() > 4096) marks.erase(marks.begin(), marks.begin() + 2048);
-    }
-    // the names a commit issued, copied into page-locked memory right behind the commit (one queue of copies,
-    // no wait): jg_orset_wave_names then waits on `ev` instead of five pageable copies and their syncs
-    // (~0.6 ms of every ORSetWorkload wave, the host mirror reads them after each wave)
-    struct NamesOut {
-        uint8_t* host = nullptr;
-        size_t cap = 0;
-        hipEvent_t ev = nullptr;
-        uint64_t g0 = 0, g1 = 0, p0 = 0, p1 = 0;  // what the queued copy holds (g0 == g1: nothing queued)
-        // or what jg_orset_names_since staged: names [since_from, since_to), pool [since_pool0, since_pool1)
-        uint64_t since_from = UINT64_MAX, since_to = 0, since_pool0 = 0, since_pool1 = 0, since_bytes = 0;
-    } nout;
-    jg::DevBuf enc_g, enc;       // jg_orset_encode_json: the gathered records, the encoder's arrays
-    std::vector<void*> retired;  // blocks the element table outgrew (grow_keep), freed at the next idle point
-    ~jg_orset_wire() {
-        for (void* p : retired) (void)hipFree(p);
-        if (nout.ev) (void)hipEventSynchronize(nout.ev);
-        if (nout.host) (void)hipHostFree(nout.host);
-        if (nout.ev) (void)hipEventDestroy(nout.ev);
-    }
-};
-
 namespace {
 
 jg_orset_wire* wire_of(jg_orset* s) {
@@ -1215,10 +785,10 @@ jg_orset_wire* wire_of(jg_orset* s) {
         s->wire = new jg_orset_wire();
         s->wire->status.alloc(128);
         std::random_device rd;
-        s->wire->salt = ((uint64_t)rd() << 32 ^ rd()) | 1;
+        s->wire->names.salt = ((uint64_t)rd() << 32 ^ rd()) | 1;
         if (const char* e = std::getenv("JANUS_TEST_NAME_HASH_BITS")) {
             const int bits = std::atoi(e);
-            if (bits > 0 && bits < 64) s->wire->kmask = (1ull << bits) - 1;
+            if (bits > 0 && bits < 64) s->wire->names.kmask = (1ull << bits) - 1;
         }
         if (const char* e = std::getenv("JANUS_TEST_ENTRY_SORT_BITS")) {
             const int bits = std::atoi(e);
@@ -1226,75 +796,6 @@ jg_orset_wire* wire_of(jg_orset* s) {
         }
     }
     return s->wire;
-}
-
-Names names_of(jg_orset_wire* w) {
-    return Names{w->tab.as<unsigned long long>(), w->tab_cap - 1, w->nset.as<uint32_t>(), w->nid.as<uint32_t>(), w->ngen.as<uint32_t>(),
-                 w->nlen.as<uint32_t>(), w->noff.as<unsigned long long>(), w->nkey.as<unsigned long long>(), w->pool.as<uint8_t>(),
-                 w->set_gen.as<uint32_t>(), w->next_id.as<uint32_t>(), w->ikey.as<unsigned long long>(), w->ival.as<uint32_t>(),
-                 w->itab_cap ? w->itab_cap - 1 : 0};
-}
-
-void ensure_sets(jg_ctx* ctx, jg_orset_wire* w, uint64_t n_sets) {
-    if (n_sets <= w->set_cap) return;
-    const uint64_t cap = std::max<uint64_t>(n_sets + n_sets / 2, 1024);
-    grow_keep(ctx, w->set_gen, cap * 4, w->set_cap * 4, true, &w->retired);
-    grow_keep(ctx, w->next_id, cap * 4, w->set_cap * 4, true, &w->retired);
-    w->set_cap = w->set_gen.bytes / 4;
-}
-
-// Room for `incoming` more names with `pool_bytes` more pool bytes; the table keeps load <= 1/2 (a
-// rebuild keeps live names only).
-void ensure_names(jg_ctx* ctx, jg_orset_wire* w, uint64_t incoming, uint64_t pool_bytes) {
-    const uint64_t total = w->n_names + incoming;
-    JG_REQUIRE(total < 0xFFFFFFF0ull, JG_ESTATE, "OR-Set element table: more than 2^32 names");
-    if (total > w->name_cap) {
-        const uint64_t cap = std::max<uint64_t>(total + total / 2, 4096);
-        grow_keep(ctx, w->nset, cap * 4, w->n_names * 4, false, &w->retired);
-        grow_keep(ctx, w->nid, cap * 4, w->n_names * 4, false, &w->retired);
-        grow_keep(ctx, w->ngen, cap * 4, w->n_names * 4, false, &w->retired);
-        grow_keep(ctx, w->nlen, cap * 4, w->n_names * 4, false, &w->retired);
-        grow_keep(ctx, w->noff, cap * 8, w->n_names * 8, false, &w->retired);
-        grow_keep(ctx, w->nkey, cap * 8, w->n_names * 8, false, &w->retired);
-        w->name_cap = std::min({w->nset.bytes / 4, w->nid.bytes / 4, w->ngen.bytes / 4, w->nlen.bytes / 4, w->noff.bytes / 8, w->nkey.bytes / 8});
-    }
-    if (w->pool_used + pool_bytes > w->pool_cap) {  // x1.5: a pool grown to the exact need grew again every wave
-        grow_keep(ctx, w->pool, std::max<uint64_t>({w->pool_used + pool_bytes, w->pool_cap + w->pool_cap / 2, 1 << 20}), w->pool_used, false,
-                  &w->retired);
-        w->pool_cap = w->pool.bytes;
-    }
-    if (w->tab_cap == 0 || 2 * total > w->tab_cap) {
-        const uint64_t cap = jg::pow2_at_least(4 * total, 1024);
-        if (w->tab.p) {  // retired, not freed (see grow_keep)
-            w->retired.push_back(w->tab.p);
-            w->tab.p = nullptr;
-            w->tab.bytes = 0;
-        }
-        w->tab.alloc(cap * 8);
-        w->tab_cap = cap;
-        JG_HIP(hipMemsetAsync(w->tab.p, 0, cap * 8, ctx->stream));
-        if (w->n_names) {
-            hipLaunchKernelGGL(k_names_rebuild, dim3(blocks_for(w->n_names)), dim3(kBlock), 0, ctx->stream, names_of(w), w->n_names);
-            JG_HIP(hipGetLastError());
-        }
-    }
-    if (w->itab_cap == 0 || 2 * total > w->itab_cap) {  // the (set, id) index: every name, load <= 1/2
-        const uint64_t cap = jg::pow2_at_least(4 * total, 1024);
-        for (jg::DevBuf* b : {&w->ikey, &w->ival})
-            if (b->p) {
-                w->retired.push_back(b->p);
-                b->p = nullptr;
-                b->bytes = 0;
-            }
-        w->ikey.alloc(cap * 8);
-        w->ival.alloc(cap * 4);
-        w->itab_cap = cap;
-        JG_HIP(hipMemsetAsync(w->ikey.p, 0, cap * 8, ctx->stream));
-        if (w->n_names) {
-            hipLaunchKernelGGL(k_itab_rebuild, dim3(blocks_for(w->n_names)), dim3(kBlock), 0, ctx->stream, names_of(w), w->n_names);
-            JG_HIP(hipGetLastError());
-        }
-    }
 }
 
 unsigned long long* status_words(jg_orset_wire* w) { return w->status.as<unsigned long long>(); }
@@ -1305,89 +806,26 @@ void read_words(jg_ctx* ctx, const unsigned long long* d, unsigned long long* h,
     std::memcpy(h, jg::pin_at(ctx, 0), n * 8);
 }
 
-// Page-locked layout of a names copy: set [n] u32 | id [n] u32 | len [n] u32 | pad | pool offset [n] u64 | pool bytes.
-size_t names_out_bytes(uint64_t n, uint64_t nb) { return jg::round_up(n * 12, 16) + n * 8 + nb; }
-
-// Queue the copy of the names [g0, g1) / pool bytes [p0, p1) the last commit issued (async on ctx->stream).
-void queue_names(jg_ctx* ctx, jg_orset_wire* w) {
-    auto& o = w->nout;
-    o.g0 = o.g1 = 0;
-    o.since_from = UINT64_MAX;  // the staging is about to hold this commit's names
-    const uint64_t n = w->g1 - w->g0, nb = w->p1 - w->p0;
-    if (n == 0) return;
-    const size_t need = names_out_bytes(n, nb);
-    if (o.cap < need) {
-        if (o.ev) JG_HIP(hipEventSynchronize(o.ev));  // no earlier copy may still land in the old block
-        if (o.host) JG_HIP(hipHostFree(o.host));
-        o.host = nullptr;
-        o.cap = 0;
-        void* p = nullptr;
-        JG_HIP(hipHostMalloc(&p, need + need / 2, hipHostMallocDefault));
-        o.host = static_cast<uint8_t*>(p);
-        o.cap = need + need / 2;
-    }
-    if (!o.ev) JG_HIP(hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
-    // on the copy queue (idle once a wave's uploads are in), behind the commit's kernels: the record sorts and
-    // the union behind them on ctx->stream do not wait for these copies.  The names arrays are only ever
-    // appended to past g1 / p1 or reallocated, and a reallocation (grow_keep) syncs the copy queue first.
-    hipStream_t q = ctx->copy ? ctx->copy : ctx->stream;
-    if (q != ctx->stream) {
-        JG_HIP(hipEventRecord(o.ev, ctx->stream));
-        JG_HIP(hipStreamWaitEvent(q, o.ev, 0));
-    }
-    uint8_t* h = o.host;
-    JG_HIP(hipMemcpyAsync(h, w->nset.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, q));
-    JG_HIP(hipMemcpyAsync(h + n * 4, w->nid.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, q));
-    JG_HIP(hipMemcpyAsync(h + n * 8, w->nlen.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, q));
-    const size_t po = jg::round_up(n * 12, 16);
-    JG_HIP(hipMemcpyAsync(h + po, w->noff.as<unsigned long long>() + w->g0, n * 8, hipMemcpyDeviceToHost, q));
-    if (nb) JG_HIP(hipMemcpyAsync(h + po + n * 8, w->pool.as<uint8_t>() + w->p0, nb, hipMemcpyDeviceToHost, q));
-    JG_HIP(hipEventRecord(o.ev, q));
-    o.g0 = w->g0, o.g1 = w->g1, o.p0 = w->p0, o.p1 = w->p1;
-}
-
-// id_bound sums the names every commit issued over ALL sets, so on a store with many sets it grows far past any
-// one set's next id and would refuse waves every set still has room for.  Before refusing, the
-// bound is tightened to the exact largest per-set next id (one device max over the sets, one round trip); the
-// check then asks whether that set plus every name of the wave could pass 2^32 - 2 — still conservative (all
-// names counted against the fullest set), exact in the case that matters (a set near its limit).
-uint64_t tight_id_bound(jg_ctx* ctx, jg_orset_wire* w) {
-    if (w->set_cap == 0) return w->id_bound = 0;
-    ensure(w->idmax, 16);
-    const uint32_t* nx = w->next_id.as<uint32_t>();
-    const int n_sets = jg::cub_count(w->set_cap, "sets");
-    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
-        return hipcub::DeviceReduce::Max(temp, bytes, nx, w->idmax.as<uint32_t>(), n_sets, ctx->stream);
-    });
-    jg::pin_get(ctx, 0, w->idmax.p, 4);
-    jg::pin_sync(ctx);
-    uint32_t mx;
-    std::memcpy(&mx, jg::pin_at(ctx, 0), 4);
-    return w->id_bound = mx;
-}
-
 // A wave must not take any set's element ids past JG_NULL_ELEM - 1 (checked before anything commits).  Three
 // tiers: id_bound + every name of the wave (host, free); the exact largest next id + every name (one device max);
 // then per set, that set's next id + the wave's entries naming it (two small kernels, one round trip) — exact
 // per set up to repeated strings, so one set synced near its limit does not block waves on the others.
 void check_id_room(jg_ctx* ctx, jg_orset_wire* w, uint64_t incoming, uint64_t n_msgs) {
-    if (w->id_bound + incoming <= JG_NULL_ELEM - 1) return;
-    if (tight_id_bound(ctx, w) + incoming <= JG_NULL_ELEM - 1) return;
-    ensure(w->idcnt, (w->set_cap + 2) * 8);
+    if (w->names.id_bound + incoming <= JG_NULL_ELEM - 1) return;
+    if (w->names.tight_id_bound(ctx, w->cub) + incoming <= JG_NULL_ELEM - 1) return;
+    ensure(w->idcnt, (w->names.set_cap + 2) * 8);
     auto* cnt = w->idcnt.as<unsigned long long>();
-    JG_HIP(hipMemsetAsync(cnt, 0, (w->set_cap + 2) * 8, ctx->stream));
+    JG_HIP(hipMemsetAsync(cnt, 0, (w->names.set_cap + 2) * 8, ctx->stream));
     if (n_msgs)
         hipLaunchKernelGGL(k_id_room_count, dim3(blocks_for(n_msgs)), dim3(kBlock), 0, ctx->stream, w->ne.as<unsigned long long>(), w->vmset, n_msgs,
-                           w->set_cap, cnt);
-    hipLaunchKernelGGL(k_id_room_check, dim3(blocks_for(w->set_cap)), dim3(kBlock), 0, ctx->stream, w->next_id.as<uint32_t>(), cnt, w->set_cap,
-                       cnt + w->set_cap);
+                           w->names.set_cap, cnt);
+    hipLaunchKernelGGL(k_id_room_check, dim3(blocks_for(w->names.set_cap)), dim3(kBlock), 0, ctx->stream, w->names.next_id.as<uint32_t>(), cnt, w->names.set_cap,
+                       cnt + w->names.set_cap);
     JG_HIP(hipGetLastError());
-    jg::pin_get(ctx, 0, cnt + w->set_cap, 16);
-    jg::pin_sync(ctx);
     unsigned long long h[2];
-    std::memcpy(h, jg::pin_at(ctx, 0), 16);
+    read_words(ctx, cnt + w->names.set_cap, h, 2);
     JG_REQUIRE(h[0] == 0 && h[1] == 0, JG_ESTATE, "jg_orset_wave: a set's element ids would pass an OR-Set's 2^32 - 2 ids in this wave (largest next id %llu)",
-               (unsigned long long)w->id_bound);
+               (unsigned long long)w->names.id_bound);
 }
 
 template <class K, class V>
@@ -1471,14 +909,23 @@ RecTab rec_tab(jg_orset_wire* w) {
                   w->ovf.as<unsigned long long>() + (1 + kLists) * kCountStride, w->rt_cap / 8};
 }
 
+// The bytes of the claims' count block for `cap` sets and of the bucket commit's block at this wave's table sizes.
+size_t claims_bytes(uint64_t cap) {
+    Claims C{};
+    return jg::carve_claims(cap, nullptr, C);
+}
+size_t items_bytes(const jg_orset_wire* w) {
+    Buckets B{};
+    return jg::carve_items(w->st_cap, w->rt_cap, nullptr, B);
+}
+
 // A wave opens: size and clear its string / record tables (queued on the compute stream, ahead of the first
 // chunk's parse).  A compact entry needs >= 43 payload bytes ("":["<guid>"]) and a tag reference >= 38, so
 // nbytes / 40 and nbytes / 38 bound the distinct strings and records; a streamed wave sized by its message
 // count alone gets 16 strings / 32 records per message and falls back to the sort path if it holds more.
-// JANUS_ORSET_TAIL=sort runs the sort path alone (read per wave: tests switch it).
 void tables_begin(jg_ctx* ctx, jg_orset_wire* w, uint64_t n_msgs, uint64_t nbytes) {
-    const char* e = std::getenv("JANUS_ORSET_TAIL");
-    w->tables = !(e && std::strcmp(e, "sort") == 0) && nbytes / kEntryDiv + 2 < 0xFFFFFFFFull && nbytes / kTagDiv + 2 < 0xFFFFFFFFull;
+    w->knobs = WaveKnobs::from_env();
+    w->tables = w->knobs.tail != WaveKnobs::kTailSort && nbytes / kEntryDiv + 2 < 0xFFFFFFFFull && nbytes / kTagDiv + 2 < 0xFFFFFFFFull;
     w->tables_ok = false;
     if (!w->tables) return;
     const uint64_t lim = 1ull << 30;  // slot ids < 2^31 (k_ow_strings packs the side above them); hipcub counts in int
@@ -1488,7 +935,7 @@ void tables_begin(jg_ctx* ctx, jg_orset_wire* w, uint64_t n_msgs, uint64_t nbyte
     // (~0.4M distinct strings and records) 16M-slot tables, ~0.5 GB probed at random, every probe a miss in
     // the 256 MB MALL.  A wave past the smaller tables' room overflows into the sort path (correct, slower) and
     // the next one sizes from the bound again.  JANUS_ORSET_TAIL=tables (no fall-back) keeps the bound.
-    const bool strict = e && std::strcmp(e, "tables") == 0;
+    const bool strict = w->knobs.tail == WaveKnobs::kTailTables;
     const uint64_t want_s = w->seen_s && !strict ? std::min(bound_s, 4 * w->seen_s + 65536) : bound_s;
     const uint64_t want_r = w->seen_r && !strict ? std::min(bound_r, 4 * w->seen_r + 65536) : bound_r;
     const uint64_t sc = std::min(lim, jg::pow2_at_least(std::max<uint64_t>(4096, want_s), 1024));
@@ -1520,23 +967,18 @@ void tables_begin(jg_ctx* ctx, jg_orset_wire* w, uint64_t n_msgs, uint64_t nbyte
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemsetAsync(w->ovf.p, 0, (1 + 2 * kLists) * kCountStride * 8, ctx->stream));  // overflow, uncounted, sub-list counts
     // the claim-time bucket counts: one per set the store knows (a set past them sends the commit to k_cb_count)
-    const uint64_t cap = std::min<uint64_t>(0x7FFFFFF0ull, std::max<uint64_t>({w->cb_cap, w->set_cap, (uint64_t)w->max_set + 1, 1024}));
+    const uint64_t cap = std::min<uint64_t>(0x7FFFFFF0ull, std::max<uint64_t>({w->cb_cap, w->names.set_cap, (uint64_t)w->max_set + 1, 1024}));
     if (cap > w->cb_cap) {
-        w->cbc.alloc(cb_counts_bytes(cap));
+        w->cbc.alloc(claims_bytes(cap));
         w->cb_cap = cap;
     }
-    JG_HIP(hipMemsetAsync(w->cbc.p, 0, cb_counts_bytes(w->cb_cap), ctx->stream));
-    ensure(w->cb, cb_items_bytes(w->st_cap, w->rt_cap));
+    JG_HIP(hipMemsetAsync(w->cbc.p, 0, claims_bytes(w->cb_cap), ctx->stream));
+    ensure(w->cb, items_bytes(w));
 }
 
 Claims claims_of(jg_orset_wire* w) {
     Claims C{};
-    char* p = w->cbc.as<char>();
-    const uint64_t c4 = cb_al((w->cb_cap + 1) * 4);
-    C.scnt = reinterpret_cast<uint32_t*>(p);
-    C.rcnt[0] = reinterpret_cast<uint32_t*>(p + c4);
-    C.rcnt[1] = reinterpret_cast<uint32_t*>(p + 2 * c4);
-    C.sbytes = reinterpret_cast<unsigned long long*>(p + 3 * c4);
+    jg::carve_claims(w->cb_cap, w->cbc.p, C);
     C.splace = w->splace.as<uint2>();
     C.rplace = w->rplace.as<uint2>();
     C.uncounted = w->ovf.as<unsigned long long>() + 1;  // ovf word 1: zeroed with the overflow word, read by the check
@@ -1547,22 +989,9 @@ Claims claims_of(jg_orset_wire* w) {
 // The bucket commit's arrays: the claims' counts, then places and bucket orders for every entry the two tables'
 // lists can hold this wave (w->cb, sized by tables_begin, so the check can queue the scatter before its read).
 Buckets buckets_of(jg_orset_wire* w) {
-    const Claims C = claims_of(w);
     Buckets B{};
-    B.scnt = C.scnt;  // the counts: cb_cap + 1 entries each (the scan covers the wave's n_sets + 1)
-    B.rcnt[0] = C.rcnt[0];
-    B.rcnt[1] = C.rcnt[1];
-    B.sbytes = C.sbytes;
-    const uint64_t s4 = cb_al((w->st_cap / 8) * kLists * 4 + 4), r4 = cb_al((w->rt_cap / 8) * kLists * 4 + 4);
-    char* q = w->cb.as<char>();
-    B.spos = reinterpret_cast<uint32_t*>(q);
-    B.sset = reinterpret_cast<uint32_t*>(q + s4);
-    B.sitem = reinterpret_cast<uint32_t*>(q + 2 * s4);
-    q += 3 * s4;
-    B.rpos = reinterpret_cast<uint32_t*>(q);
-    B.rset = reinterpret_cast<uint32_t*>(q + r4);
-    B.ritem[0] = reinterpret_cast<uint32_t*>(q + 2 * r4);
-    B.ritem[1] = reinterpret_cast<uint32_t*>(q + 3 * r4);
+    jg::carve_claims(w->cb_cap, w->cbc.p, B);  // the counts: cb_cap + 1 entries each (the scan covers the wave's n_sets + 1)
+    jg::carve_items(w->st_cap, w->rt_cap, w->cb.p, B);
     B.n_sets = (uint32_t)std::min<uint64_t>((uint64_t)w->max_set + 1, 0xFFFFFFFFull);
     return B;
 }
@@ -1573,11 +1002,11 @@ void launch_tables(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
     auto* ovf = w->ovf.as<unsigned long long>();
     // the element table and the sets' generation words as they stand (both only change at a commit); a wave
     // before the first commit has no table yet: every string is resolved by the commit
-    const uint32_t set_lim = w->tab_cap ? (uint32_t)std::min<uint64_t>(w->set_cap, 0xFFFFFFFFull) : 0u;
+    const uint32_t set_lim = w->names.tab_cap ? (uint32_t)std::min<uint64_t>(w->names.set_cap, 0xFFFFFFFFull) : 0u;
     const dim3 grid(blocks_for(m1 - m0, kTabWaves));  // one message per wave
     const dim3 grid_m(blocks_for(m1 - m0, kTabWaves * kMsgsPerWave));  // kMsgsPerWave messages per wave
     hipLaunchKernelGGL(k_ow_strings, grid, dim3(kBlock), 0, ctx->stream, S, w->voff, w->vmset, w->vbytes, w->ne.as<unsigned long long>(),
-                       w->na.as<uint32_t>(), m0, m1, str_tab(w), w->err.as<unsigned long long>(), ovf, names_of(w), set_lim,
+                       w->na.as<uint32_t>(), m0, m1, str_tab(w), w->err.as<unsigned long long>(), ovf, w->names.view(), set_lim,
                        w->sid_id.as<uint32_t>(), claims_of(w));
     hipLaunchKernelGGL(k_ow_rkeys, grid_m, dim3(kBlock), 0, ctx->stream, S, w->voff, w->vmset, w->nt.as<unsigned long long>(), m0, m1);
     hipLaunchKernelGGL(k_ow_rins, grid_m, dim3(kBlock), 0, ctx->stream, S, w->voff, w->vmset, w->nt.as<unsigned long long>(), m0, m1, rec_tab(w), ovf,
@@ -1585,18 +1014,17 @@ void launch_tables(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
     JG_HIP(hipGetLastError());
 }
 
-// One wave per message (k_ow_group, orset_group.hpp), then the serial parse of the messages it left;
-// JANUS_ORSET_PARSE=serial runs the serial parse alone, =group the group parse alone (read per chunk: tests
-// switch it).
+// One wave per message (k_ow_group, orset_group.hpp), then the serial parse of the messages it left
+// (WaveKnobs::parse, read per chunk, runs one of them alone).
 void launch_parse(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
     if (m1 <= m0) return;
-    const char* e = std::getenv("JANUS_ORSET_PARSE");
-    const bool serial = e && std::strcmp(e, "serial") == 0, strict = e && std::strcmp(e, "group") == 0;
+    w->knobs = WaveKnobs::from_env();
+    const bool serial = w->knobs.parse == WaveKnobs::kParseSerial, strict = w->knobs.parse == WaveKnobs::kParseGroup;
     uint8_t* slow = nullptr;
     if (!serial) {
         slow = w->slow.as<uint8_t>();
         hipLaunchKernelGGL(k_ow_group, dim3(blocks_for(m1 - m0, kOgWaves)), dim3(kBlock), 0, ctx->stream, w->vbytes, w->voff,
-                           w->vmset, m0, m1, sparse_of(w), w->kmask, w->salt, w->ne.as<unsigned long long>(), w->nt.as<unsigned long long>(),
+                           w->vmset, m0, m1, sparse_of(w), w->names.kmask, w->names.salt, w->ne.as<unsigned long long>(), w->nt.as<unsigned long long>(),
                            w->na.as<uint32_t>(), w->err.as<unsigned long long>(), slow);
         JG_HIP(hipGetLastError());
     }
@@ -1605,7 +1033,7 @@ void launch_parse(jg_ctx* ctx, jg_orset_wire* w, uint64_t m0, uint64_t m1) {
                            w->nt.as<unsigned long long>(), w->na.as<uint32_t>(), w->err.as<unsigned long long>());
     else
         hipLaunchKernelGGL(k_ow_parse, dim3(blocks_for(m1 - m0)), dim3(kBlock), 0, ctx->stream, w->vbytes, w->voff, w->vmset, m0, m1,
-                           sparse_of(w), w->kmask, w->salt, w->ne.as<unsigned long long>(), w->nt.as<unsigned long long>(), w->na.as<uint32_t>(),
+                           sparse_of(w), w->names.kmask, w->names.salt, w->ne.as<unsigned long long>(), w->nt.as<unsigned long long>(), w->na.as<uint32_t>(),
                            w->err.as<unsigned long long>(), slow);
     JG_HIP(hipGetLastError());
     if (w->tables) launch_tables(ctx, w, m0, m1);
@@ -1620,17 +1048,16 @@ double g_tmark[6] = {};
 // use them (a limit, an uncounted claim, an overflowed table, JANUS_ORSET_COMMIT=radix / count) repacks or
 // recounts as before; this only writes the packed lists, the counts and specst.
 void spec_commit_prep(jg_ctx* ctx, jg_orset_wire* w) {
-    const char* e = std::getenv("JANUS_ORSET_COMMIT");
     const uint64_t n_sets = (uint64_t)w->max_set + 1;
-    const char* sp = std::getenv("JANUS_ORSET_SPEC");  // =0: the commit packs and scans after the check (A/B runs)
-    w->spec = !(e && (std::strcmp(e, "radix") == 0 || std::strcmp(e, "count") == 0)) && !(sp && std::strcmp(sp, "0") == 0) && n_sets <= w->cb_cap;
+    const auto commit = w->knobs.commit;
+    w->spec = commit != WaveKnobs::kCommitRadix && commit != WaveKnobs::kCommitCount && w->knobs.spec && n_sets <= w->cb_cap;
     if (!w->spec) return;
     const StrTab ST = str_tab(w);
     const RecTab RT = rec_tab(w);
     const uint64_t cs = kLists * ST.sub_cap, cr = kLists * RT.sub_cap;
     // buffers sized by tables_begin: an allocation here (hipFree / hipMalloc behind the uploads) cost ~0.5 ms
     if (w->st_packed.bytes < cs * 4 + 4 || w->rt_packed.bytes < cr * 4 + 4 || !w->loffs.p || !w->specst.p ||
-        w->cb.bytes < cb_items_bytes(w->st_cap, w->rt_cap)) {
+        w->cb.bytes < items_bytes(w)) {
         w->spec = false;
         return;
     }
@@ -1656,10 +1083,59 @@ void spec_commit_prep(jg_ctx* ctx, jg_orset_wire* w) {
     JG_HIP(hipGetLastError());
 }
 
+// The smallest message with an error word into status word 0 (kNone: none).
+void launch_first_bad(jg_ctx* ctx, jg_orset_wire* w) {
+    unsigned long long* st = status_words(w);
+    JG_HIP(hipMemsetAsync(st, 0xFF, 8, ctx->stream));
+    hipLaunchKernelGGL(k_ow_first_bad, dim3(blocks_for(w->wn)), dim3(kBlock), 0, ctx->stream, w->err.as<unsigned long long>(), w->wn, st);
+    JG_HIP(hipGetLastError());
+}
+
+// The check's verdict on its first bad message m (kNone: none, JG_OK): m with its error word's kind and byte
+// position recorded for the caller's message (one 8-byte read, on a rejected wave only); returns m's code.
+int note_bad(jg_ctx* ctx, jg_orset_wire* w, uint64_t m) {
+    if (m == kNone) return JG_OK;
+    unsigned long long e;
+    JG_HIP(hipMemcpyAsync(&e, w->err.as<unsigned long long>() + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+    JG_HIP(hipStreamSynchronize(ctx->stream));
+    w->first_bad = m;
+    w->bad_kind = e & 3;
+    w->bad_pos = e >> 2;
+    return w->bad_kind == kKindState ? JG_ESTATE : JG_EINVAL;
+}
+
+// The wave's n_ent entries grouped by (set, string): sorted (stable) on the low sort_bits of their keys, each run
+// of equal bits linked (k_ow_link marks a run that mixes strings impure) and every entry labelled with the first
+// entry of its string; an impure run is scanned for at most impure_scan entries, past which status word 1 is
+// raised (k_ow_label) — UINT32_MAX: no limit, the word is left alone.
+void group_entries(jg_ctx* ctx, jg_orset_wire* w, int sort_bits, uint32_t impure_scan) {
+    const uint64_t ne = w->n_ent;
+    const Entries E = entries_of(w);
+    sort_pairs(ctx, w, E.key, w->skey.as<unsigned long long>(), E.val, w->sval.as<uint32_t>(), ne, sort_bits);
+    const unsigned long long run_mask = sort_bits >= 64 ? ~0ull : (1ull << sort_bits) - 1;
+    hipLaunchKernelGGL(k_ow_head, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, w->skey.as<unsigned long long>(), ne, run_mask,
+                       w->hs.as<uint32_t>());
+    JG_HIP(hipGetLastError());
+    const int n_ent = jg::cub_count(ne, "entries");
+    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceScan::InclusiveScan(temp, bytes, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), n_ent, ctx->stream);
+    });
+    JG_HIP(hipMemsetAsync(w->impure.p, 0, ne, ctx->stream));
+    hipLaunchKernelGGL(k_ow_link, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes, w->sval.as<uint32_t>(),
+                       w->seg.as<uint32_t>(), ne, w->impure.as<uint8_t>());
+    JG_HIP(hipGetLastError());
+    if (impure_scan != UINT32_MAX) JG_HIP(hipMemsetAsync(status_words(w) + 1, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_ow_label, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes, w->sval.as<uint32_t>(),
+                       w->seg.as<uint32_t>(), w->impure.as<uint8_t>(), ne, w->label.as<uint32_t>(), w->err.as<unsigned long long>(), impure_scan,
+                       status_words(w) + 1);
+    JG_HIP(hipGetLastError());
+}
+
 // Passes 2 + grouping over the whole wave; sets w->first_bad.  Returns the first bad message's code.
 int check_wave(jg_orset* s, jg_orset_wire* w) {
     jg_ctx* ctx = s->ctx;
     const uint64_t n = w->wn;
+    w->knobs = WaveKnobs::from_env();  // the check queues the commit's first steps (spec_commit_prep)
     w->checked = true;
     w->first_bad = kNone;
     w->n_ent = w->n_tag = 0;
@@ -1667,9 +1143,7 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
     if (n == 0) return JG_OK;
     if (w->tables) {  // the chunks filled the tables (and reported repeated names): the first bad message is all
         unsigned long long* st = status_words(w);  // that is left, unless a table overflowed
-        JG_HIP(hipMemsetAsync(st, 0xFF, 8, ctx->stream));
-        hipLaunchKernelGGL(k_ow_first_bad, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, w->err.as<unsigned long long>(), n, st);
-        JG_HIP(hipGetLastError());
+        launch_first_bad(ctx, w);
         spec_commit_prep(ctx, w);
         // the overflow word and the tables' sub-list counts (the commit's) come back with the first bad message,
         // and with them the claims' bucket totals: one round trip, page-locked
@@ -1682,16 +1156,13 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
         g_tmark[0] = jg::now_us();
         std::memcpy(w->lc.data(), jg::pin_at(ctx, 64), w->lc.size() * 8);
         if (w->spec) std::memcpy(w->spec_h, jg::pin_at(ctx, at_spec), sizeof w->spec_h);
-        unsigned long long h[2];
-        std::memcpy(h, jg::pin_at(ctx, 0), 8);
-        h[1] = w->lc[0];
+        const unsigned long long h[2] = {*static_cast<const unsigned long long*>(jg::pin_at(ctx, 0)), w->lc[0]};  // first bad, overflow
         // the speculative scatter found a claimed place outside its arrays in a wave whose claims all counted: the
         // tables are inconsistent, and nothing of the wave may commit (it would commit a bucket with a stale slot)
         JG_REQUIRE(!(w->spec && h[1] == 0 && w->lc[1] == 0 && w->spec_h[8] != 0), JG_EHIP,
                    "OR-Set wave check: the claims' scatter found places outside the bucket arrays (flags %llx): internal table inconsistency",
                    w->spec_h[8]);
-        const char* e = std::getenv("JANUS_ORSET_TAIL");  // =tables (tests): no fall-back, an overflow is an error
-        JG_REQUIRE(h[1] == 0 || !(e && std::strcmp(e, "tables") == 0), JG_ESTATE, "OR-Set wave tables overflowed (JANUS_ORSET_TAIL=tables)");
+        JG_REQUIRE(h[1] == 0 || w->knobs.tail != WaveKnobs::kTailTables, JG_ESTATE, "OR-Set wave tables overflowed (JANUS_ORSET_TAIL=tables)");
         w->seen_s = w->seen_r = 0;  // an overflowed wave: the next one sizes its tables from the bound
         if (h[1] == 0) {
             w->tables_ok = true;
@@ -1702,16 +1173,9 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
             // a set's element ids cannot run out in this wave's commit: every set's next id is at most the
             // names issued so far, and the wave adds at most one per distinct (set, string) — checked here,
             // before a node wave commits anything (the commit's own check then never fires mid-wave)
-            uint64_t ns = 0;
-            for (uint32_t j = 0; j < kLists; ++j) ns += w->lc[(1 + j) * kCountStride];
-            check_id_room(ctx, w, ns, n);
+            check_id_room(ctx, w, w->seen_s, n);
             g_tmark[1] = jg::now_us();
-            if (h[0] == kNone) return JG_OK;
-            unsigned long long e;
-            JG_HIP(hipMemcpyAsync(&e, w->err.as<unsigned long long>() + h[0], 8, hipMemcpyDeviceToHost, ctx->stream));
-            JG_HIP(hipStreamSynchronize(ctx->stream));
-            w->first_bad = h[0];
-            return (e & 3) == kKindState ? JG_ESTATE : JG_EINVAL;
+            return note_bad(ctx, w, h[0]);
         }
     }
     // offsets: exclusive sums with a zero sentinel at [n]
@@ -1758,61 +1222,17 @@ int check_wave(jg_orset* s, jg_orset_wire* w) {
         ensure(w->seg, ne * 4);
         ensure(w->impure, ne);
         ensure(w->label, ne * 4);
-        sort_pairs(ctx, w, E.key, w->skey.as<unsigned long long>(), E.val, w->sval.as<uint32_t>(), ne, w->sort_bits);
-        const unsigned long long run_mask = w->sort_bits >= 64 ? ~0ull : (1ull << w->sort_bits) - 1;
-        hipLaunchKernelGGL(k_ow_head, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, w->skey.as<unsigned long long>(), ne, run_mask,
-                           w->hs.as<uint32_t>());
-        JG_HIP(hipGetLastError());
-        const int n_ent = jg::cub_count(ne, "entries");
-        jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceScan::InclusiveScan(temp, bytes, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), n_ent, ctx->stream);
-        });
-        JG_HIP(hipMemsetAsync(w->impure.p, 0, ne, ctx->stream));
-        hipLaunchKernelGGL(k_ow_link, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes,
-                           w->sval.as<uint32_t>(), w->seg.as<uint32_t>(), ne, w->impure.as<uint8_t>());
-        JG_HIP(hipGetLastError());
-        JG_HIP(hipMemsetAsync(status_words(w) + 1, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_ow_label, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes,
-                           w->sval.as<uint32_t>(), w->seg.as<uint32_t>(), w->impure.as<uint8_t>(), ne, w->label.as<uint32_t>(),
-                           w->err.as<unsigned long long>(), kImpureScan, status_words(w) + 1);
-        JG_HIP(hipGetLastError());
+        group_entries(ctx, w, w->sort_bits, kImpureScan);
     }
-    unsigned long long* st = status_words(w);
-    JG_HIP(hipMemsetAsync(st, 0xFF, 8, ctx->stream));
-    hipLaunchKernelGGL(k_ow_first_bad, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, w->err.as<unsigned long long>(), n, st);
-    JG_HIP(hipGetLastError());
+    launch_first_bad(ctx, w);
     unsigned long long words[2] = {kNone, 0};
-    read_words(ctx, st, words, ne ? 2 : 1);
+    read_words(ctx, status_words(w), words, ne ? 2 : 1);
     if (words[1]) {  // a long impure run: entries again by their whole 64-bit keys, then label without a limit
-        const Entries E = entries_of(w);
-        sort_pairs(ctx, w, E.key, w->skey.as<unsigned long long>(), E.val, w->sval.as<uint32_t>(), ne, 64);
-        hipLaunchKernelGGL(k_ow_head, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, w->skey.as<unsigned long long>(), ne, ~0ull,
-                           w->hs.as<uint32_t>());
-        JG_HIP(hipGetLastError());
-        const int n_ent = jg::cub_count(ne, "entries");
-        jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceScan::InclusiveScan(temp, bytes, w->hs.as<uint32_t>(), w->seg.as<uint32_t>(), hipcub::Max(), n_ent, ctx->stream);
-        });
-        JG_HIP(hipMemsetAsync(w->impure.p, 0, ne, ctx->stream));
-        hipLaunchKernelGGL(k_ow_link, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes, w->sval.as<uint32_t>(),
-                           w->seg.as<uint32_t>(), ne, w->impure.as<uint8_t>());
-        hipLaunchKernelGGL(k_ow_label, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes, w->sval.as<uint32_t>(),
-                           w->seg.as<uint32_t>(), w->impure.as<uint8_t>(), ne, w->label.as<uint32_t>(), w->err.as<unsigned long long>(),
-                           UINT32_MAX, st + 1);
-        JG_HIP(hipGetLastError());
-        JG_HIP(hipMemsetAsync(st, 0xFF, 8, ctx->stream));
-        hipLaunchKernelGGL(k_ow_first_bad, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, w->err.as<unsigned long long>(), n, st);
-        JG_HIP(hipGetLastError());
-        read_words(ctx, st, words, 1);
-        ++w->resorts;
+        group_entries(ctx, w, 64, UINT32_MAX);
+        launch_first_bad(ctx, w);
+        read_words(ctx, status_words(w), words, 1);
     }
-    const unsigned long long bad = words[0];
-    if (bad == kNone) return JG_OK;
-    unsigned long long e;
-    JG_HIP(hipMemcpyAsync(&e, w->err.as<unsigned long long>() + bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-    JG_HIP(hipStreamSynchronize(ctx->stream));
-    w->first_bad = bad;
-    return (e & 3) == kKindState ? JG_ESTATE : JG_EINVAL;
+    return note_bad(ctx, w, words[0]);
 }
 
 // Sort one side's distinct records by (key, tag.lo, tag.hi) into a dense stream; ords = first tag index in the
@@ -1826,9 +1246,7 @@ void sort_side_begin(jg_ctx* ctx, jg_orset_wire* w, int sd, uint64_t n, int key_
     out.next = nt;
     JG_HIP(hipMemsetAsync(long_run, 0, 8, ctx->stream));
     if (n == 0) return;
-    ensure(w->rk, n * 8);
-    ensure(w->rk2, n * 8);
-    ensure(w->perm[sd], n * 4);
+    ensure(w->perm[sd], n * 4);  // (rk / rk2: sized for both sides by finish_records)
     ensure(w->perm2[sd], n * 4);
     const auto* dk = w->dk[sd].as<unsigned long long>();
     const auto* dt = w->dt[sd].as<Tag16>();
@@ -1864,18 +1282,46 @@ void sort_side_end(jg_ctx* ctx, jg_orset_wire* w, int sd, uint64_t n, int key_bi
     JG_HIP(hipGetLastError());
 }
 
-void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t ns, uint64_t nrec, uint32_t csi_lim, uint32_t t_lim,
-                   uint64_t t_next, double* tc, bool tr);
+// The wave's sorted records, the union's source: kept across waves (no allocation per commit).
+jg_orset* recs_of(jg_ctx* ctx, jg_orset_wire* w) {
+    if (!w->recs) {
+        w->recs = new jg_orset();
+        w->recs->ctx = ctx;
+    }
+    return w->recs;
+}
 
-// The bucket commit (orset_commit.hpp): false if a set's bucket is past the LDS sorts (or JANUS_ORSET_COMMIT=radix),
+// The radix record tail: each side's cnt[sd] distinct records (w->dk / dt / ds) sorted by (key, tag) into the wave's
+// record store — ords mint[slot * stride], all below t_next — and unioned into the store.  One read between the
+// two halves: both sides' long-run flags; returns the host time behind that read when the knobs ask for a trace.
+double finish_records(jg_orset* s, jg_orset_wire* w, const unsigned long long (&cnt)[2], uint64_t t_next, const uint32_t* mint, uint32_t stride) {
+    jg_ctx* ctx = s->ctx;
+    unsigned long long* st = status_words(w);
+    jg_orset* recs = recs_of(ctx, w);
+    const int key_bits = 32 + bits_for(w->max_set);
+    const uint64_t nmax = std::max(cnt[0], cnt[1]);  // the radix-key buffers serve both sides: sized once,
+    ensure(w->rk, nmax * 8);                           // so no reallocation frees one that queued work reads
+    ensure(w->rk2, nmax * 8);
+    sort_side_begin(ctx, w, 0, cnt[0], key_bits, t_next, recs->add, st + 6);
+    sort_side_begin(ctx, w, 1, cnt[1], key_bits, t_next, recs->rem, st + 7);
+    unsigned long long long_run[2];
+    read_words(ctx, st + 6, long_run, 2);
+    const double t_read = w->knobs.trace ? jg::now_us() : 0;
+    sort_side_end(ctx, w, 0, cnt[0], key_bits, recs->add, long_run[0] != 0, mint, stride);
+    sort_side_end(ctx, w, 1, cnt[1], key_bits, recs->rem, long_run[1] != 0, mint, stride);
+    jg::orset_merge_store(s, recs, w->external);  // a node wave: the node's final read brings the counts
+    return t_read;
+}
+
+void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t ns, uint64_t nrec, uint32_t csi_lim, uint32_t t_lim,
+                   uint64_t t_next, double* tc);
+
+// The bucket commit (orset_commit.hpp): false if a set's bucket is past the LDS sorts (or WaveKnobs::kCommitRadix),
 // with nothing changed but the resolved ids of known strings (the radix path writes them again).
 bool commit_buckets(jg_orset* s, jg_orset_wire* w, const StrTab& ST, const RecTab& RT, uint64_t ns, uint64_t nrec, uint32_t csi_lim,
                     uint32_t t_lim, uint64_t t_next) {
-    // JANUS_ORSET_COMMIT (read per wave: tests switch it): radix = the radix path alone; buckets = no fall-back (a
-    // wave the bucket path cannot take is an error)
-    const char* e = std::getenv("JANUS_ORSET_COMMIT");
-    if (e && std::strcmp(e, "radix") == 0) return false;
-    const bool strict = e && std::strcmp(e, "buckets") == 0;
+    if (w->knobs.commit == WaveKnobs::kCommitRadix) return false;
+    const bool strict = w->knobs.commit == WaveKnobs::kCommitBuckets;
     jg_ctx* ctx = s->ctx;
     const uint64_t n_sets = (uint64_t)w->max_set + 1;
     // one count per set id up to the wave's largest: sparse set ids (far more ids than items) take the radix path
@@ -1888,30 +1334,27 @@ bool commit_buckets(jg_orset* s, jg_orset_wire* w, const StrTab& ST, const RecTa
     // and places stand, and neither k_cb_count nor its memsets run
     // (only a wave the check prepared: its scatter's bound flag was read with the check's words)
     const bool claimed = w->spec && csi_lim == 0xFFFFFFFFu && t_lim == 0xFFFFFFFFu && w->lc.size() > 1 && w->lc[1] == 0 && n_sets <= w->cb_cap &&
-                         !(e && std::strcmp(e, "count") == 0);  // JANUS_ORSET_COMMIT=count: the counting pass always (tests)
-    ensure(w->cb, cb_items_bytes(w->st_cap, w->rt_cap));  // (sized by tables_begin)
-    Buckets B = buckets_of(w);
+                         w->knobs.commit != WaveKnobs::kCommitCount;  // the counting pass always (tests)
+    ensure(w->cb, items_bytes(w));  // (sized by tables_begin)
     unsigned long long* st = status_words(w);
     if (n_sets > w->cb_cap) {  // (a set the wave's claims could not count) room for every set's counts
-        w->cbc.alloc(cb_counts_bytes(n_sets));  // the tables' claims are done with the old block (same stream)
+        w->cbc.alloc(claims_bytes(n_sets));  // the tables' claims are done with the old block (same stream)
         w->cb_cap = n_sets;
-        const Claims C2 = claims_of(w);
-        B.scnt = C2.scnt, B.rcnt[0] = C2.rcnt[0], B.rcnt[1] = C2.rcnt[1], B.sbytes = C2.sbytes;
     }
+    const Buckets B = buckets_of(w);
     // not from the claims: the counts again from the lists (the check may have scanned the claims' counts in place)
-    if (!claimed) JG_HIP(hipMemsetAsync(w->cbc.p, 0, cb_counts_bytes(w->cb_cap), ctx->stream));  // the four count arrays (and their trailing zeros)
+    if (!claimed) JG_HIP(hipMemsetAsync(w->cbc.p, 0, claims_bytes(w->cb_cap), ctx->stream));  // the four count arrays (and their trailing zeros)
     // the scan's words (and k_cb_strings' id flag, a device-side guard no host reads: the check ruled the overflow
     // out); a commit from the check's scan reads no word here, and skips the call (~25-40 us of host time right
     // behind the check's sync, with the device idle)
     if (!(claimed && w->spec)) JG_HIP(hipMemsetAsync(st, 0, 9 * 8, ctx->stream));
-    static const bool trm = std::getenv("JANUS_TRACE_MERGE") != nullptr;
-    if (trm) {
+    if (w->knobs.trace) {
         g_tmark[5] = jg::now_us();
         std::fprintf(stderr, "commit host: read -> check end %.0f us, -> commit %.0f, -> names %.0f, names %.0f, -> first launch %.0f\n", g_tmark[1] - g_tmark[0],
                      g_tmark[2] - g_tmark[1], g_tmark[3] - g_tmark[2], g_tmark[4] - g_tmark[3], g_tmark[5] - g_tmark[4]);
     }
     const Sparse S = sparse_of(w);
-    const Names N = names_of(w);
+    const Names N = w->names.view();
     unsigned long long h[8];  // totals: new strings, their bytes, records per side; then the largest buckets
     if (claimed) {  // scanned by the check, totals read with it (spec_commit_prep)
         std::memcpy(h, w->spec_h, sizeof h);
@@ -1932,34 +1375,21 @@ bool commit_buckets(jg_orset* s, jg_orset_wire* w, const StrTab& ST, const RecTa
     const uint64_t n_new = h[0], nb = h[1], cnt[2] = {h[2], h[3]};
     if (!claimed && ns + nrec)  // (a claimed wave was scattered by the check: spec_commit_prep)
         hipLaunchKernelGGL(k_cb_scatter, dim3(blocks_for(ns + nrec)), dim3(kBlock), 0, ctx->stream, ns, nrec, ST, RT, B);
-    if (claimed) ++w->waves_claimed;
     // LDS and threads for the largest bucket (orset_commit.hpp)
     auto cb_threads = [](uint32_t P) { return std::min<uint32_t>(kCbBlock, std::max<uint32_t>(64, P)); };
     const uint32_t Ps = pow2_ge(std::max<uint32_t>(1, (uint32_t)h[4])), Pr = pow2_ge(std::max<uint32_t>(1, (uint32_t)std::max(h[6], h[7])));
     if (n_new)
-        hipLaunchKernelGGL(k_cb_strings, dim3((unsigned)n_sets), dim3(cb_threads(Ps)), cb_strings_lds(Ps), ctx->stream, S, w->vbytes, ST, B, w->n_names,
-                           w->pool_used, N, w->sid_id.as<uint32_t>(), st);
+        hipLaunchKernelGGL(k_cb_strings, dim3((unsigned)n_sets), dim3(cb_threads(Ps)), cb_strings_lds(Ps), ctx->stream, S, w->vbytes, ST, B, w->names.n_names,
+                           w->names.pool_used, N, w->sid_id.as<uint32_t>(), st);
     JG_HIP(hipGetLastError());
-    ++w->waves_bucketed;
-    // ids issued (the check ruled out running past 2^32 - 2: id_bound), names in (set, first entry) order
-    w->n_names += n_new;
-    w->id_bound += n_new;
-    w->pool_used += nb;
-    w->g1 = w->n_names;
-    w->p1 = w->pool_used;
-    queue_names(ctx, w);
-    w->mark();
+    w->names.issue_names(ctx, n_new, w->names.pool_used + nb);
     w->last_cnt[0] = cnt[0], w->last_cnt[1] = cnt[1];
     if (cnt[0] + cnt[1] == 0) return true;
-    if (!w->recs) {
-        w->recs = new jg_orset();
-        w->recs->ctx = ctx;
-    }
-    jg::set_dense(ctx, w->recs->add, cnt[0]);
-    jg::set_dense(ctx, w->recs->rem, cnt[1]);
-    w->recs->add.next = w->recs->rem.next = t_next;
-    jg_stream_soa& a = w->recs->add;
+    jg_stream_soa& a = recs_of(ctx, w)->add;
     jg_stream_soa& r = w->recs->rem;
+    jg::set_dense(ctx, a, cnt[0]);
+    jg::set_dense(ctx, r, cnt[1]);
+    a.next = r.next = t_next;
     hipLaunchKernelGGL(k_cb_records, dim3((unsigned)n_sets, 2), dim3(cb_threads(Pr)), cb_records_lds(Pr), ctx->stream, S, ST, RT, B, w->sid_id.as<uint32_t>(),
                        a.key.as<unsigned long long>(), a.tag.as<Tag16>(), a.ord.as<uint32_t>(), r.key.as<unsigned long long>(), r.tag.as<Tag16>(),
                        r.ord.as<uint32_t>());
@@ -1974,9 +1404,7 @@ bool commit_buckets(jg_orset* s, jg_orset_wire* w, const StrTab& ST, const RecTa
 void commit_tables(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
     jg_ctx* ctx = s->ctx;
     const uint64_t n = w->wn;
-    static const bool tr = std::getenv("JANUS_TRACE_MERGE") != nullptr;
-    const auto now = jg::now_us;
-    double tc[5] = {tr ? now() : 0};
+    double tc[5] = {w->knobs.trace ? jg::now_us() : 0};
     g_tmark[2] = tc[0];
     uint64_t lim_off = w->wnb;
     if (limit < n) {  // the limit message's byte offset
@@ -1987,53 +1415,48 @@ void commit_tables(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
     const uint32_t csi_lim = limit < n ? (uint32_t)((lim_off + kEntryDiv - 1) / kEntryDiv) : 0xFFFFFFFFu;
     const uint32_t t_lim = limit < n ? (uint32_t)((lim_off + kTagDiv - 1) / kTagDiv) : 0xFFFFFFFFu;
     const uint64_t t_next = (w->wnb + kTagDiv - 1) / kTagDiv + 1;  // every tag slot of the wave is below this
-    ensure_sets(ctx, w, (uint64_t)w->max_set + 1);
-    ensure_names(ctx, w, 0, 0);
+    w->names.ensure_sets(ctx, (uint64_t)w->max_set + 1);
+    w->names.ensure_names(ctx, 0, 0);
     StrTab ST = str_tab(w);
     RecTab RT = rec_tab(w);
     // the wave's strings (the table's list; those first named past the limit are skipped)
     // the sub-lists packed into one list each (offsets from the counts: one read, one pack launch per table)
     const std::vector<unsigned long long>& lc = w->lc;  // read by the check with the first bad message
-    if (w->spec) {  // packed by the check (spec_commit_prep): the offsets on the device gave the same layout
-        uint64_t ns = 0, nrec = 0;
-        for (uint32_t j = 0; j < kLists; ++j) ns += lc[(1 + j) * kCountStride], nrec += lc[(1 + kLists + j) * kCountStride];
-        ST.list = w->st_packed.as<uint32_t>();
-        RT.list = w->rt_packed.as<uint32_t>();
-        commit_packed(s, w, ST, RT, ns, nrec, csi_lim, t_lim, t_next, tc, tr);
-        return;
-    }
     unsigned long long offs[2][kLists + 1];
     for (int t = 0; t < 2; ++t) {
         offs[t][0] = 0;
         for (uint32_t j = 0; j < kLists; ++j) offs[t][j + 1] = offs[t][j] + lc[(1 + t * kLists + j) * kCountStride];
     }
     const uint64_t ns = offs[0][kLists], nrec = offs[1][kLists];
-    ensure(w->loffs, sizeof offs);
-    ensure(w->st_packed, ns * 4 + 4);
-    ensure(w->rt_packed, nrec * 4 + 4);
-    // from the context's page-locked write area (a pageable source is staged by the runtime, a host round trip);
-    // nothing else writes there before this wave's commit has synced
-    static_assert(sizeof offs <= jg::kPinBytes - jg::kPinRead, "offsets fit the page-locked write area");
-    void* hoffs = static_cast<char*>(ctx->hstat) + jg::kPinRead;
-    std::memcpy(hoffs, offs, sizeof offs);
-    JG_HIP(hipMemcpyAsync(w->loffs.p, hoffs, sizeof offs, hipMemcpyHostToDevice, ctx->stream));
-    const auto* doffs = w->loffs.as<unsigned long long>();
-    if (ns)
-        hipLaunchKernelGGL(k_list_pack, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, ST.list, ST.sub_cap, doffs, w->st_packed.as<uint32_t>());
-    if (nrec)
-        hipLaunchKernelGGL(k_list_pack, dim3(blocks_for(nrec)), dim3(kBlock), 0, ctx->stream, RT.list, RT.sub_cap, doffs + kLists + 1,
-                           w->rt_packed.as<uint32_t>());
-    JG_HIP(hipGetLastError());
+    if (!w->spec) {  // (else packed by the check, spec_commit_prep: the offsets on the device gave the same layout)
+        ensure(w->loffs, sizeof offs);
+        ensure(w->st_packed, ns * 4 + 4);
+        ensure(w->rt_packed, nrec * 4 + 4);
+        // from the context's page-locked write area (a pageable source is staged by the runtime, a host round trip);
+        // nothing else writes there before this wave's commit has synced
+        static_assert(sizeof offs <= jg::kPinBytes - jg::kPinRead, "offsets fit the page-locked write area");
+        void* hoffs = static_cast<char*>(ctx->hstat) + jg::kPinRead;
+        std::memcpy(hoffs, offs, sizeof offs);
+        JG_HIP(hipMemcpyAsync(w->loffs.p, hoffs, sizeof offs, hipMemcpyHostToDevice, ctx->stream));
+        const auto* doffs = w->loffs.as<unsigned long long>();
+        if (ns)
+            hipLaunchKernelGGL(k_list_pack, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, ST.list, ST.sub_cap, doffs, w->st_packed.as<uint32_t>());
+        if (nrec)
+            hipLaunchKernelGGL(k_list_pack, dim3(blocks_for(nrec)), dim3(kBlock), 0, ctx->stream, RT.list, RT.sub_cap, doffs + kLists + 1,
+                               w->rt_packed.as<uint32_t>());
+        JG_HIP(hipGetLastError());
+    }
     ST.list = w->st_packed.as<uint32_t>();  // the commit kernels read the packed lists
     RT.list = w->rt_packed.as<uint32_t>();
-    commit_packed(s, w, ST, RT, ns, nrec, csi_lim, t_lim, t_next, tc, tr);
+    commit_packed(s, w, ST, RT, ns, nrec, csi_lim, t_lim, t_next, tc);
 }
 
 // The table commit from the packed lists: the bucket commit, or the radix path.
 void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t ns, uint64_t nrec, uint32_t csi_lim, uint32_t t_lim,
-                   uint64_t t_next, double* tc, bool tr) {
+                   uint64_t t_next, double* tc) {
     jg_ctx* ctx = s->ctx;
     const auto now = jg::now_us;
+    const bool tr = w->knobs.trace;
     unsigned long long* st = status_words(w);
     const Sparse S = sparse_of(w);
     // room for every listed string (an upper bound of the new ones: the element tables then grow ahead of the
@@ -2042,7 +1465,7 @@ void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t
     // (both commit paths issue exactly those names), else the wave's bytes
     const bool exact = w->spec && csi_lim == 0xFFFFFFFFu && t_lim == 0xFFFFFFFFu && w->lc.size() > 1 && w->lc[1] == 0;
     if (tr) g_tmark[3] = now();
-    if (ns) ensure_names(ctx, w, ns, exact ? w->spec_h[1] : w->wnb);
+    if (ns) w->names.ensure_names(ctx, ns, exact ? w->spec_h[1] : w->wnb);
     if (tr) g_tmark[4] = now();
     if (commit_buckets(s, w, ST, RT, ns, nrec, csi_lim, t_lim, t_next)) {
         if (tr) std::fprintf(stderr, "commit_tables: bucket commit %.0f us (%llu strings, %llu records listed)\n", now() - tc[0],
@@ -2051,20 +1474,20 @@ void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t
     }
     // strings: each looked up (new ones keyed by (set, first entry), known ones kNone), all sorted by that key
     // (known last), new ids assigned in that order; no host round trip until the record counts are read
-    const unsigned long long init[4] = {0, 0, w->pool_used, 0};
+    const unsigned long long init[4] = {0, 0, w->names.pool_used, 0};
     JG_HIP(hipMemcpyAsync(st, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
     if (ns) {
         ensure(w->newk, ns * 8);
         ensure(w->snk, ns * 8);
         ensure(w->snv, ns * 4);
-        hipLaunchKernelGGL(k_ow_sresolve, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, S, w->vbytes, ST, ns, csi_lim, names_of(w),
+        hipLaunchKernelGGL(k_ow_sresolve, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, S, w->vbytes, ST, ns, csi_lim, w->names.view(),
                            w->sid_id.as<uint32_t>(), w->newk.as<unsigned long long>());
         JG_HIP(hipGetLastError());
         sort_pairs(ctx, w, w->newk.as<unsigned long long>(), w->snk.as<unsigned long long>(), ST.list, w->snv.as<uint32_t>(), ns, 64);
         hipLaunchKernelGGL(k_ow_sassign, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, S, w->vbytes, ST, w->snk.as<unsigned long long>(),
-                           w->snv.as<uint32_t>(), ns, w->n_names, names_of(w), w->sid_id.as<uint32_t>(), st);
+                           w->snv.as<uint32_t>(), ns, w->names.n_names, w->names.view(), w->sid_id.as<uint32_t>(), st);
         JG_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ow_snext_ids, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, w->snk.as<unsigned long long>(), ns, names_of(w));
+        hipLaunchKernelGGL(k_ow_snext_ids, dim3(blocks_for(ns)), dim3(kBlock), 0, ctx->stream, w->snk.as<unsigned long long>(), ns, w->names.view());
         JG_HIP(hipGetLastError());
     }
     // the wave's records (the table's list), per side, first occurring before the limit
@@ -2080,13 +1503,7 @@ void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t
     read_words(ctx, st, hh, 6);
     if (tr) tc[2] = now();
     JG_REQUIRE(hh[3] == 0, JG_ESTATE, "jg_orset_wave_commit: too many elements in one OR-Set (2^32 - 2 ids)");
-    w->n_names += hh[1];
-    w->id_bound += hh[1];
-    w->pool_used = hh[2];
-    w->g1 = w->n_names;
-    w->p1 = w->pool_used;
-    queue_names(ctx, w);
-    w->mark();
+    w->names.issue_names(ctx, hh[1], hh[2]);
     const unsigned long long cnt[2] = {hh[4], hh[5]};
     w->last_cnt[0] = cnt[0], w->last_cnt[1] = cnt[1];
     if (cnt[0] + cnt[1] == 0) return;
@@ -2100,22 +1517,7 @@ void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t
                            w->ds[sd].as<uint32_t>());
         JG_HIP(hipGetLastError());
     }
-    if (!w->recs) {
-        w->recs = new jg_orset();
-        w->recs->ctx = ctx;
-    }
-    const int key_bits = 32 + bits_for(w->max_set);
-    const uint64_t nmax = std::max(cnt[0], cnt[1]);
-    ensure(w->rk, nmax * 8);
-    ensure(w->rk2, nmax * 8);
-    sort_side_begin(ctx, w, 0, cnt[0], key_bits, t_next, w->recs->add, st + 6);
-    sort_side_begin(ctx, w, 1, cnt[1], key_bits, t_next, w->recs->rem, st + 7);
-    unsigned long long long_run[2];
-    read_words(ctx, st + 6, long_run, 2);
-    if (tr) tc[3] = now();
-    sort_side_end(ctx, w, 0, cnt[0], key_bits, w->recs->add, long_run[0] != 0, &RT.slot[0].mint, 4);
-    sort_side_end(ctx, w, 1, cnt[1], key_bits, w->recs->rem, long_run[1] != 0, &RT.slot[0].mint, 4);
-    jg::orset_merge_store(s, w->recs, w->external);  // a node wave: the node's final read brings the counts
+    tc[3] = finish_records(s, w, cnt, t_next, &RT.slot[0].mint, 4);  // the record table's 16-byte slots
     if (tr) {
         tc[4] = now();
         std::fprintf(stderr, "commit_tables: strings queued %.0f us, counts read %.0f, record sorts + long-run read %.0f, union %.0f (%llu strings, %llu + %llu records)\n",
@@ -2125,21 +1527,17 @@ void commit_packed(jg_orset* s, jg_orset_wire* w, StrTab ST, RecTab RT, uint64_t
 
 void commit_wave(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
     jg_ctx* ctx = s->ctx;
-    w->g0 = w->g1 = w->n_names;
-    w->p0 = w->p1 = w->pool_used;
+    w->knobs = WaveKnobs::from_env();
+    w->names.no_names_issued();
     if (limit == 0) return;
     if (w->tables_ok) {
-        ++w->waves_fast;
         commit_tables(s, w, limit);
         return;
     }
-    ++w->waves_sorted;
     const uint64_t ne = w->n_ent, nt = w->n_tag;
-    w->g0 = w->g1 = w->n_names;
-    w->p0 = w->p1 = w->pool_used;
-    if (limit == 0 || (ne == 0 && nt == 0)) return;
-    ensure_sets(ctx, w, (uint64_t)w->max_set + 1);
-    ensure_names(ctx, w, 0, 0);
+    if (ne == 0 && nt == 0) return;
+    w->names.ensure_sets(ctx, (uint64_t)w->max_set + 1);
+    w->names.ensure_names(ctx, 0, 0);
     unsigned long long* st = status_words(w);
     const Entries E = entries_of(w);
     ensure(w->gid, ne * 4 + 4);
@@ -2150,7 +1548,7 @@ void commit_wave(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
         ensure(w->newv, ne * 4);
         JG_HIP(hipMemsetAsync(st, 0, 64, ctx->stream));
         hipLaunchKernelGGL(k_ow_resolve, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, E, w->vmset, w->vbytes,
-                           w->skey.as<unsigned long long>(), w->sval.as<uint32_t>(), w->label.as<uint32_t>(), ne, limit, names_of(w),
+                           w->skey.as<unsigned long long>(), w->sval.as<uint32_t>(), w->label.as<uint32_t>(), ne, limit, w->names.view(),
                            w->gid.as<uint32_t>(), w->newk.as<unsigned long long>());
         JG_HIP(hipGetLastError());
         // the marked sorted indices compacted (count into st[1]) and their keys gathered; the sort below
@@ -2165,28 +1563,22 @@ void commit_wave(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
         nnew = h[1];
     }
     if (nnew) {
-        ensure_names(ctx, w, nnew, w->wnb);
+        w->names.ensure_names(ctx, nnew, w->wnb);
         ensure(w->snk, nnew * 8);
         ensure(w->snv, nnew * 4);
         sort_pairs(ctx, w, w->cnk.as<unsigned long long>(), w->snk.as<unsigned long long>(), w->newv.as<uint32_t>(), w->snv.as<uint32_t>(), nnew,
                    32 + bits_for(w->max_set));
-        const unsigned long long init[4] = {0, 0, w->pool_used, 0};
+        const unsigned long long init[4] = {0, 0, w->names.pool_used, 0};
         JG_HIP(hipMemcpyAsync(st, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_ow_assign, dim3(blocks_for(nnew)), dim3(kBlock), 0, ctx->stream, E, w->vbytes, w->skey.as<unsigned long long>(),
-                           w->snk.as<unsigned long long>(), w->snv.as<uint32_t>(), nnew, w->n_names, names_of(w), w->gid.as<uint32_t>(), st);
+                           w->snk.as<unsigned long long>(), w->snv.as<uint32_t>(), nnew, w->names.n_names, w->names.view(), w->gid.as<uint32_t>(), st);
         JG_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ow_next_ids, dim3(blocks_for(nnew)), dim3(kBlock), 0, ctx->stream, w->snk.as<unsigned long long>(), nnew, names_of(w));
+        hipLaunchKernelGGL(k_ow_next_ids, dim3(blocks_for(nnew)), dim3(kBlock), 0, ctx->stream, w->snk.as<unsigned long long>(), nnew, w->names.view());
         JG_HIP(hipGetLastError());
         unsigned long long h[4];
         read_words(ctx, st, h, 4);
         JG_REQUIRE(h[3] == 0, JG_ESTATE, "jg_orset_wave_commit: too many elements in one OR-Set (2^32 - 2 ids)");
-        w->n_names += nnew;
-        w->id_bound += nnew;
-        w->pool_used = h[2];
-        w->g1 = w->n_names;
-        w->p1 = w->pool_used;
-        queue_names(ctx, w);
-        w->mark();
+        w->names.issue_names(ctx, nnew, h[2]);
     }
     if (ne) {
         hipLaunchKernelGGL(k_ow_entry_ids, dim3(blocks_for(ne)), dim3(kBlock), 0, ctx->stream, w->sval.as<uint32_t>(), w->label.as<uint32_t>(),
@@ -2228,21 +1620,7 @@ void commit_wave(jg_orset* s, jg_orset_wire* w, uint64_t limit) {
     read_words(ctx, st + 4, cnt, 2);
     w->last_cnt[0] = cnt[0], w->last_cnt[1] = cnt[1];
     if (cnt[0] + cnt[1] == 0) return;
-    if (!w->recs) {  // the wave's sorted records: kept across waves (no allocation per commit)
-        w->recs = new jg_orset();
-        w->recs->ctx = ctx;
-    }
-    const int key_bits = 32 + bits_for(w->max_set);
-    const uint64_t nmax = std::max(cnt[0], cnt[1]);  // the radix-key buffers serve both sides: sized once,
-    ensure(w->rk, nmax * 8);                           // so no reallocation frees one that queued work reads
-    ensure(w->rk2, nmax * 8);
-    sort_side_begin(ctx, w, 0, cnt[0], key_bits, nt, w->recs->add, st + 6);
-    sort_side_begin(ctx, w, 1, cnt[1], key_bits, nt, w->recs->rem, st + 7);
-    unsigned long long long_run[2];
-    read_words(ctx, st + 6, long_run, 2);
-    sort_side_end(ctx, w, 0, cnt[0], key_bits, w->recs->add, long_run[0] != 0, w->dmin.as<uint32_t>(), 1);
-    sort_side_end(ctx, w, 1, cnt[1], key_bits, w->recs->rem, long_run[1] != 0, w->dmin.as<uint32_t>(), 1);
-    jg::orset_merge_store(s, w->recs, w->external);  // a node wave: the node's final read brings the counts
+    finish_records(s, w, cnt, nt, w->dmin.as<uint32_t>(), 1);  // the dedup table's array
 }
 
 void close_wave(jg_orset_wire* w) {
@@ -2255,137 +1633,34 @@ void close_wave(jg_orset_wire* w) {
     w->first_bad = kNone;
 }
 
-
-// jg_orset_encode_json: gather the sets' records below the limits, order them (runs by section and element, tags
-// by ord), size every state, then write them (see the kernels' header comment).  Two round trips: the record
-// count (gather) and the states' offsets; a third copy brings the bytes.
-void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* off, uint8_t* out,
-                 uint64_t cap, uint8_t* sha) {
-    jg_ctx* ctx = s->ctx;
-    jg_orset_wire* w = wire_of(s);
-    if (!w->itab_cap || !w->tab_cap) ensure_names(ctx, w, 0, 0);  // a store that never saw a name: empty tables
-    const bool lim = add_lim != nullptr;
-    using ull = unsigned long long;
-    uint32_t* d_sets;
-    ull* d_lim;
-    jg::Layout Q;
-    Q.add(d_sets, n), Q.add(d_lim, lim ? 2 * n : 0);
-    Q.bind(jg::scratch(ctx, ctx->scratch, Q.bytes() + 256));
-    if (!lim) d_lim = nullptr;
-    JG_HIP(hipMemcpyAsync(d_sets, set, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (lim) {
-        std::vector<unsigned long long> l(2 * n);
-        for (uint64_t i = 0; i < n; ++i) l[2 * i] = add_lim[i], l[2 * i + 1] = rem_lim[i];
-        JG_HIP(hipMemcpyAsync(d_lim, l.data(), 2 * n * 8, hipMemcpyHostToDevice, ctx->stream));
-        JG_HIP(hipStreamSynchronize(ctx->stream));  // l is a local
-    }
-    const jg::OrsetGathered G = jg::orset_gather_sets(s, n, d_sets, d_lim, w->enc_g);
-    const uint64_t R = G.R;
-    const EncRec E{G.key, G.tlo, G.thi, G.ord, G.qs};
-    // the encoder's arrays, one block
-    const uint64_t R1 = R + 1;
-    uint32_t *kidx, *hf, *rid, *rstart, *rend, *rfirst, *rval, *srun, *rrank, *sfirst, *recv, *srec;
-    ull *K, *nruns, *rkey, *skey, *cnt, *tlen, *rpos, *cpos, *qsec, *qlen, *qoff, *reck, *reck2, *rtags;
-    unsigned* err;
-    jg::Layout L;
-    L.add(kidx, R), L.add(K, 1), L.add(hf, R), L.add(rid, R), L.add(rstart, R), L.add(rend, R), L.add(rfirst, R), L.add(nruns, 1);
-    L.add(rkey, R), L.add(rval, R), L.add(skey, R), L.add(srun, R), L.add(rrank, R), L.add(cnt, R1), L.add(tlen, R1), L.add(rpos, R1), L.add(cpos, R1);
-    L.add(qsec, 4 * n), L.add(sfirst, 4 * n), L.add(qlen, n + 1), L.add(qoff, n + 1);
-    L.add(reck, R), L.add(recv, R), L.add(reck2, R), L.add(srec, R), L.add(rtags, R), L.add(err, 1);
-    ensure(w->enc, L.bytes());
-    L.bind(w->enc.p);
-    JG_HIP(hipMemsetAsync(qsec, 0, 4 * n * 8, ctx->stream));
-    JG_HIP(hipMemsetAsync(sfirst, 0xFF, 4 * n * 4, ctx->stream));
-    JG_HIP(hipMemsetAsync(err, 0, 4, ctx->stream));
-    JG_HIP(hipMemsetAsync(K, 0, 8, ctx->stream));
-    JG_HIP(hipMemsetAsync(nruns, 0, 8, ctx->stream));
-    const Names N = names_of(w);
-    const unsigned gR = blocks_for(R);
-    if (R) {
-        const int n_R = jg::cub_count(R, "records"), n_R1 = jg::cub_count(R1, "records");
-        const auto tmp = jg::cub_in(w->cub);
-        hipcub::CountingInputIterator<uint32_t> iota(0);
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceSelect::Flagged(temp, bytes, iota, G.keep, kidx, K, n_R, ctx->stream); });
-        hipLaunchKernelGGL(k_enc_heads, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, R, hf);
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(temp, bytes, hf, rid, n_R, ctx->stream); });
-        hipLaunchKernelGGL(k_enc_runs, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rstart, rend, rfirst, nruns);
-        hipLaunchKernelGGL(k_enc_first_ord, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rfirst);
-        hipLaunchKernelGGL(k_enc_run_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, rstart, rfirst, nruns, R, rkey, rval);
-        JG_HIP(hipGetLastError());
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, rkey, skey, rval, srun, n_R, 0, 64, ctx->stream);
-        });
-        hipLaunchKernelGGL(k_enc_run_len, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, kidx, rstart, rend, skey, srun, nruns, R, rrank, cnt, tlen, qsec,
-                           sfirst, err);
-        hipLaunchKernelGGL(k_enc_rec_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rrank, R, reck, recv);
-        JG_HIP(hipGetLastError());
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, reck, reck2, recv, srec, n_R, 0, 64, ctx->stream);
-        });
-        JG_HIP(hipMemsetAsync(tlen + R, 0, 8, ctx->stream));
-        JG_HIP(hipMemsetAsync(cnt + R, 0, 8, ctx->stream));
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, tlen, rpos, n_R1, ctx->stream); });
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, cpos, n_R1, ctx->stream); });
-    }
-    hipLaunchKernelGGL(k_enc_qlen, dim3(blocks_for(n + 1)), dim3(kBlock), 0, ctx->stream, qsec, n, qlen);
-    JG_HIP(hipGetLastError());
-    const int n_q = jg::cub_count(n + 1, "sets");
-    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, qlen, qoff, n_q, ctx->stream); });
-    JG_HIP(hipMemcpyAsync(off, qoff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    jg::pin_get(ctx, 0, err, 4);
-    jg::pin_sync(ctx);  // the stream's copies above are done too
-    unsigned e;
-    std::memcpy(&e, jg::pin_at(ctx, 0), 4);
-    JG_REQUIRE(e == 0, JG_ESTATE, "jg_orset_encode_json: a record names an element id the store's element table does not hold (names not synced)");
-    if (!out) return;  // size query
-    JG_REQUIRE(off[n] <= cap, JG_ESTATE, "jg_orset_encode_json: %llu bytes exceed cap %llu", (unsigned long long)off[n], (unsigned long long)cap);
-    auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, off[n] + 64));
-    hipLaunchKernelGGL(k_enc_fixed, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, qoff, qsec, n, dout);
-    if (R) {
-        hipLaunchKernelGGL(k_enc_run_text, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, kidx, rstart, skey, srun, nruns, rpos, tlen, sfirst, qoff, qsec,
-                           rtags, dout);
-        hipLaunchKernelGGL(k_enc_rec_text, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, srec, rid, rrank, cpos, rtags, dout);
-    }
-    JG_HIP(hipGetLastError());
-    if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(qoff), n, sha);  // each state's SHA-256 (ComputeDigest's first level)
-    JG_HIP(hipMemcpyAsync(out, dout, off[n], hipMemcpyDeviceToHost, ctx->stream));
-    JG_HIP(hipStreamSynchronize(ctx->stream));
-}
-}  // namespace
-
-namespace {
 // The check and the commit of the open wave: the ABI's (which a held store refuses) and a node wave's own
 // (orset_node_check / orset_node_commit, which hold the store).
+// What both calls start with, under the context's lock: the store's open wave, checked.
+jg_orset_wire* checked_wave(jg_orset* s, const char* who, bool node) {
+    if (!node) jg::require_writable(s, who);
+    JG_REQUIRE(s && s->wire && s->wire->open, JG_EINVAL, "%s: no open wave (jg_orset_wave_begin)", who);
+    jg::ensure_device(s->ctx);
+    if (!s->wire->checked) check_wave(s, s->wire);
+    return s->wire;
+}
+
 int wave_check_call(jg_orset* s, uint64_t* bad_msg, bool node) {
     if (bad_msg) *bad_msg = UINT64_MAX;
     return jg::guard([&] {
         auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
-        if (!node) jg::require_writable(s, "jg_orset_wave_check");
-        JG_REQUIRE(s && s->wire && s->wire->open, JG_EINVAL, "jg_orset_wave_check: no open wave (jg_orset_wave_begin)");
-        jg_ctx* ctx = s->ctx;
-        jg::ensure_device(ctx);
-        jg_orset_wire* w = s->wire;
-        if (!w->checked) check_wave(s, w);
+        jg_orset_wire* w = checked_wave(s, "jg_orset_wave_check", node);
         if (w->first_bad == kNone) return;
         if (bad_msg) *bad_msg = w->first_bad;
-        unsigned long long e;
-        JG_HIP(hipMemcpyAsync(&e, w->err.as<unsigned long long>() + w->first_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-        JG_HIP(hipStreamSynchronize(ctx->stream));
-        const bool state = (e & 3) == kKindState;
+        const bool state = w->bad_kind == kKindState;  // recorded by the check (note_bad)
         jg::fail(state ? JG_ESTATE : JG_EINVAL, "OR-Set state message %llu is rejected by ORSetMsg.Decode / Merge (%s at byte %llu)",
-                 (unsigned long long)w->first_bad, state ? "an element with an empty tag set" : "JsonException", (unsigned long long)(e >> 2));
+                 (unsigned long long)w->first_bad, state ? "an element with an empty tag set" : "JsonException", (unsigned long long)w->bad_pos);
     });
 }
 
 int wave_commit_call(jg_orset* s, uint64_t limit, bool node) {
     return jg::guard([&] {
         auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
-        if (!node) jg::require_writable(s, "jg_orset_wave_commit");
-        JG_REQUIRE(s && s->wire && s->wire->open, JG_EINVAL, "jg_orset_wave_commit: no open wave (jg_orset_wave_begin)");
-        jg_ctx* ctx = s->ctx;
-        jg::ensure_device(ctx);
-        jg_orset_wire* w = s->wire;
-        if (!w->checked) check_wave(s, w);
+        jg_orset_wire* w = checked_wave(s, "jg_orset_wave_commit", node);
         JG_REQUIRE(limit <= w->wn, JG_EINVAL, "jg_orset_wave_commit: limit %llu beyond the wave (%llu messages)", (unsigned long long)limit,
                    (unsigned long long)w->wn);
         JG_REQUIRE(w->first_bad == kNone || limit <= w->first_bad, JG_EINVAL, "jg_orset_wave_commit: limit %llu passes the bad message %llu",
@@ -2398,6 +1673,13 @@ int wave_commit_call(jg_orset* s, uint64_t limit, bool node) {
         }
         close_wave(w);
     });
+}
+
+// The calling thread's last error text (jg_last_error), kept across the calls that follow.
+std::string last_error() {
+    char buf[1024];
+    jg_last_error(buf, sizeof buf);
+    return buf;
 }
 }  // namespace
 
@@ -2417,7 +1699,6 @@ void orset_node_begin(jg_orset* s, uint8_t* bytes, uint64_t* off, uint32_t* mset
     w->wn = n;
     w->wnb = nbytes;
     w->max_set = max_set;
-    w->any_set = true;
     w->open = true;
 }
 void orset_node_parse(jg_orset* s, uint64_t m0, uint64_t m1) { launch_parse(s->ctx, s->wire, m0, m1); }
@@ -2429,25 +1710,16 @@ int orset_node_check(jg_orset* s, uint64_t n, uint64_t nbytes, uint64_t* bad, st
     // the union targets sized for the store plus twice the last wave's distinct records while this wave's
     // uploads are still in flight (a growing store reallocates here, not behind the last upload)
     const uint64_t* lc = s->wire->last_cnt;
-    static const bool tr = std::getenv("JANUS_TRACE_MERGE") != nullptr;
     const double t0 = jg::now_us();
     orset_reserve_union(s, 2 * lc[0] + 4096, 2 * lc[1] + 4096);
-    if (tr) std::fprintf(stderr, "orset_node_check: union targets reserved in %.0f us\n", jg::now_us() - t0);
+    if (s->wire->knobs.trace) std::fprintf(stderr, "orset_node_check: union targets reserved in %.0f us\n", jg::now_us() - t0);
     const int rc = wave_check_call(s, bad, true);
-    if (rc != JG_OK) {
-        char buf[1024];
-        jg_last_error(buf, sizeof buf);
-        *why = buf;
-    }
+    if (rc != JG_OK) *why = last_error();
     return rc;
 }
 void orset_node_commit(jg_orset* s, uint64_t limit) {
     const int rc = wave_commit_call(s, limit, true);
-    if (rc != JG_OK) {
-        char buf[1024];
-        jg_last_error(buf, sizeof buf);
-        fail(rc, "%s", buf);
-    }
+    if (rc != JG_OK) fail(rc, "%s", last_error().c_str());
 }
 void orset_node_abort(jg_orset* s) {
     if (s->wire) close_wave(s->wire);
@@ -2456,25 +1728,11 @@ void orset_node_abort(jg_orset* s) {
 // ends before committing must not leave the previous call's there).
 void orset_node_no_names(jg_orset* s) {
     if (!s->wire) return;
-    s->wire->g0 = s->wire->g1 = s->wire->n_names;
-    s->wire->p0 = s->wire->p1 = s->wire->pool_used;
+    s->wire->names.no_names_issued();
 }
 
-// The by-name entry points (orset_names.hip) work on the table through these three.
-NamesRef orset_names_ref(jg_orset* s, uint64_t n_sets, uint64_t incoming, uint64_t pool_bytes) {
-    jg_orset_wire* w = wire_of(s);
-    ensure_sets(s->ctx, w, n_sets);
-    if (incoming || pool_bytes || !w->tab_cap || !w->itab_cap) ensure_names(s->ctx, w, incoming, pool_bytes);
-    return NamesRef{names_of(w), w->kmask, w->salt, w->n_names, w->pool_used, w->set_cap, w->open};
-}
-
-void orset_names_appended(jg_orset* s, uint64_t n, uint64_t nb, uint64_t id_bound) {
-    jg_orset_wire* w = s->wire;
-    w->n_names += n;
-    w->pool_used += nb;
-    w->id_bound = std::max(w->id_bound, id_bound);
-    w->mark();
-}
+ElemTable* orset_elem_table(jg_orset* s, bool create) { return create ? &wire_of(s)->names : s->wire ? &s->wire->names : nullptr; }
+bool orset_wave_open(const jg_orset* s) { return s->wire && s->wire->open; }
 
 void orset_wire_free(jg_orset_wire* w) {
     if (w) delete w->recs;
@@ -2482,69 +1740,12 @@ void orset_wire_free(jg_orset_wire* w) {
 }
 
 void orset_wire_free_retired(jg_orset_wire* w) {
-    for (void* p : w->retired) (void)hipFree(p);
-    w->retired.clear();
+    for (void* p : w->names.retired) (void)hipFree(p);
+    w->names.retired.clear();
 }
 }  // namespace jg
 
 extern "C" {
-
-int jg_orset_names_sync(jg_orset* s, uint64_t n_sets, const uint32_t* set, const uint32_t* next_id, const uint8_t* cleared, uint64_t n_names,
-                        const uint32_t* name_set, const uint32_t* name_id, const uint64_t* off, const uint8_t* bytes) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
-        jg::require_writable(s, "jg_orset_names_sync");
-        JG_REQUIRE(s, JG_EINVAL, "jg_orset_names_sync: store is NULL");
-        JG_REQUIRE((n_sets == 0 || (set && next_id && cleared)) && (n_names == 0 || (name_set && name_id && off && bytes)), JG_EINVAL,
-                   "jg_orset_names_sync: NULL argument");
-        JG_REQUIRE(n_names == 0 || off[0] == 0, JG_EINVAL, "jg_orset_names_sync: off[0] must be 0");
-        jg_ctx* ctx = s->ctx;
-        jg::ensure_device(ctx);
-        jg_orset_wire* w = wire_of(s);
-        JG_REQUIRE(!w->open, JG_EINVAL, "jg_orset_names_sync: a wave is open");
-        uint64_t mx = 0, idb = 0;
-        for (uint64_t i = 0; i < n_sets; ++i) mx = std::max<uint64_t>(mx, (uint64_t)set[i] + 1), idb = std::max<uint64_t>(idb, next_id[i]);
-        for (uint64_t i = 0; i < n_names; ++i) {
-            JG_REQUIRE(off[i + 1] >= off[i] && off[i + 1] - off[i] < 0x7FFFFFFFull, JG_EINVAL, "jg_orset_names_sync: bad offsets at name %llu",
-                       (unsigned long long)i);
-            JG_REQUIRE(name_id[i] < JG_NULL_ELEM - 1, JG_EINVAL, "jg_orset_names_sync: id %u out of range", name_id[i]);
-            mx = std::max<uint64_t>(mx, (uint64_t)name_set[i] + 1);
-        }
-        if (mx == 0) return;
-        ensure_sets(ctx, w, mx);
-        const uint64_t nb = n_names ? off[n_names] : 0;
-        ensure_names(ctx, w, n_names, nb);
-        const size_t need = n_sets * 9 + n_names * 8 + (n_names + 1) * 8 + 64;
-        char* stage = static_cast<char*>(jg::scratch(ctx, ctx->scratch, need));
-        auto* d_set = reinterpret_cast<uint32_t*>(stage);
-        auto* d_next = d_set + n_sets;
-        auto* d_nset = d_next + n_sets;
-        auto* d_nid = d_nset + n_names;
-        auto* d_off = reinterpret_cast<uint64_t*>(stage + jg::round_up(n_sets * 8 + n_names * 8, 16));
-        auto* d_clr = reinterpret_cast<uint8_t*>(d_off + n_names + 1);
-        if (n_sets) {
-            JG_HIP(hipMemcpyAsync(d_set, set, n_sets * 4, hipMemcpyHostToDevice, ctx->stream));
-            JG_HIP(hipMemcpyAsync(d_next, next_id, n_sets * 4, hipMemcpyHostToDevice, ctx->stream));
-            JG_HIP(hipMemcpyAsync(d_clr, cleared, n_sets, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_sets_update, dim3(blocks_for(n_sets)), dim3(kBlock), 0, ctx->stream, names_of(w), d_set, d_next, d_clr, n_sets);
-            JG_HIP(hipGetLastError());
-        }
-        if (n_names) {
-            JG_HIP(hipMemcpyAsync(d_nset, name_set, n_names * 4, hipMemcpyHostToDevice, ctx->stream));
-            JG_HIP(hipMemcpyAsync(d_nid, name_id, n_names * 4, hipMemcpyHostToDevice, ctx->stream));
-            JG_HIP(hipMemcpyAsync(d_off, off, (n_names + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-            if (nb) JG_HIP(hipMemcpyAsync(w->pool.as<uint8_t>() + w->pool_used, bytes, nb, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_names_put, dim3(blocks_for(n_names)), dim3(kBlock), 0, ctx->stream, names_of(w), w->n_names, w->pool_used, d_nset, d_nid,
-                               d_off, n_names, w->kmask, w->salt);
-            JG_HIP(hipGetLastError());
-        }
-        JG_HIP(hipStreamSynchronize(ctx->stream));
-        w->n_names += n_names;
-        w->id_bound = std::max(w->id_bound, idb);
-        w->pool_used += nb;
-        w->mark();
-    });
-}
 
 int jg_orset_wave_begin(jg_orset* s, uint64_t cap_msgs, uint64_t cap_bytes) {
     return jg::guard([&] {
@@ -2595,7 +1796,6 @@ int jg_orset_wave_append(jg_orset* s, uint64_t n, const uint32_t* set, const uin
         w->wn = m0 + n;
         w->wnb = b0 + nb;
         w->max_set = mx;
-        w->any_set = true;
     });
 }
 
@@ -2612,125 +1812,7 @@ int jg_orset_wave_abort(jg_orset* s) {
         JG_HIP(hipStreamSynchronize(s->ctx->copy));  // the caller's chunk buffers are released after this
         if (s->wire) {
             close_wave(s->wire);
-            s->wire->g0 = s->wire->g1 = s->wire->n_names;
-            s->wire->p0 = s->wire->p1 = s->wire->pool_used;
-        }
-    });
-}
-
-int jg_orset_wave_names(jg_orset* s, uint64_t* n_names, uint64_t* n_bytes, uint32_t* set, uint32_t* id, uint64_t* off, uint8_t* bytes) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
-        JG_REQUIRE(s && n_names && n_bytes, JG_EINVAL, "jg_orset_wave_names: NULL argument");
-        jg_orset_wire* w = s->wire;
-        const uint64_t n = w ? w->g1 - w->g0 : 0, nb = w ? w->p1 - w->p0 : 0;
-        *n_names = n;
-        *n_bytes = nb;
-        if (!set || n == 0) return;
-        JG_REQUIRE(id && off && (bytes || nb == 0), JG_EINVAL, "jg_orset_wave_names: NULL buffer");
-        jg_ctx* ctx = s->ctx;
-        jg::ensure_device(ctx);
-        const auto& o = w->nout;
-        if (o.g0 != o.g1 && o.g0 == w->g0 && o.g1 == w->g1 && o.p0 == w->p0 && o.p1 == w->p1) {  // queued by the commit
-            JG_HIP(hipEventSynchronize(o.ev));
-            const uint8_t* h = o.host;
-            const auto* hlen = reinterpret_cast<const uint32_t*>(h + n * 8);
-            const auto* hpo = reinterpret_cast<const unsigned long long*>(h + jg::round_up(n * 12, 16));
-            const uint8_t* hpool = reinterpret_cast<const uint8_t*>(hpo + n);
-            std::memcpy(set, h, n * 4);
-            std::memcpy(id, h + n * 4, n * 4);
-            off[0] = 0;
-            for (uint64_t i = 0; i < n; ++i) {
-                off[i + 1] = off[i] + hlen[i];
-                if (hlen[i]) std::memcpy(bytes + off[i], hpool + (hpo[i] - w->p0), hlen[i]);
-            }
-            return;
-        }
-        std::vector<uint32_t> len(n);
-        std::vector<unsigned long long> po(n);
-        std::vector<uint8_t> pool(nb);
-        JG_HIP(hipMemcpyAsync(set, w->nset.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        JG_HIP(hipMemcpyAsync(id, w->nid.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        JG_HIP(hipMemcpyAsync(len.data(), w->nlen.as<uint32_t>() + w->g0, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        JG_HIP(hipMemcpyAsync(po.data(), w->noff.as<unsigned long long>() + w->g0, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (nb) JG_HIP(hipMemcpyAsync(pool.data(), w->pool.as<uint8_t>() + w->p0, nb, hipMemcpyDeviceToHost, ctx->stream));
-        JG_HIP(hipStreamSynchronize(ctx->stream));
-        off[0] = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            off[i + 1] = off[i] + len[i];
-            if (len[i]) std::copy(pool.begin() + (po[i] - w->p0), pool.begin() + (po[i] - w->p0) + len[i], bytes + off[i]);
-        }
-    });
-}
-
-int jg_orset_names_since(jg_orset* s, uint64_t from, uint64_t* to, uint64_t* n_bytes, uint32_t* set, uint32_t* id, uint64_t* off, uint8_t* bytes) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(s);
-        JG_REQUIRE(s && to && n_bytes, JG_EINVAL, "jg_orset_names_since: NULL argument");
-        jg_orset_wire* w = s->wire;
-        const uint64_t total = w ? w->n_names : 0;
-        JG_REQUIRE(from <= total, JG_EINVAL, "jg_orset_names_since: from %llu past the %llu names held", (unsigned long long)from,
-                   (unsigned long long)total);
-        *to = total;
-        *n_bytes = 0;
-        const uint64_t n = total - from;
-        if (n == 0) return;
-        jg_ctx* ctx = s->ctx;
-        jg::ensure_device(ctx);
-        auto& o = w->nout;
-        if (!(o.since_from == from && o.since_to == total && o.since_pool1 == w->pool_used)) {
-            // A commit's new names take their pool bytes by atomics (not in name order), so the bytes of names
-            // [from, total) lie in the pool range that starts at the last mark at or before `from` (every name
-            // past a mark was made after it) and ends at pool_used.  One queue of copies into page-locked
-            // staging, one wait; kept for the second call of a size query + fill.
-            uint64_t pool0 = 0;
-            for (auto it = w->marks.rbegin(); it != w->marks.rend(); ++it)
-                if (it->first <= from) { pool0 = it->second; break; }
-            const uint64_t nb = w->pool_used - pool0;
-            const size_t need = names_out_bytes(n, nb);
-            if (o.ev) JG_HIP(hipEventSynchronize(o.ev));
-            o.g0 = o.g1 = 0;  // the staging is reused here: a queued wave-names copy is gone
-            if (o.cap < need) {
-                if (o.host) JG_HIP(hipHostFree(o.host));
-                o.host = nullptr;
-                o.cap = 0;
-                void* p = nullptr;
-                JG_HIP(hipHostMalloc(&p, need + need / 2, hipHostMallocDefault));
-                o.host = static_cast<uint8_t*>(p);
-                o.cap = need + need / 2;
-            }
-            uint8_t* h = o.host;
-            const size_t po = jg::round_up(n * 12, 16);
-            JG_HIP(hipMemcpyAsync(h, w->nset.as<uint32_t>() + from, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            JG_HIP(hipMemcpyAsync(h + n * 4, w->nid.as<uint32_t>() + from, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            JG_HIP(hipMemcpyAsync(h + n * 8, w->nlen.as<uint32_t>() + from, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            JG_HIP(hipMemcpyAsync(h + po, w->noff.as<unsigned long long>() + from, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (nb) JG_HIP(hipMemcpyAsync(h + po + n * 8, w->pool.as<uint8_t>() + pool0, nb, hipMemcpyDeviceToHost, ctx->stream));
-            JG_HIP(hipStreamSynchronize(ctx->stream));
-            const auto* hlen = reinterpret_cast<const uint32_t*>(h + n * 8);
-            const auto* hpo = reinterpret_cast<const unsigned long long*>(h + po);
-            uint64_t sum = 0;
-            for (uint64_t i = 0; i < n; ++i) {
-                JG_REQUIRE(hpo[i] >= pool0 && hpo[i] + hlen[i] <= w->pool_used, JG_ESTATE,
-                           "jg_orset_names_since: name %llu's bytes lie outside the pool range of its log position", (unsigned long long)(from + i));
-                sum += hlen[i];
-            }
-            o.since_from = from, o.since_to = total, o.since_pool0 = pool0, o.since_pool1 = w->pool_used, o.since_bytes = sum;
-        }
-        *n_bytes = o.since_bytes;
-        if (!set) return;
-        JG_REQUIRE(id && off && (bytes || o.since_bytes == 0), JG_EINVAL, "jg_orset_names_since: NULL buffer");
-        const uint8_t* h = o.host;
-        const size_t po = jg::round_up(n * 12, 16);
-        const auto* hlen = reinterpret_cast<const uint32_t*>(h + n * 8);
-        const auto* hpo = reinterpret_cast<const unsigned long long*>(h + po);
-        const uint8_t* hpool = reinterpret_cast<const uint8_t*>(hpo + n);
-        std::memcpy(set, h, n * 4);
-        std::memcpy(id, h + n * 4, n * 4);
-        off[0] = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            off[i + 1] = off[i] + hlen[i];
-            if (hlen[i]) std::memcpy(bytes + off[i], hpool + (hpo[i] - o.since_pool0), hlen[i]);
+            s->wire->names.no_names_issued();
         }
     });
 }
@@ -2744,28 +1826,11 @@ int jg_orset_merge_json(jg_orset* s, uint64_t n, const uint32_t* set, const uint
     if (rc == JG_OK) rc = jg_orset_wave_append(s, n, set, off, bytes);
     if (rc == JG_OK) rc = jg_orset_wave_check(s, bad_msg);
     if (rc != JG_OK) {
-        char keep[1024];
-        jg_last_error(keep, sizeof keep);
+        const std::string keep = last_error();
         jg_orset_wave_abort(s);
-        return jg::guard([&] { jg::fail(rc, "%s", keep); });
+        return jg::guard([&] { jg::fail(rc, "%s", keep.c_str()); });
     }
     return jg_orset_wave_commit(s, n);
-}
-
-
-int jg_orset_encode_json(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* off, uint8_t* out,
-                         uint64_t cap, uint8_t* sha) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(s);  // calls on one context are serialised (shared scratch, stream)
-        JG_REQUIRE(s && off, JG_EINVAL, "jg_orset_encode_json: NULL argument");
-        off[0] = 0;
-        if (n == 0) return;
-        JG_REQUIRE(set, JG_EINVAL, "jg_orset_encode_json: NULL set list");
-        JG_REQUIRE(!add_lim == !rem_lim, JG_EINVAL, "jg_orset_encode_json: add_lim and rem_lim go together");
-        JG_REQUIRE(n < (1ull << 29), JG_EINVAL, "jg_orset_encode_json: at most 2^29 states per call");
-        jg::ensure_device(s->ctx);
-        encode_sets(s, n, set, add_lim, rem_lim, off, out, cap, out ? sha : nullptr);
-    });
 }
 
 }  // extern "C"

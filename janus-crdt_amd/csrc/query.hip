@@ -151,10 +151,12 @@ int jg_node_query_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_
         jg_ctx* ctx = ks->ctx;
         jg::ensure_device(ctx);
         const jg::NodeRef nd = jg::node_query_ref(node, "jg_node_query_keys");  // pending registrations to the device
-        jg::NamesRef R{};
+        jg::ElemTable none;  // a node without an OR-Set store: no name resolves
+        jg::ElemTable* T = &none;
         if (nd.orset) {
             jg::sync_counts(nd.orset);
-            R = jg::orset_names_ref(nd.orset, 0, 0, 0);
+            T = jg::orset_elem_table(nd.orset, true);
+            T->ensure_names(ctx, 0, 0);
         }
 
         // keys, elements, flags and offsets in one staging copy: koff | eoff | flag | key bytes | element bytes
@@ -196,7 +198,7 @@ int jg_node_query_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_
         stamp(1);
         JG_HIP(hipMemsetAsync(o.count, 0, 16, ctx->stream));
         hipLaunchKernelGGL(k_q_resolve, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
-                           nd.pnc ? nd.pnc->n_keys : 0, R.N, nd.orset ? R.set_cap : 0, R.kmask, R.salt, in, n, o);
+                           nd.pnc ? nd.pnc->n_keys : 0, T->view(), T->set_cap, T->kmask, T->salt, in, n, o);
         JG_HIP(hipGetLastError());
         if (nd.pnc) jg::pnc_values_device(nd.pnc, o.prow, n, o.value, o.status, o.pat, o.count, JG_Q_OVERFLOW);
         if (nd.orset) jg::orset_contains_device(nd.orset, o.oq, n, nullptr, o.oat, o.count + 1, o.value);

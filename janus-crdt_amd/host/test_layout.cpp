@@ -1,13 +1,15 @@
 // test_layout.cpp — csrc/layout.hpp on the CPU (no device code): the layout builder, pow2_at_least and the checked
-// narrowings blocks_for / cub_count.  Prints one "ok <check>" line per check and "PASS" at the end; exits 1 at the
-// first failure.  tests/test_layout.py runs it.
+// narrowings blocks_for / cub_count; and csrc/orset_layouts.hpp, the OR-Set wave path's carved blocks.  Prints one
+// "ok <check>" line per check and "PASS" at the end; exits 1 at the first failure.  tests/test_layout.py runs it.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "layout.hpp"
+#include "orset_layouts.hpp"
 
 namespace jg {
 struct Error {
@@ -149,6 +151,89 @@ void test_cub_count() {
     std::printf("ok cub_count\n");
 }
 
+// csrc/orset_layouts.hpp: the three carved blocks of the OR-Set wave path, held to their formulas written out
+uint64_t al(uint64_t b) { return (b + 255) & ~255ull; }
+
+// the fields the carve functions bind (the device structs Claims and Buckets hold the same ones)
+struct Counts {
+    uint32_t* scnt = nullptr;
+    uint32_t* rcnt[2] = {nullptr, nullptr};
+    unsigned long long* sbytes = nullptr;
+};
+struct Items {
+    uint32_t *spos = nullptr, *sset = nullptr, *sitem = nullptr, *rpos = nullptr, *rset = nullptr;
+    uint32_t* ritem[2] = {nullptr, nullptr};
+};
+template <class T> uint64_t off_of(const T* p, const void* base) { return (uint64_t)((uintptr_t)p - (uintptr_t)base); }
+
+void test_orset_layouts() {
+    // offsets of the large blocks are read against a base that is never dereferenced
+    void* const far = reinterpret_cast<void*>(uintptr_t(1) << 40);
+    // the claims' four count arrays of cap + 1 entries
+    for (uint64_t cap : {0ull, 1ull, 62ull, 63ull, 1023ull, 1024ull, 1ull << 20, 0x7FFFFFF0ull - 1}) {
+        Counts K, U;
+        const uint64_t c4 = al((cap + 1) * 4);
+        CHECK(jg::carve_claims(cap, far, K) == 3 * c4 + al((cap + 1) * 8));
+        CHECK(off_of(K.scnt, far) == 0 && off_of(K.rcnt[0], far) == c4 && off_of(K.rcnt[1], far) == 2 * c4 && off_of(K.sbytes, far) == 3 * c4);
+        CHECK(jg::carve_claims(cap, nullptr, U) == 3 * c4 + al((cap + 1) * 8) && U.scnt == nullptr && U.sbytes == nullptr);  // size only
+    }
+    {  // bound to a real block: the last entry of the last array lies inside it
+        Counts K;
+        std::vector<unsigned char> block(jg::carve_claims(62, nullptr, K));
+        jg::carve_claims(62, block.data(), K);
+        CHECK((void*)K.scnt == block.data());
+        K.sbytes[62] = ~0ull;
+        CHECK(off_of(K.sbytes, block.data()) + 63 * 8 <= block.size() && block[off_of(K.sbytes, block.data()) + 62 * 8] == 0xFF);
+    }
+    // the bucket commit's places and orders: three arrays per string-list entry, four per record-list entry
+    for (uint64_t st_cap : {4096ull, 1ull << 20, 1ull << 30})
+        for (uint64_t rt_cap : {4096ull, 1ull << 20, 1ull << 30}) {
+            Items I;
+            const uint64_t s4 = al((st_cap / 8) * 16 * 4 + 4), r4 = al((rt_cap / 8) * 16 * 4 + 4);
+            CHECK(jg::carve_items(st_cap, rt_cap, far, I) == 3 * s4 + 4 * r4);
+            CHECK(off_of(I.spos, far) == 0 && off_of(I.sset, far) == s4 && off_of(I.sitem, far) == 2 * s4);
+            CHECK(off_of(I.rpos, far) == 3 * s4 && off_of(I.rset, far) == 3 * s4 + r4);
+            CHECK(off_of(I.ritem[0], far) == 3 * s4 + 2 * r4 && off_of(I.ritem[1], far) == 3 * s4 + 3 * r4);
+        }
+    {
+        Items I;
+        std::vector<unsigned char> block(jg::carve_items(4096, 4096, nullptr, I));
+        jg::carve_items(4096, 4096, block.data(), I);
+        CHECK((void*)I.spos == block.data());
+        I.ritem[1][(4096 / 8) * 16] = 1;  // the spare entry of the last array
+        CHECK(off_of(I.ritem[1], block.data()) + ((4096 / 8) * 16 + 1) * 4 <= block.size());
+    }
+    static_assert(jg::kLists == 16, "the formulas above write kLists out");
+    // the names staging: set | id | len | pad to 16 | pool offsets | pool bytes
+    for (uint64_t n : {0ull, 1ull, 3ull, 4ull, 5ull})
+        for (uint64_t nb : {0ull, 1ull, 17ull}) {
+            const jg::NamesStaging L(n, nb);
+            const uint64_t po = jg::round_up(12 * n, 16);
+            CHECK(L.bytes == po + 8 * n + nb);
+            CHECK(L.set == 0 && L.id == 4 * n && L.len == 8 * n && L.pool_off == po && L.pool == po + 8 * n);
+        }
+    {  // copy_out: three names whose bytes sit out of name order in the staged pool range [100, 117); one is empty
+        const jg::NamesStaging L(3, 17);
+        std::vector<unsigned char> h(L.bytes, 0);
+        const uint32_t set[3] = {7, 7, 9}, id[3] = {0, 1, 5}, len[3] = {5, 0, 12};
+        const uint64_t at[3] = {112, 105, 100};
+        std::memcpy(h.data() + L.set, set, 12), std::memcpy(h.data() + L.id, id, 12), std::memcpy(h.data() + L.len, len, 12);
+        std::memcpy(h.data() + L.pool_off, at, 24);
+        std::memcpy(h.data() + L.pool, "twelve bytesAhell", 17);  // [100, 112) then [112, 117)
+        uint32_t oset[3], oid[3];
+        uint64_t off[4];
+        unsigned char out[17];
+        CHECK(L.copy_out(h.data(), 100, oset, oid, off, out) == 17);
+        CHECK(std::memcmp(oset, set, 12) == 0 && std::memcmp(oid, id, 12) == 0);
+        CHECK(off[0] == 0 && off[1] == 5 && off[2] == 5 && off[3] == 17);
+        CHECK(std::memcmp(out, "Ahelltwelve bytes", 17) == 0);
+        // no names: nothing written but off[0]
+        off[0] = 9, off[1] = 9;
+        CHECK(jg::NamesStaging(0, 0).copy_out(h.data(), 0, oset, oid, off, out) == 0 && off[0] == 0 && off[1] == 9);
+    }
+    std::printf("ok orset_layouts\n");
+}
+
 }  // namespace
 
 int main() {
@@ -156,6 +241,7 @@ int main() {
     test_round_pow2();
     test_blocks_for();
     test_cub_count();
+    test_orset_layouts();
     std::printf("PASS %d checks\n", g_checks);
     return 0;
 }

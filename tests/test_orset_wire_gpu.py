@@ -456,6 +456,29 @@ def test_names_log_holds_every_wave_and_sync(ctx):
         s.close()
 
 
+@pytest.mark.parametrize("tail", ["default", "sort"])
+def test_wave_names_after_a_names_since_pull(ctx, monkeypatch, tail):
+    """jg_orset_wave_names after jg_orset_names_since took over the page-locked staging the commit had queued its
+    names into: the same names, ids, offsets and bytes the commit issued (an empty string, one written with a \\u
+    escape, a plain one, over two sets), on the table and the sort path."""
+    if tail == "default":
+        monkeypatch.delenv("JANUS_ORSET_TAIL", raising=False)
+    else:
+        monkeypatch.setenv("JANUS_ORSET_TAIL", tail)
+    rest = b',"removeSet":{},"nullAddGuid":[],"nullRemoveGuid":[]}'
+    msgs = [b'{"addSet":{"":["' + _A.encode() + b'"],"caf\\u00e9":["' + _B.encode() + b'"]}' + rest,
+            b'{"addSet":{"plain":["' + _A.encode() + b'"]}' + rest]
+    want = [(0, 0, b""), (0, 1, "café".encode()), (1, 0, b"plain")]
+    s = jg.ORSetStore(ctx)
+    try:
+        s.merge_json([0, 1], msgs)
+        assert s.names_since(0) == (3, want)  # a size query, then the fill: the staging now holds the pull
+        assert s.wave_names() == want
+        assert s.wave_names() == want and s.names_since(1) == (3, want[1:])
+    finally:
+        s.close()
+
+
 def test_element_id_space_limit(ctx):
     """Ids are issued up to 2^32 - 3 (JG_NULL_ELEM - 1 is reserved): a wave that could pass it is rejected with
     JG_ESTATE and nothing applied; one that fits commits."""
