@@ -163,6 +163,20 @@ int jg_pnc_merge_batch(jg_pnc* pnc, const jg_rows* rows, int async);
 int jg_pnc_set_dense_filter(jg_pnc* pnc, int on);
 /* *state = 0: off or cold (no valid copy), 1: armed (the next dense identity merge builds it), 2: valid. */
 int jg_pnc_dense_filter_state(jg_pnc* pnc, int* state);
+/* The narrow form of a received batch (additive entry points, JG_ABI_VERSION stays 10).  An int64 batch without key
+ * indices whose every cell of P and N is ABSENT (INT64_MIN) or in (INT32_MIN, INT32_MAX] is held on the device as
+ * 4-byte codes (INT32_MIN for ABSENT, the value otherwise; a real value of INT32_MIN does not fit), and the dense
+ * identity merge reads 4 bytes per received cell instead of 8.  The form is decided where the batch is born:
+ * jg_rows_upload narrows each chunk as it lands, under the next chunk's copy, and copies the batch again as it is if a
+ * cell did not fit; jg_synth_pnc_rows writes the form an upload of the same cells would have.  Batches with key
+ * indices and int32 batches are always wide.  No device memory is added (the codes live in the batch's own buffers)
+ * and nothing a merge, a route or an exchange returns changes: every reader but the dense merge widens a narrow
+ * batch in place first, after which it is wide until its next upload or synth.
+ * on != 0 (the default) allows the narrow form; 0 widens a narrow batch now (the call waits for the context's queued
+ * work) and pins the batch to the wide form from its next upload or synth on. */
+int jg_rows_set_narrow(jg_rows* rows, int on);
+/* *form = 0: wide (eb-byte cells), 1: narrow. */
+int jg_rows_form(jg_rows* rows, int* form);
 
 /* ---------------------------------------------------------------------------------------------
  * PN-Counter replica table + wire-format apply (csrc/json.hip).  The store keeps, per key, the

@@ -185,7 +185,15 @@ struct jg_rows {
     uint32_t eb;
     bool has_keys = false;
     uint32_t max_key = 0;  // largest key_idx uploaded (validated against the store at merge)
-    jg::DevBuf P, N, keys;
+    // The received cells, [n_rows x R], in one of two forms.  Wide: eb bytes each, over the whole of P_ /
+    // N_.  Narrow (eb == 8 identity batches whose every cell fits, pnc_filter.hpp `fits`): 4-byte codes in the lower
+    // half of P_ / N_; the upper half is free (the upload's staging area).  The dense merge (pnc.hip) reads either form
+    // in place through the raw fields; every other reader takes the arrays from jg::rows_wide, which widens a narrow
+    // batch first.  `narrow` is host state under the context lock; launches are stream-ordered.
+    jg::DevBuf P_, N_, keys;
+    mutable bool narrow = false;
+    bool narrow_on = true;  // jg_rows_set_narrow
+    bool may_narrow() const { return eb == 8 && !has_keys && narrow_on; }  // an upload or synth of fitting cells is narrow
 };
 
 // One sorted tag-record stream in the CHUNKED layout (orset_union.hpp): structure of arrays
@@ -272,6 +280,10 @@ void sync_counts(jg_orset* s);   // fold a pending async count into the host cop
 void set_dense(jg_ctx* ctx, jg_stream_soa& s, uint64_t n);
 // pnc.hip: scatter-max of n_rows device rows into the store's keys (async on the store's stream).
 void pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t* d_keys, uint64_t n_rows);
+// pnc.hip: the batch's P and N as arrays of eb-byte cells for every reader but the dense merge.  A narrow batch is
+// widened in place first (queued on the context's stream) and is wide from then on.
+struct WideRows { const void *P, *N; };
+WideRows rows_wide(const jg_rows* r);
 // pnc.hip: the store grown to at least [n_keys x n_replicas] (jg_pnc_reserve without its open-wave refusals), and
 // one doubling of R under jg_pnc_set_max_replicas' bound (false: at the bound).
 void pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas);

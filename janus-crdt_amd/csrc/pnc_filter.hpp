@@ -1,5 +1,6 @@
 // pnc_filter.hpp — the per-cell arithmetic of the dense PN-Counter merge's 32-bit shadow (HIP-free: the filtered
-// kernel and the build launch in pnc_filter_kernels.hpp and host/test_pnc_filter.cpp share this one definition).
+// kernel and the build launch in pnc_filter_kernels.hpp and host/test_pnc_filter.cpp share this one definition), and
+// of the narrow form of a received cell (fits / narrow / widen: pnc.hip's batch kernels, host/test_pnc_narrow.cpp).
 //
 // The shadow of an int64 cell a is s = clamp32(a).  Strictly inside the int32 range the shadow IS the cell
 // (a == (int64)s), so a merge needs no read of a; at the two clamp values ("escapes") it only bounds it:
@@ -20,6 +21,13 @@ namespace filt {
 constexpr int32_t kLo = INT32_MIN, kHi = INT32_MAX;
 
 JG_FILT_HD int32_t clamp32(long long v) { return v < (long long)kLo ? kLo : v > (long long)kHi ? kHi : (int32_t)v; }
+
+// The narrow form of a received int64 cell b (a dense identity batch held as 4-byte codes, jg_rows): b fits if it is
+// ABSENT (INT64_MIN) or INT32_MIN < b <= INT32_MAX; its code is INT32_MIN for ABSENT and (int32)b otherwise, so a real
+// value of exactly INT32_MIN does not fit (that code is taken).  widen(narrow(b)) == b for every fitting b.
+JG_FILT_HD bool fits(long long b) { return b == INT64_MIN || (b > (long long)kLo && b <= (long long)kHi); }
+JG_FILT_HD int32_t narrow(long long b) { return b == INT64_MIN ? kLo : (int32_t)b; }
+JG_FILT_HD long long widen(int32_t c) { return c == kLo ? INT64_MIN : (long long)c; }
 
 // The shadow value determines the cell.
 JG_FILT_HD bool known(int32_t s) { return s != kLo && s != kHi; }

@@ -47,6 +47,23 @@ template <int CPL> __device__ __forceinline__ void st_shadow(int* S, uint64_t un
     else __builtin_nontemporal_store(v4i{s[0], s[1], s[2], s[3]}, reinterpret_cast<v4i*>(S) + unit);
 }
 
+// A lane's CPL consecutive cells of the received batch in its form (jg_rows): BT = long long, the cells themselves;
+// BT = int, the narrow form's 4-byte codes (pnc_filter.hpp `narrow`), one 8-B or 16-B vector widened in registers.
+template <int CPL, class BT> __device__ __forceinline__ void ld_batch(const BT* B, uint64_t unit, long long (&b)[CPL]) {
+    if constexpr (sizeof(BT) == 8) {
+        ld_cells<CPL>(B, unit, b);
+    } else {
+        int c[CPL];
+        ld_shadow<CPL>(B, unit, c);
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) b[k] = widen(c[k]);
+    }
+}
+template <class BT> __device__ __forceinline__ long long batch_cell(const BT* B, uint64_t at) {
+    if constexpr (sizeof(BT) == 8) return B[at];
+    else return widen(B[at]);
+}
+
 // Any lane of this lane's aligned group of G lanes set in the wave's ballot `mask` (G lanes x CPL cells = one 128-B
 // line of A: the unit a store is elided by, as k_merge_dense's kElideLanes).
 template <uint32_t G> __device__ __forceinline__ bool group_any(unsigned long long mask, uint32_t lane) {
@@ -65,16 +82,17 @@ __device__ __forceinline__ void merge_tail_cell(long long* a, int* s, long long 
 // halves of `half` workgroups as k_merge_dense's: P's, then N's.  A lane reads the shadows and B of VECS units,
 // BLOCK apart, every load issued before the first use, and A only for a 128-B line that holds an escape cell while
 // a cell of the line may change (rare: the escape path is exact, not fast).  A line of A is written whole or not at
-// all; the shadow's 64 B of the line are written with it.
-template <int CPL, int VECS, int BLOCK>
+// all; the shadow's 64 B of the line are written with it.  BT: the batch's cell type (ld_batch); everything after the
+// load is the same code for both forms.
+template <int CPL, int VECS, int BLOCK, class BT = long long>
 __global__ __launch_bounds__(BLOCK) void k_merge_filtered(long long* __restrict__ AP, long long* __restrict__ AN, int* __restrict__ SP,
-                                                          int* __restrict__ SN, const long long* __restrict__ BP,
-                                                          const long long* __restrict__ BN, uint64_t n_units, uint32_t tail, uint32_t half) {
+                                                          int* __restrict__ SN, const BT* __restrict__ BP,
+                                                          const BT* __restrict__ BN, uint64_t n_units, uint32_t tail, uint32_t half) {
     constexpr uint32_t G = 16 / CPL;
     const bool isN = blockIdx.x >= half;
     long long* const A = isN ? AN : AP;
     int* const S = isN ? SN : SP;
-    const long long* const B = isN ? BN : BP;
+    const BT* const B = isN ? BN : BP;
     const uint32_t blk = blockIdx.x - (isN ? half : 0);
     const uint64_t base = (uint64_t)blk * (VECS * BLOCK) + threadIdx.x;
     int s[VECS][CPL];
@@ -86,7 +104,7 @@ __global__ __launch_bounds__(BLOCK) void k_merge_filtered(long long* __restrict_
         in[u] = i < n_units;
 #pragma unroll
         for (int k = 0; k < CPL; ++k) s[u][k] = 0, b[u][k] = INT64_MIN;  // a lane past the end: nothing may change
-        if (in[u]) ld_shadow<CPL>(S, i, s[u]), ld_cells<CPL>(B, i, b[u]);
+        if (in[u]) ld_shadow<CPL>(S, i, s[u]), ld_batch<CPL>(B, i, b[u]);
     }
     const uint32_t lane = threadIdx.x & 63;
 #pragma unroll
@@ -113,25 +131,25 @@ __global__ __launch_bounds__(BLOCK) void k_merge_filtered(long long* __restrict_
     }
     if (blk == 0 && threadIdx.x < tail) {
         const uint64_t at = n_units * CPL + threadIdx.x;
-        merge_tail_cell(A + at, S + at, B[at]);
+        merge_tail_cell(A + at, S + at, batch_cell(B, at));
     }
 }
 
 // The build launch: k_merge_dense's int64 merge (A and B read, the raised 128-B lines of A written back) plus the
-// shadow of every cell of the batch, written unconditionally.  Two cells per lane, two halves.
-template <int BLOCK>
+// shadow of every cell of the batch, written unconditionally.  Two cells per lane, two halves.  BT as above.
+template <int BLOCK, class BT = long long>
 __global__ __launch_bounds__(BLOCK) void k_merge_build(long long* __restrict__ AP, long long* __restrict__ AN, int* __restrict__ SP,
-                                                       int* __restrict__ SN, const long long* __restrict__ BP, const long long* __restrict__ BN,
+                                                       int* __restrict__ SN, const BT* __restrict__ BP, const BT* __restrict__ BN,
                                                        uint64_t n_units, uint32_t tail, uint32_t half) {
     const bool isN = blockIdx.x >= half;
     long long* const A = isN ? AN : AP;
     int* const S = isN ? SN : SP;
-    const long long* const B = isN ? BN : BP;
+    const BT* const B = isN ? BN : BP;
     const uint32_t blk = blockIdx.x - (isN ? half : 0);
     const uint64_t i = (uint64_t)blk * BLOCK + threadIdx.x;
     const bool in = i < n_units;
     long long a[2] = {0, 0}, b[2] = {INT64_MIN, INT64_MIN};
-    if (in) ld_cells<2>(A, i, a), ld_cells<2>(B, i, b);
+    if (in) ld_cells<2>(A, i, a), ld_batch<2>(B, i, b);
     const Merged r0 = merge_cell(a[0], b[0]), r1 = merge_cell(a[1], b[1]);
     const unsigned long long c = __ballot(r0.changed || r1.changed);
     if (in) {
@@ -142,7 +160,7 @@ __global__ __launch_bounds__(BLOCK) void k_merge_build(long long* __restrict__ A
     }
     if (blk == 0 && threadIdx.x < tail) {
         const uint64_t at = n_units * 2 + threadIdx.x;
-        const Merged r = merge_cell(A[at], B[at]);
+        const Merged r = merge_cell(A[at], batch_cell(B, at));
         if (r.changed) A[at] = r.m;
         S[at] = r.s;
     }

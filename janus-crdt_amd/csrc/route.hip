@@ -271,11 +271,13 @@ void route_rows(jg_ctx* ctx, const jg_rows* r, uint32_t world, uint64_t* counts,
     const RowOwner own{keys, world};
     const Tiles tl{r->n_rows, nullptr, kRowTile};
     const uint64_t* pos = route_plan(ctx, own, tl, n_tiles, world, counts);
+    const jg::WideRows w = jg::rows_wide(r);  // a narrow batch is widened first: the movers copy whole int64 rows
+    const char *wP = static_cast<const char*>(w.P), *wN = static_cast<const char*>(w.N);
     if (((uint64_t)r->R * EB) % 16 == 0) {
-        const RowMover<EB, true> mv{keys, r->P.as<char>(), r->N.as<char>(), (uint32_t*)dk, (char*)dP, (char*)dN, r->R, world};
+        const RowMover<EB, true> mv{keys, wP, wN, (uint32_t*)dk, (char*)dP, (char*)dN, r->R, world};
         hipLaunchKernelGGL((k_route_scatter<RowOwner, RowMover<EB, true>>), dim3(n_tiles), dim3(kRB), 0, ctx->stream, own, tl, n_tiles, pos, mv);
     } else {
-        const RowMover<EB, false> mv{keys, r->P.as<char>(), r->N.as<char>(), (uint32_t*)dk, (char*)dP, (char*)dN, r->R, world};
+        const RowMover<EB, false> mv{keys, wP, wN, (uint32_t*)dk, (char*)dP, (char*)dN, r->R, world};
         hipLaunchKernelGGL((k_route_scatter<RowOwner, RowMover<EB, false>>), dim3(n_tiles), dim3(kRB), 0, ctx->stream, own, tl, n_tiles, pos,
                            mv);
     }

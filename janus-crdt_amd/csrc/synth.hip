@@ -77,7 +77,11 @@ int jg_synth_pnc_rows(jg_rows* r, uint64_t seed, uint64_t key0) {
         auto lk_ = jg::lock(r);  // calls on one context are serialised (shared scratch, stream)
         JG_REQUIRE(r, JG_EINVAL, "jg_synth_pnc_rows: rows is NULL");
         jg::ensure_device(r->ctx);
-        fill_pnc(r->ctx, r->eb, r->P.p, r->N.p, key0, r->n_rows, r->R, 2, seed);  // key indices (if uploaded) are kept
+        // key indices (if uploaded) are kept.  The batch takes the form an upload of the same cells would (jg_rows): a
+        // received cell is ABSENT or below 2^31 - 1, so every cell fits, and the int32 generator's cell (INT32_MIN for
+        // ABSENT, the same value otherwise) is the int64 cell's code: an int64 identity batch is written narrow in one pass.
+        r->narrow = r->may_narrow();
+        fill_pnc(r->ctx, r->narrow ? 4 : r->eb, r->P_.p, r->N_.p, key0, r->n_rows, r->R, 2, seed);
         JG_HIP(hipStreamSynchronize(r->ctx->stream));
     });
 }

@@ -48,6 +48,7 @@ EXPORTS = [
     "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
+    "jg_rows_set_narrow", "jg_rows_form",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -176,6 +177,8 @@ _SIGS = {
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
     "jg_pnc_set_dense_filter": ([_vp, C.c_int], C.c_int),
     "jg_pnc_dense_filter_state": ([_vp, C.POINTER(C.c_int)], C.c_int),
+    "jg_rows_set_narrow": ([_vp, C.c_int], C.c_int),
+    "jg_rows_form": ([_vp, C.POINTER(C.c_int)], C.c_int),
 }
 GUID_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])  # jg_guid
 
@@ -318,6 +321,17 @@ class Rows:
 
     def synth(self, seed: int, key0: int = 0) -> None:
         _check(load().jg_synth_pnc_rows(self._h, seed, key0))
+
+    # ---- the narrow form (jg_rows_set_narrow / jg_rows_form) ----
+    def set_narrow(self, on: bool) -> None:
+        """Allow (default) or forbid holding an int64 identity batch whose cells fit as 4-byte codes; off widens it now."""
+        _check(load().jg_rows_set_narrow(self._h, 1 if on else 0))
+
+    def form(self) -> int:
+        """0 wide (cells of the batch's width), 1 narrow (4-byte codes the dense merge reads in place)."""
+        f = C.c_int(-1)
+        _check(load().jg_rows_form(self._h, C.byref(f)))
+        return int(f.value)
 
     def route(self, world: int, d_keys: int, d_P: int, d_N: int, cap_rows: int | None = None) -> np.ndarray:
         """jg_rows_route: stable partition of the batch by owner rank (key % world) into caller DEVICE

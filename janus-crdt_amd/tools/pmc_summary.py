@@ -87,13 +87,15 @@ def dense_split(path, counter, kernel="k_merge_dense<8>"):
 
 def filter_split(path, counter):
     """The dense merge's counter values (bytes) of an int64 store that merges by its 32-bit shadow, in dispatch order:
-    the first launch after the synthesis is k_merge_dense<8> as ever, the second builds the shadow (k_merge_build),
-    the later ones are the filtered kernel's (k_merge_filtered): the steady state the bench times."""
+    the first launch after the synthesis is k_merge_dense<8> as ever (k_merge_dense_narrow where the batch is held as
+    4-byte codes), the second builds the shadow (k_merge_build), the later ones are the filtered kernel's
+    (k_merge_filtered): the steady state the bench times."""
     with open(path) as f:
         rows = sorted((r for r in csv.DictReader(f) if r["Counter_Name"] == counter), key=lambda r: int(r["Dispatch_Id"]))
     out = {"first": [], "build": [], "steady": []}
     for r in rows:
-        for kernel, key in (("k_merge_dense<8>", "first"), ("k_merge_build<", "build"), ("k_merge_filtered<", "steady")):
+        for kernel, key in (("k_merge_dense<8>", "first"), ("k_merge_dense_narrow", "first"), ("k_merge_build<", "build"),
+                            ("k_merge_filtered<", "steady")):
             if kernel in r["Kernel_Name"]:
                 out[key].append(float(r["Counter_Value"]) * 1024)
     return out

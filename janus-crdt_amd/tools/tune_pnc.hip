@@ -4,6 +4,8 @@
 // `tune_pnc <rounds> steady`: the read-only steady state bench.py times (data x cadence, then the read-side shapes).
 // `tune_pnc <rounds> filter`: the merge by the 32-bit shadow (csrc/pnc_filter_kernels.hpp, the library's own kernels
 // in several shapes) and its build launch beside the parent's kernel.
+// `tune_pnc <rounds> narrow`: the same merge of a batch held as 4-byte codes (the narrow form) in 2- and 4-cell shapes
+// beside the wide batch's kernel.
 // Build: make -C janus-crdt_amd build/tune_pnc (hipcc -O3 --offload-arch=gfx950) ; run on the GPU box.
 #include <hip/hip_runtime.h>
 
@@ -736,6 +738,126 @@ int filter_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int roun
     return ok ? 0 : 1;
 }
 
+// ---- the merge of a narrow batch (`tune_pnc <rounds> narrow`) -------------------------------------------------------
+// The `filter` mode's data and three patterns with B held twice: wide (BP / BN) and as the narrow form's 4-byte codes
+// (CP / CN, rewritten untimed behind every fill).  The parent's wide-batch kernel (the library's filtered shape
+// reading 8-byte cells of B) runs first and last: the difference of its two medians is the A/A spread.  The variants
+// between read the codes in 2- and 4-cell shapes at 256 and 512 lanes; the build launch and the unfiltered kernel's
+// narrow instantiation are not shaped here (they run once per cold spell).
+__global__ __launch_bounds__(256) void k_codes(const long long* B, int* C, unsigned long long n, unsigned* bad) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (!jg::filt::fits(B[i])) atomicAdd(bad, 1u);
+    C[i] = jg::filt::narrow(B[i]);
+}
+
+struct NVariant {
+    const char* name;
+    void (*launch)(v2*, v2*, int*, int*, const v2*, const v2*, const int*, const int*, unsigned long long, hipStream_t);
+};
+void LN_parent(v2* ap, v2* an, int* sp, int* sn, const v2* bp, const v2* bn, const int*, const int*, unsigned long long n_cells, hipStream_t s) {
+    LF<2, 1, 512>(ap, an, sp, sn, bp, bn, n_cells, s);
+}
+template <int CPL, int VECS, int BLOCK>
+void LN(v2* ap, v2* an, int* sp, int* sn, const v2*, const v2*, const int* cp, const int* cn, unsigned long long n_cells, hipStream_t s) {
+    const unsigned long long nu = n_cells / CPL;
+    const unsigned half = blocks_of(nu, (unsigned long long)VECS * BLOCK);
+    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CPL, VECS, BLOCK, int>), dim3(2 * half), dim3(BLOCK), 0, s, (long long*)ap, (long long*)an, sp, sn,
+                       cp, cn, nu, (unsigned)(n_cells - nu * CPL), half);
+}
+
+int narrow_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int rounds) {
+    const unsigned long long n_cells = nv * 2;
+    hipStream_t s;
+    CK(hipStreamCreate(&s));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    if (rounds > 500) rounds = 500;  // the generation stays below 2^16 (k_fill_f)
+    int *SP, *SN, *CP, *CN;
+    CK(hipMalloc(&SP, n_cells * 4)); CK(hipMalloc(&SN, n_cells * 4)); CK(hipMalloc(&CP, n_cells * 4)); CK(hipMalloc(&CN, n_cells * 4));
+    unsigned* bad;  // [0] cells of A behind B, [1] cells whose shadow is not their clamp, [2] cells of B that do not fit
+    CK(hipMalloc(&bad, 12));
+    CK(hipMemsetAsync(bad, 0, 12, s));
+    const unsigned g256 = (unsigned)((nv + 255) / 256), gc = (unsigned)((n_cells + 255) / 256);
+    const std::vector<NVariant> vs = {
+        {"parent (wide B, 2 cells B512)", LN_parent},
+        {"narrow 2 cells U1 B256", LN<2, 1, 256>},
+        {"narrow 2 cells U1 B512", LN<2, 1, 512>},
+        {"narrow 2 cells U2 B256", LN<2, 2, 256>},
+        {"narrow 2 cells U4 B256", LN<2, 4, 256>},
+        {"narrow 2 cells U2 B512", LN<2, 2, 512>},
+        {"narrow 4 cells U1 B256", LN<4, 1, 256>},
+        {"narrow 4 cells U1 B512", LN<4, 1, 512>},
+        {"parent (again)", LN_parent},
+    };
+    const size_t nvar = vs.size();
+    const auto clamp_all = [&] {
+        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(num_cus * 16), dim3(256), 0, s, (const long long*)AP, SP, 0ull, n_cells);
+        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(num_cus * 16), dim3(256), 0, s, (const long long*)AN, SN, 0ull, n_cells);
+    };
+    const auto codes = [&] {
+        hipLaunchKernelGGL(k_codes, dim3(gc), dim3(256), 0, s, (const long long*)BP, CP, n_cells, bad + 2);
+        hipLaunchKernelGGL(k_codes, dim3(gc), dim3(256), 0, s, (const long long*)BN, CN, n_cells, bad + 2);
+    };
+    const auto check = [&] {
+        hipLaunchKernelGGL(k_count_behind, dim3(g256), dim3(256), 0, s, AP, AN, BP, BN, nv, bad);
+        hipLaunchKernelGGL(k_count_shadow, dim3(gc), dim3(256), 0, s, (const long long*)AP, SP, n_cells, bad + 1);
+        hipLaunchKernelGGL(k_count_shadow, dim3(gc), dim3(256), 0, s, (const long long*)AN, SN, n_cells, bad + 1);
+    };
+    const auto launch = [&](const NVariant& v) { v.launch(AP, AN, SP, SN, BP, BN, CP, CN, n_cells, s); };
+    // the bench's data: A merged once, its shadow exact
+    hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, AP, AN, nv, 0u);
+    hipLaunchKernelGGL(k_synth, dim3(g256), dim3(256), 0, s, BP, BN, nv, 2u);
+    codes();
+    clamp_all();
+    launch(vs[0]);
+    std::vector<std::vector<float>> t0(nvar), t1(nvar), t2(nvar);
+    for (int r = -1; r < rounds; ++r)  // 0 %: 5 untimed launches, a fence, 20 launches between one event pair
+        for (size_t k = 0; k < nvar; ++k) {
+            for (int i = 0; i < 5; ++i) launch(vs[k]);
+            CK(hipStreamSynchronize(s));
+            CK(hipEventRecord(e0, s));
+            for (int i = 0; i < 20; ++i) launch(vs[k]);
+            CK(hipEventRecord(e1, s));
+            CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (r >= 0) t0[k].push_back(ms / 20);
+            else check();
+        }
+    long long gen = 0;
+    for (int pat = 1; pat <= 2; ++pat)
+        for (int r = -1; r < rounds; ++r)
+            for (size_t k = 0; k < nvar; ++k) {
+                hipLaunchKernelGGL(k_fill_f, dim3(g256), dim3(256), 0, s, BP, BN, nv, pat, ++gen);
+                codes();
+                clamp_all();
+                CK(hipEventRecord(e0, s));
+                launch(vs[k]);
+                CK(hipEventRecord(e1, s));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                if (r >= 0) (pat == 1 ? t1 : t2)[k].push_back(ms);
+                else check();
+            }
+    std::printf("C2 shape: 10M keys x 64 replicas, int64, the bench's cells (A merged once); median of %d rounds, ms per launch\n", rounds);
+    std::printf("%-32s %22s %22s %22s\n", "", "0 % (back to back)", "one column per key", "100 %");
+    std::printf("%-32s %22s %22s %22s\n", "variant", "", "(behind a fill)", "(behind a fill)");
+    for (size_t k = 0; k < nvar; ++k) std::printf("%-32s %22.3f %22.3f %22.3f\n", vs[k].name, median(t0[k]), median(t1[k]), median(t2[k]));
+    std::printf("%-32s %22.3f %22.3f %22.3f\n", "A/A spread (parent twice)", std::fabs(median(t0[0]) - median(t0[nvar - 1])),
+                std::fabs(median(t1[0]) - median(t1[nvar - 1])), std::fabs(median(t2[0]) - median(t2[nvar - 1])));
+    for (size_t k = 0; k < nvar; ++k)
+        std::printf("%-32s %10.3f .. %-10.3f %10.3f .. %-10.3f %10.3f .. %-10.3f (min .. max of rounds)\n", vs[k].name,
+                    *std::min_element(t0[k].begin(), t0[k].end()), *std::max_element(t0[k].begin(), t0[k].end()),
+                    *std::min_element(t1[k].begin(), t1[k].end()), *std::max_element(t1[k].begin(), t1[k].end()),
+                    *std::min_element(t2[k].begin(), t2[k].end()), *std::max_element(t2[k].begin(), t2[k].end()));
+    unsigned h[3] = {0, 0, 0};
+    CK(hipMemcpy(h, bad, 12, hipMemcpyDeviceToHost));
+    const bool ok = h[0] == 0 && h[1] == 0 && h[2] == 0;
+    std::printf("vectors of A left behind B over every variant and pattern: %u; cells whose shadow is not their clamp: %u; cells of B that do not fit: %u%s\n",
+                h[0], h[1], h[2], ok ? " (ok)" : " (WRONG)");
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     const unsigned long long n_cells = 10000000ull * 64, nv = n_cells / 2;
     hipDeviceProp_t prop;
@@ -745,6 +867,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&AP, nv * 16)); CK(hipMalloc(&AN, nv * 16)); CK(hipMalloc(&BP, nv * 16)); CK(hipMalloc(&BN, nv * 16));
     if (argc > 2 && std::string(argv[2]) == "elide") return elide_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
     if (argc > 2 && std::string(argv[2]) == "filter") return filter_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
+    if (argc > 2 && std::string(argv[2]) == "narrow") return narrow_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
     if (argc > 2 && std::string(argv[2]) == "steady") return steady_sweep(AP, AN, BP, BN, nv, std::atoi(argv[1]) > 0 ? std::atoi(argv[1]) : 7);
     CK(hipMemset(AP, 1, nv * 16)); CK(hipMemset(AN, 2, nv * 16)); CK(hipMemset(BP, 3, nv * 16)); CK(hipMemset(BN, 0, nv * 16));
     std::vector<Variant> vs = {
