@@ -100,6 +100,34 @@ struct DevBuf {
 
 }  // namespace jg
 
+struct jg_pnc;
+namespace jg {
+// pnc_dense.hip: a dense identity merge of n_rows device rows into the store (async on the store's stream): the one
+// writer of P / N that does not go through rw_P / rw_N, and the one function that advances the shadow's state.
+// narrow: the batch is an int64 batch's 4-byte codes (jg_rows).
+void pnc_merge_dense(jg_pnc* p, const void* BP, const void* BN, uint64_t n_rows, bool narrow);
+
+// The dense merge's shadow of an int64 store: sP / sN = clamp32 of every cell of P / N, int32
+// [n_keys x R], a cache the dense identity merge reads instead of P / N.  cold: no valid shadow (the buffers may be
+// kept); armed: the last write to the store was a dense identity merge; valid: the shadow is exact.  Host state under
+// the context lock; launches are stream-ordered, so a state set here holds for every later launch.  No file but
+// pnc_dense.hip reads the buffers.
+struct DenseShadow {
+    enum State : uint8_t { kCold = 0, kArmed = 1, kValid = 2 };
+    DevBuf sP, sN;
+    bool on = true;      // jg_pnc_set_dense_filter
+    bool nomem = false;  // the shadow did not fit on the device at this shape: not asked for again until it changes
+    State state() const { return state_; }
+    void invalidate() { state_ = kCold; }  // another writer has P / N (jg_pnc::rw_P / rw_N)
+    void drop();                           // the buffers go too: the store's shape changed, or the filter was set off
+    bool ready(size_t bytes);              // the buffers hold `bytes` each (false: no room on the device)
+
+private:
+    friend void pnc_merge_dense(jg_pnc*, const void*, const void*, uint64_t, bool);
+    State state_ = kCold;
+};
+}  // namespace jg
+
 // ---- handle types (opaque at the ABI) ------------------------------------------------------------
 struct jg_ctx {
     int device = 0;
@@ -136,22 +164,14 @@ struct jg_pnc {
     uint32_t eb;  // elem bytes (4 | 8)
     uint32_t max_R = 0;  // jg_pnc_set_max_replicas: a row-capacity failure widens R up to this (0: fixed shape)
     // The counters, [n_keys x R] of eb bytes each.  Reached through the accessors only: ro_P / ro_N for launches and
-    // copies that read, rw_P / rw_N for everything that may write, which drops the dense merge's shadow (below).
-    // The filtered dense merge itself (pnc.hip), which keeps the shadow exact, is the one user of the raw fields.
+    // copies that read, rw_P / rw_N for everything that may write, which invalidates the dense merge's shadow.
+    // The dense merge itself (pnc_dense.hip), which keeps the shadow exact, is the one user of the raw fields.
     jg::DevBuf P_, N_;
     const void* ro_P() const { return P_.p; }
     const void* ro_N() const { return N_.p; }
-    void* rw_P() { filt = kFiltCold; return P_.p; }
-    void* rw_N() { filt = kFiltCold; return N_.p; }
-    // Dense merge filter (eb == 8 only): sP / sN = clamp32 of every cell of P / N, int32 [n_keys x R],
-    // a cache the dense identity merge reads instead of P / N.  cold: no valid shadow (the buffers may be kept);
-    // armed: the last write to the store was a dense identity merge; valid: the shadow is exact.  Host state under
-    // the context lock; launches are stream-ordered, so a flag cleared here holds for every later launch.
-    enum : uint8_t { kFiltCold = 0, kFiltArmed = 1, kFiltValid = 2 };
-    jg::DevBuf sP, sN;
-    uint8_t filt = kFiltCold;
-    bool filt_on = true;      // jg_pnc_set_dense_filter
-    bool filt_nomem = false;  // the shadow did not fit on the device at this shape: not asked for again until it changes
+    void* rw_P() { shadow.invalidate(); return P_.p; }
+    void* rw_N() { shadow.invalidate(); return N_.p; }
+    jg::DenseShadow shadow;  // eb == 8 only
     // replica table (json.hip): [n_keys x R] 16-byte Guids + [n_keys] column counts, first use only
     jg::DevBuf cols, ncols;
     // grouped indexed merge (k_group_*): per-key list head of the batch being merged (gen << 32 | row,
@@ -187,9 +207,9 @@ struct jg_rows {
     uint32_t max_key = 0;  // largest key_idx uploaded (validated against the store at merge)
     // The received cells, [n_rows x R], in one of two forms.  Wide: eb bytes each, over the whole of P_ /
     // N_.  Narrow (eb == 8 identity batches whose every cell fits, pnc_filter.hpp `fits`): 4-byte codes in the lower
-    // half of P_ / N_; the upper half is free (the upload's staging area).  The dense merge (pnc.hip) reads either form
-    // in place through the raw fields; every other reader takes the arrays from jg::rows_wide, which widens a narrow
-    // batch first.  `narrow` is host state under the context lock; launches are stream-ordered.
+    // half of P_ / N_; the upper half is free (the upload's staging area).  The dense merge (pnc_dense.hip) reads either
+    // form in place through the raw fields; every other reader takes the arrays from jg::rows_wide, which widens a
+    // narrow batch first.  `narrow` is host state under the context lock; launches are stream-ordered.
     jg::DevBuf P_, N_, keys;
     mutable bool narrow = false;
     bool narrow_on = true;  // jg_rows_set_narrow
@@ -265,6 +285,7 @@ template <class H> inline CtxLock lock(const H* h) { return lock(h ? h->ctx : nu
 template <class S> inline void require_writable(const S* s, const char* fn) {
     JG_REQUIRE(!s || !s->node_open, JG_EINVAL, "%s: a node wave (jg_apply_stream_begin .. _end) holds this store", fn);
 }
+inline void check_store(const jg_pnc* p, const char* fn) { JG_REQUIRE(p, JG_EINVAL, "%s: store is NULL", fn); }
 void ensure_device(jg_ctx* ctx);  // hipSetDevice(ctx->device) on the calling thread
 void* scratch(jg_ctx* ctx, DevBuf& b, size_t bytes);
 // After H2D copies queued on ctx->copy: make ctx->stream wait for them (stream order for the kernels
@@ -280,7 +301,7 @@ void sync_counts(jg_orset* s);   // fold a pending async count into the host cop
 void set_dense(jg_ctx* ctx, jg_stream_soa& s, uint64_t n);
 // pnc.hip: scatter-max of n_rows device rows into the store's keys (async on the store's stream).
 void pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t* d_keys, uint64_t n_rows);
-// pnc.hip: the batch's P and N as arrays of eb-byte cells for every reader but the dense merge.  A narrow batch is
+// pnc_dense.hip: the batch's P and N as arrays of eb-byte cells for every reader but the dense merge.  A narrow batch is
 // widened in place first (queued on the context's stream) and is wide from then on.
 struct WideRows { const void *P, *N; };
 WideRows rows_wide(const jg_rows* r);

@@ -1,5 +1,6 @@
 // layout.hpp — host-side sizing helpers that need no HIP type: rounding, pow2_at_least, the checked narrowings
-// of a launch grid and of a hipcub item count, and the builder that carves one block into aligned arrays.
+// of a launch grid and of a hipcub item count, the two-halves grid of the dense PN-Counter merges, and the builder
+// that carves one block into aligned arrays.
 // launch.hpp adds the parts that touch a context or a stream; host/test_layout.cpp tests this file with g++ alone.
 #pragma once
 
@@ -29,6 +30,21 @@ inline unsigned blocks_for(uint64_t n, unsigned block = 256) {
     const uint64_t g = n / block + (n % block != 0);
     if (g > (uint64_t)INT_MAX) fail(JG_EINVAL, "%llu items in workgroups of %u exceed one launch (2^31 - 1)", (unsigned long long)n, block);
     return g ? (unsigned)g : 1u;
+}
+
+// The grid of a dense PN-Counter merge over n_cells cells per array (pnc_dense_kernels.hpp): two halves of `blocks`
+// workgroups, P's then N's, each workgroup taking units_per_block units of cells_per_unit cells; a half's first takes
+// the `tail` cells past the last whole unit, so a half has at least one.  fits(): both halves go into one launch.
+struct Halves {
+    uint64_t n_units;  // whole units per array
+    uint32_t tail;     // trailing cells (< cells_per_unit)
+    uint64_t blocks;   // workgroups per half (at least one)
+    bool fits() const { return 2 * blocks < 0xFFFFFFFFull; }
+};
+inline Halves halves_of(uint64_t n_cells, uint32_t cells_per_unit, uint64_t units_per_block) {
+    const uint64_t n_units = n_cells / cells_per_unit;
+    const uint64_t blocks = n_units / units_per_block + (n_units % units_per_block != 0);
+    return Halves{n_units, (uint32_t)(n_cells - n_units * cells_per_unit), blocks ? blocks : 1};
 }
 
 // A hipcub item count: hipcub's entry points are instantiated for int here.

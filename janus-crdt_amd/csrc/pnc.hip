@@ -3,26 +3,8 @@
 // Layout in HBM: P and N are row-major [n_keys x R] arrays of the store's width (int32 = the
 // reference's `int`, int64 = the BASELINE variant).  Row = interned key, column = interned replica.
 //
+// The dense identity merge (jg::pnc_merge_dense, its shadow, the received batch's handle) is csrc/pnc_dense.hip's.
 // Kernels and their roofline (HBM):
-//   k_merge_dense    A = max(A, B) over identity rows.  Reads A.P A.N B.P B.N: 4 x elem_bytes per cell
-//                    (32 B at int64), and writes back only the 128-B lines of A.P / A.N that a cell of B
-//                    raised: up to 2 x elem_bytes more (48 B per cell when every line changes, 32 B for a
-//                    re-delivered batch).  Two halves of one grid: P's workgroups, then N's (two read streams
-//                    at a time); kDenseVecs 16-B vectors of A and of B per lane, non-temporal.  This is
-//                    PNCounter.Merge (PNCounters.cs:131-144).
-//   k_merge_filtered (pnc_filter_kernels.hpp) the same merge of an int64 store by its 32-bit shadow sP / sN = clamp32(P / N):
-//                    reads sA.P sA.N B.P B.N, 24 B per cell, and A itself only for lines that hold a cell at a clamp
-//                    value; writes the raised lines of A with their 64 B of shadow.  From the third consecutive dense
-//                    identity merge on (merge_dense_store: cold -> armed -> valid; k_merge_build writes the shadow
-//                    at the second); every other writer of P / N takes them through jg_pnc::rw_P / rw_N, which
-//                    drops the shadow.
-//   the narrow form  an int64 identity batch (jg_rows) whose every cell is ABSENT or fits 32 bits is held as 4-byte codes
-//                    (pnc_filter.hpp `narrow`), decided where the batch is born: jg_rows_upload narrows each landed chunk
-//                    under the next chunk's copy (k_rows_narrow), jg_synth_pnc_rows writes the codes.  The three dense
-//                    kernels read it in place and widen in registers (k_merge_dense_narrow, k_merge_build / k_merge_filtered
-//                    with BT = int): a steady launch reads sA and B at 4 B each, 16 B per cell (P and N), the first launch
-//                    and the build launch 8 B less per cell than with a wide batch.  Every other reader goes through
-//                    jg::rows_wide, which widens the batch in place first.
 //   k_merge_indexed  scatter-max of received rows into their keys (atomicMax: rows may repeat a
 //                    key inside one committed batch, SafeCRDTManager.cs:122-146).
 //   k_apply_ops      Increment/Decrement (PNCounters.cs:97-112): wrapping atomic adds.
@@ -35,131 +17,18 @@
 #include <cstdlib>
 
 #include "launch.hpp"
-#include "pnc_filter_kernels.hpp"
+#include "pnc_vec.hpp"
 
 namespace {
 
+using jg::check_store;
+using namespace jg::filt;  // pnc_vec.hpp: nt_ld / nt_st, vmax, differs, group_any and kElideLanes
+
 constexpr int kBlock = 256;
-
-struct I64x2 { long long x, y; };
-struct I32x4 { int x, y, z, w; };
-
-template <int EB> __device__ __forceinline__ uint4 vmax(uint4 a, uint4 b);
-template <> __device__ __forceinline__ uint4 vmax<8>(uint4 a, uint4 b) {
-    I64x2 p = __builtin_bit_cast(I64x2, a), q = __builtin_bit_cast(I64x2, b);
-    I64x2 r{p.x > q.x ? p.x : q.x, p.y > q.y ? p.y : q.y};
-    return __builtin_bit_cast(uint4, r);
-}
-template <> __device__ __forceinline__ uint4 vmax<4>(uint4 a, uint4 b) {
-    I32x4 p = __builtin_bit_cast(I32x4, a), q = __builtin_bit_cast(I32x4, b);
-    I32x4 r{max(p.x, q.x), max(p.y, q.y), max(p.z, q.z), max(p.w, q.w)};
-    return __builtin_bit_cast(uint4, r);
-}
-
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 nt_load(const uint4* p) {
-    return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p)));
-}
-__device__ __forceinline__ void nt_store(uint4* p, uint4 v) {
-    __builtin_nontemporal_store(__builtin_bit_cast(v4u, v), reinterpret_cast<v4u*>(p));
-}
 
 template <int EB> struct Elem;
 template <> struct Elem<4> { using T = int; };
 template <> struct Elem<8> { using T = long long; };
-
-// True where the two vectors differ in any bit.
-__device__ __forceinline__ bool differs(uint4 a, uint4 b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0; }
-
-// Store elision (merge kernels): max is idempotent and most merges are no-ops for most cells (a replica advances
-// its own column only, every message is a full state, anti-entropy re-delivers merged states), so a vector of A
-// is stored only if its aligned group of kElideLanes lanes holds a lane whose maximum differs from what it loaded:
-// 8 lanes x 16 B = one 128-B line where the lanes' vectors are consecutive and the group's first is line-aligned
-// (k_merge_dense always; k_merge_grouped where the row is a multiple of 128 B), so a line is written whole or
-// not at all.  Granularity measured against per-lane (16 B) and per-wave (1 KB) elision over 0 - 100 % changed
-// cells (tools/tune_pnc.hip, profiles/r07/tune_pnc_elide.txt).  Correctness rests on neither grouping nor
-// alignment: a lane that stores writes the maximum, a lane that skips held an unchanged value.  `mask` is the
-// wave's ballot of changed lanes (inactive lanes read as unchanged).
-constexpr uint32_t kElideLanes = 8;
-__device__ __forceinline__ bool group_changed(unsigned long long mask, uint32_t lane) {
-    return ((mask >> (lane & (64 - kElideLanes))) & ((1u << kElideLanes) - 1)) != 0;
-}
-
-// Dense merge: nv 16-byte vectors per array plus `tail` trailing cells (< 16 B) done by block 0.  The grid is two
-// halves of `half` workgroups: the first merges P (A.P, B.P), the second N (A.N, B.N), so in dispatch order the chip
-// streams two arrays at a time, then the other two, instead of four at once.  A workgroup takes kDenseVecs vectors
-// per lane, kDenseBlock apart (a wave-instruction reads 1 KB contiguous, an aligned group of kElideLanes lanes is one
-// 128-B line), every load issued before the first use.  Measured on MI355X in the regime the kernel now mostly
-// runs in — four read streams, nothing stored — and behind batches that raise one column per key or every cell
-// (tools/tune_pnc.hip `steady`, profiles/r08/tune_pnc_steady*.txt), against the four-streams-per-workgroup shape it
-// had since round 1 and against 2 / 4 vectors per lane, workgroups of 512 / 1024, bounded grids (grid-stride and
-// block-chunk walks), P then N inside a workgroup, default-policy loads and LDS-DMA loads: see DESIGN.md §4 for
-// what each measured.  P and N are elided separately as before (each half writes only its own array); the bounds
-// test is a predicate, not a branch around the ballot, so every lane of a wave that loaded data votes (lanes past
-// nv vote unchanged).
-constexpr int kDenseVecs = 1;     // 16-B vectors of each array per lane
-constexpr int kDenseBlock = 256;  // lanes per workgroup: kDenseVecs x kDenseBlock vectors per workgroup
-
-// Vector i of the batch beside A's 16-B vector i.  BV = uint4: the batch's own cells (the wide form, and every int32
-// batch).  BV = uint2 (int64 stores only): two 4-byte codes of a narrow batch (jg_rows), widened in registers.
-__device__ __forceinline__ uint4 ld_batch_vec(const uint4* B, uint64_t i) { return nt_load(B + i); }
-__device__ __forceinline__ uint4 ld_batch_vec(const uint2* B, uint64_t i) {
-    const jg::filt::v2i c = __builtin_nontemporal_load(reinterpret_cast<const jg::filt::v2i*>(B) + i);
-    return __builtin_bit_cast(uint4, I64x2{jg::filt::widen(c.x), jg::filt::widen(c.y)});
-}
-template <class T> __device__ __forceinline__ T ld_batch_cell(const uint4* B, uint64_t nv, uint32_t k) { return reinterpret_cast<const T*>(B + nv)[k]; }
-template <class T> __device__ __forceinline__ T ld_batch_cell(const uint2* B, uint64_t nv, uint32_t k) {
-    return (T)jg::filt::widen(reinterpret_cast<const int*>(B + nv)[k]);
-}
-
-template <int EB, class BV>
-__device__ __forceinline__ void merge_dense_body(uint4* __restrict__ AP, uint4* __restrict__ AN, const BV* __restrict__ BP,
-                                                 const BV* __restrict__ BN, uint64_t nv, uint32_t tail, uint32_t half) {
-    using T = typename Elem<EB>::T;
-    static_assert(sizeof(BV) == 16 || EB == 8, "the narrow form is an int64 batch's");
-    const bool isN = blockIdx.x >= half;
-    uint4* const A = isN ? AN : AP;
-    const BV* const B = isN ? BN : BP;
-    const uint64_t base = (uint64_t)(blockIdx.x - (isN ? half : 0)) * (kDenseVecs * kDenseBlock) + threadIdx.x;
-    uint4 a[kDenseVecs], b[kDenseVecs];
-    bool in[kDenseVecs];
-#pragma unroll
-    for (int u = 0; u < kDenseVecs; ++u) {
-        const uint64_t i = base + u * kDenseBlock;
-        in[u] = i < nv;
-        a[u] = b[u] = uint4{};
-        if (in[u]) a[u] = nt_load(A + i), b[u] = ld_batch_vec(B, i);
-    }
-    const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-    for (int u = 0; u < kDenseVecs; ++u) {
-        const uint4 m = vmax<EB>(a[u], b[u]);
-        const unsigned long long c = __ballot(in[u] && differs(m, a[u]));
-        if (in[u] && group_changed(c, lane)) nt_store(A + base + u * kDenseBlock, m);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < tail) {
-        T* ap = reinterpret_cast<T*>(AP + nv) + threadIdx.x;
-        T* an = reinterpret_cast<T*>(AN + nv) + threadIdx.x;
-        const T bp = ld_batch_cell<T>(BP, nv, threadIdx.x);
-        const T bn = ld_batch_cell<T>(BN, nv, threadIdx.x);
-        if (bp > *ap) *ap = bp;
-        if (bn > *an) *an = bn;
-    }
-}
-
-template <int EB>
-__global__ __launch_bounds__(kDenseBlock) void k_merge_dense(uint4* __restrict__ AP, uint4* __restrict__ AN,
-                                                             const uint4* __restrict__ BP, const uint4* __restrict__ BN,
-                                                             uint64_t nv, uint32_t tail, uint32_t half) {
-    merge_dense_body<EB, uint4>(AP, AN, BP, BN, nv, tail, half);
-}
-
-// The same merge of an int64 store with a narrow batch: nv 16-B vectors of A beside nv 8-B vectors of codes.
-__global__ __launch_bounds__(kDenseBlock) void k_merge_dense_narrow(uint4* __restrict__ AP, uint4* __restrict__ AN,
-                                                                    const uint2* __restrict__ BP, const uint2* __restrict__ BN,
-                                                                    uint64_t nv, uint32_t tail, uint32_t half) {
-    merge_dense_body<8, uint2>(AP, AN, BP, BN, nv, tail, half);
-}
 
 // Scatter-max: cell (m, c) of the received rows into row keys[m].  ABSENT cells are skipped.
 template <int EB>
@@ -205,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void k_merge_indexed_rows(typename Elem<EB>
 // key's rows into a list: next[m] = the key's previous head, head[key] = gen << 32 | m (one atomicExch per
 // row).  Pass 2 (k_merge_grouped): the head row of every key loads its A row once, max-folds every B row of
 // the key in registers — each B row's load issued together with its next[] link, so a key held k times
-// costs k - 1 dependent hops — and stores the 128-B lines of A that the fold raised, once (store elision, above:
+// costs k - 1 dependent hops — and stores the 128-B lines of A that the fold raised, once (store elision, group_any:
 // a key whose rows are all at or below A writes nothing); the other rows of the key do nothing.  Heads carry the
 // batch's generation: a head left by an earlier batch reads as empty, so nothing resets them (the list
 // head's `head[key] = kNil` store was one more random write per distinct key: 0.578 -> 0.566 ms per 1M rows,
@@ -253,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_merge_grouped(typename Elem<EB>::T* 
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (lead[u]) {
-                    b[u] = nt_load(reinterpret_cast<const uint4*>(B + (m0 + u) * R) + w);
+                    b[u] = nt_ld(reinterpret_cast<const uint4*>(B + (m0 + u) * R) + w);
                     a0[u] = *(reinterpret_cast<const uint4*>(A + key[u] * R) + w);
                 }
             }
@@ -263,14 +132,14 @@ __global__ __launch_bounds__(kBlock) void k_merge_grouped(typename Elem<EB>::T* 
                 a[u] = vmax<EB>(a0[u], b[u]);
                 uint64_t hops = 0;  // a list holds at most n_rows - 1 more rows: a bound every walk reaches
                 for (uint32_t cur = next[m0 + u]; cur != kNil && ++hops < n_rows;) {  // the key's other rows
-                    const uint4 bb = nt_load(reinterpret_cast<const uint4*>(B + (uint64_t)cur * R) + w);
+                    const uint4 bb = nt_ld(reinterpret_cast<const uint4*>(B + (uint64_t)cur * R) + w);
                     const uint32_t nx = next[cur];
                     a[u] = vmax<EB>(a[u], bb);
                     cur = nx;
                 }
                 // lead[u] and the list walk are wave-uniform: the ballot is taken by the lanes of this trip of the
                 // v loop (the last trip's idle lanes vote unchanged)
-                if (group_changed(__ballot(differs(a[u], a0[u])), lane)) *(reinterpret_cast<uint4*>(A + key[u] * R) + w) = a[u];
+                if (group_any<kElideLanes>(__ballot(differs(a[u], a0[u])), lane)) *(reinterpret_cast<uint4*>(A + key[u] * R) + w) = a[u];
             }
         }
     }
@@ -389,10 +258,6 @@ __global__ __launch_bounds__(kBlock) void k_values(const typename Elem<EB>::T* _
 // (step_rows, step_cols: divided on the host) with a compare; a lane's own unit lies at most kBlock / dw + 1 rows
 // further, found by a float reciprocal with a +-1 fix-up (exact: the quotient is at most 257 and dw < 2^30) — no
 // 64-bit divide per unit.  Touched once: non-temporal both ways, no LDS.
-template <class T> __device__ __forceinline__ T nt_ld(const T* p) { return __builtin_nontemporal_load(p); }
-template <> __device__ __forceinline__ uint4 nt_ld<uint4>(const uint4* p) { return nt_load(p); }
-template <class T> __device__ __forceinline__ void nt_st(T* p, T v) { __builtin_nontemporal_store(v, p); }
-template <> __device__ __forceinline__ void nt_st<uint4>(uint4* p, uint4 v) { nt_store(p, v); }
 
 constexpr uint64_t kRestrideBlocks = 1u << 16;  // x kBlock = 16.8M units a pass (268 MB of vectors)
 
@@ -421,10 +286,6 @@ __global__ __launch_bounds__(kBlock) void k_restride(T* __restrict__ dst, const 
     }
 }
 
-void check_store(const jg_pnc* p, const char* fn) {
-    JG_REQUIRE(p, JG_EINVAL, "%s: store is NULL", fn);
-}
-
 void check_keys(const uint32_t* k, uint64_t n, uint64_t n_keys, const char* fn) {
     for (uint64_t i = 0; i < n; ++i)
         JG_REQUIRE(k[i] < n_keys, JG_EINVAL, "%s: key_idx[%llu] = %u out of range (n_keys %llu)", fn,
@@ -437,139 +298,6 @@ uint32_t* upload_keys(jg_ctx* ctx, const uint32_t* key_idx, uint64_t n, uint64_t
     auto* d = static_cast<uint32_t*>(jg::scratch(ctx, ctx->scratch, n * 4));
     JG_HIP(hipMemcpyAsync(d, key_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
     return d;
-}
-
-// narrow: B is an int64 batch's 4-byte codes (eb == 8 only).
-void launch_merge_dense(jg_ctx* ctx, uint32_t eb, void* AP, void* AN, const void* BP, const void* BN, uint64_t n_cells, bool narrow = false) {
-    const uint64_t bytes = n_cells * eb;
-    const uint64_t nv = bytes / 16;
-    const uint32_t tail = (uint32_t)((bytes - nv * 16) / eb);
-    constexpr uint64_t per = (uint64_t)kDenseVecs * kDenseBlock;
-    const uint64_t blocks = (nv + per - 1) / per;  // per array: the grid holds P's, then N's
-    JG_REQUIRE(2 * blocks < 0xFFFFFFFFull, JG_EINVAL, "merge: %llu cells exceed one launch", (unsigned long long)n_cells);
-    const unsigned half = blocks ? (unsigned)blocks : 1u;  // block 0 exists for the trailing cells
-    if (narrow) {
-        hipLaunchKernelGGL(k_merge_dense_narrow, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint2*)BP,
-                           (const uint2*)BN, nv, tail, half);
-    } else {
-        jg::dispatch_eb(eb, [&](auto EB) {
-            hipLaunchKernelGGL(k_merge_dense<EB()>, dim3(2 * half), dim3(kDenseBlock), 0, ctx->stream, (uint4*)AP, (uint4*)AN, (const uint4*)BP,
-                               (const uint4*)BN, nv, tail, half);
-        });
-    }
-    JG_HIP(hipGetLastError());
-}
-
-// ---- the dense merge by the 32-bit shadow (int64 stores; pnc_filter_kernels.hpp) -------------------
-// The filtered kernel's shape: kFiltCells cells per lane and unit (2: an 8-B shadow load beside one 16-B vector of B,
-// 8 lanes to a 128-B line of A; 4: a 16-B shadow load beside two vectors of B, 4 lanes to a line), kFiltVecs units per
-// lane, kFiltBlock lanes per workgroup.  Measured against the other shapes in tools/tune_pnc.hip `filter`
-// (profiles/r09/tune_pnc_filter.txt): every shape reads a merged batch in 2.23 - 2.28 ms against k_merge_dense's
-// 2.88 ms; the 4-cell shapes are the fastest there by 0.02 ms but 0.4 ms slower than k_merge_dense when every line
-// changes (4 lanes store a 128-B line of A in two instructions each); of the 2-cell shapes this one is at or ahead of
-// k_merge_dense on all three patterns and the fastest on the merged batch.
-constexpr int kFiltCells = 2;
-constexpr int kFiltVecs = 1;
-constexpr int kFiltBlock = 512;
-constexpr int kBuildBlock = 256;
-
-unsigned halves_for(uint64_t n_units, uint64_t per, uint64_t n_cells) {
-    const uint64_t blocks = (n_units + per - 1) / per;  // per array: the grid holds P's, then N's
-    JG_REQUIRE(2 * blocks < 0xFFFFFFFFull, JG_EINVAL, "merge: %llu cells exceed one launch", (unsigned long long)n_cells);
-    return blocks ? (unsigned)blocks : 1u;  // a half's first block exists for the trailing cells
-}
-
-template <int CELLS, int VECS, int BLOCK, class BT>
-void launch_merge_filtered_as(jg_pnc* p, const void* BP, const void* BN, uint64_t n_cells) {
-    const uint64_t n_units = n_cells / CELLS;
-    const uint32_t tail = (uint32_t)(n_cells - n_units * CELLS);
-    const unsigned half = halves_for(n_units, (uint64_t)VECS * BLOCK, n_cells);
-    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CELLS, VECS, BLOCK, BT>), dim3(2 * half), dim3(BLOCK), 0, p->ctx->stream,
-                       p->P_.as<long long>(), p->N_.as<long long>(), p->sP.as<int>(), p->sN.as<int>(), (const BT*)BP, (const BT*)BN, n_units,
-                       tail, half);
-    JG_HIP(hipGetLastError());
-}
-
-// The filtered kernel's shape for a narrow batch (4-byte codes of B beside the 4-byte shadow: two equal read streams),
-// chosen like the wide batch's in tools/tune_pnc.hip `narrow`.
-constexpr int kNarrowCells = 2;
-constexpr int kNarrowVecs = 2;
-constexpr int kNarrowBlock = 256;
-
-void launch_merge_filtered(jg_pnc* p, const void* BP, const void* BN, uint64_t n_cells, bool narrow) {
-    if (narrow) launch_merge_filtered_as<kNarrowCells, kNarrowVecs, kNarrowBlock, int>(p, BP, BN, n_cells);
-    else launch_merge_filtered_as<kFiltCells, kFiltVecs, kFiltBlock, long long>(p, BP, BN, n_cells);
-}
-
-template <class BT> void launch_build_as(jg_pnc* p, const void* BP, const void* BN, uint64_t n_units, uint32_t tail, unsigned half) {
-    hipLaunchKernelGGL((jg::filt::k_merge_build<kBuildBlock, BT>), dim3(2 * half), dim3(kBuildBlock), 0, p->ctx->stream, p->P_.as<long long>(),
-                       p->N_.as<long long>(), p->sP.as<int>(), p->sN.as<int>(), (const BT*)BP, (const BT*)BN, n_units, tail, half);
-}
-
-// The build launch over the batch's cells, then the clamp pass over the store's cells behind the batch.
-void launch_merge_build(jg_pnc* p, const void* BP, const void* BN, uint64_t n_cells, bool narrow) {
-    jg_ctx* ctx = p->ctx;
-    const uint64_t n_units = n_cells / 2;
-    const uint32_t tail = (uint32_t)(n_cells - n_units * 2);
-    const unsigned half = halves_for(n_units, kBuildBlock, n_cells);
-    if (narrow) launch_build_as<int>(p, BP, BN, n_units, tail, half);
-    else launch_build_as<long long>(p, BP, BN, n_units, tail, half);
-    const uint64_t all = p->n_keys * p->R;
-    if (n_cells < all) {
-        const unsigned g = jg::grid_for(ctx, all - n_cells, 256, 16);
-        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(g), dim3(256), 0, ctx->stream, p->P_.as<long long>(), p->sP.as<int>(), n_cells, all);
-        hipLaunchKernelGGL(jg::filt::k_shadow_clamp, dim3(g), dim3(256), 0, ctx->stream, p->N_.as<long long>(), p->sN.as<int>(), n_cells, all);
-    }
-    JG_HIP(hipGetLastError());
-}
-
-// The shadow's buffers for the store's shape (kept across cold spells).  false: no room on the device; remembered
-// until the shape changes (pnc_grow), so a store that does not fit does not ask the allocator on every merge.
-bool shadow_ready(jg_pnc* p) {
-    const size_t bytes = (size_t)p->n_keys * p->R * 4;
-    if (p->sP.p && p->sN.p && p->sP.bytes >= bytes && p->sN.bytes >= bytes) return true;
-    if (p->filt_nomem) return false;
-    try {
-        p->sP.alloc(bytes);
-        p->sN.alloc(bytes);
-    } catch (const jg::Error&) {
-        p->sP.release();
-        p->sN.release();
-        p->filt_nomem = true;
-        (void)hipGetLastError();  // the failed allocation's code must not surface at the next launch check
-        jg::clear_error();
-        return false;
-    }
-    return true;
-}
-
-void drop_shadow(jg_pnc* p) {
-    p->sP.release();
-    p->sN.release();
-    p->filt = jg_pnc::kFiltCold;
-    p->filt_nomem = false;
-}
-
-// A dense identity merge of n_rows rows into the store: the one writer that does not go through rw_P / rw_N.
-// int32 stores and stores with the filter off run k_merge_dense and stay cold.  An int64 store runs it while cold
-// (and becomes armed: nothing else has written since this merge), the build launch while armed (and becomes valid),
-// the filtered kernel while valid.  narrow: the batch's form (jg_rows; int64 stores only): every one of the three
-// kernels reads a narrow batch as 4-byte codes.
-void merge_dense_store(jg_pnc* p, const void* BP, const void* BN, uint64_t n_rows, bool narrow = false) {
-    jg_ctx* ctx = p->ctx;
-    const uint64_t n_cells = n_rows * p->R;
-    if (p->eb == 8 && p->filt_on) {
-        if (p->filt == jg_pnc::kFiltValid) return launch_merge_filtered(p, BP, BN, n_cells, narrow);
-        if (p->filt == jg_pnc::kFiltArmed && shadow_ready(p)) {
-            launch_merge_build(p, BP, BN, n_cells, narrow);
-            p->filt = jg_pnc::kFiltValid;
-            return;
-        }
-        launch_merge_dense(ctx, 8, p->P_.p, p->N_.p, BP, BN, n_cells, narrow);
-        p->filt = jg_pnc::kFiltArmed;
-        return;
-    }
-    launch_merge_dense(ctx, p->eb, p->rw_P(), p->rw_N(), BP, BN, n_cells, narrow);
 }
 
 // The store's per-key list heads (generation-tagged) and a next[] link per received row (grown to the
@@ -677,128 +405,7 @@ void swap_buf(jg::DevBuf& a, jg::DevBuf& b) {
     std::swap(a.own, b.own);
 }
 
-// ---- the narrow form of a received batch (jg_rows in jg_internal.hpp, pnc_filter.hpp) ---------------
-// An int64 identity batch whose every cell fits is held as 4-byte codes in the lower half of P_ / N_.  It is decided
-// where the batch is born: jg_rows_upload narrows each landed chunk under the next chunk's copy, jg_synth_pnc_rows
-// writes the codes directly.  rows_wide gives every reader but the dense merge the int64 arrays back.
-
-constexpr size_t kNarrowFlagAt = 128;  // the upload's "a cell does not fit" word in ctx->flags (zero between calls)
-// Cells per staged chunk of an upload: at most a quarter of an array (two chunks fit the free upper half), capped at
-// 128 MB: every chunk costs the link a launch's worth of host time, and only the last chunk's narrowing (about 50 us
-// at the cap) is not hidden under a copy.
-constexpr uint64_t kNarrowChunkCap = 16777216;
-
-// codes[i] = narrow(cells[i]) for n cells of a landed chunk; *flag raised if a cell does not fit (every writer
-// stores the same value).
-__global__ __launch_bounds__(kBlock) void k_rows_narrow(const long long* __restrict__ cells, int* __restrict__ codes, uint64_t n,
-                                                        unsigned* __restrict__ flag) {
-    bool bad = false;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const long long b = __builtin_nontemporal_load(cells + i);
-        bad |= !jg::filt::fits(b);
-        codes[i] = jg::filt::narrow(b);
-    }
-    if (bad) *flag = 1u;
-}
-
-// The same in place over the first n <= kBlock cells of `buf`, one workgroup: every cell is read before any code is
-// written (a batch too small to stage in its own upper half).
-__global__ __launch_bounds__(kBlock) void k_rows_narrow_small(void* buf, uint32_t n, unsigned* flag) {
-    const bool in = threadIdx.x < n;
-    const long long b = in ? static_cast<const long long*>(buf)[threadIdx.x] : 0;
-    __syncthreads();
-    if (in) {
-        if (!jg::filt::fits(b)) *flag = 1u;
-        static_cast<int*>(buf)[threadIdx.x] = jg::filt::narrow(b);
-    }
-}
-
-// cells[i] = widen(codes[i]) for i in [lo, hi), both views of one buffer.  The caller keeps 8 lo >= 4 hi: the bytes
-// written ([8 lo, 8 hi)) lie behind the bytes read ([4 lo, 4 hi)).
-__global__ __launch_bounds__(kBlock) void k_rows_widen(void* buf, uint64_t lo, uint64_t hi) {
-    const int* codes = static_cast<const int*>(buf);
-    long long* cells = static_cast<long long*>(buf);
-    for (uint64_t i = lo + (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < hi; i += (uint64_t)gridDim.x * kBlock)
-        cells[i] = jg::filt::widen(codes[i]);
-}
-
-// The first n <= kBlock cells, one workgroup: every code is read before any cell is written.
-__global__ __launch_bounds__(kBlock) void k_rows_widen_small(void* buf, uint32_t n) {
-    const bool in = threadIdx.x < n;
-    const int c = in ? static_cast<const int*>(buf)[threadIdx.x] : 0;
-    __syncthreads();
-    if (in) static_cast<long long*>(buf)[threadIdx.x] = jg::filt::widen(c);
-}
-
-// One array widened in place, back to front by halves: the pass over cells [ceil(hi / 2), hi) writes only bytes no
-// code of a later pass lies in; a batch of n cells takes log2(n / kBlock) launches (this path is correct, not fast).
-void widen_in_place(jg_ctx* ctx, void* buf, uint64_t n_cells) {
-    uint64_t hi = n_cells;
-    while (hi > (uint64_t)kBlock) {
-        const uint64_t lo = (hi + 1) / 2;
-        hipLaunchKernelGGL(k_rows_widen, dim3(jg::grid_for(ctx, hi - lo, kBlock, 16)), dim3(kBlock), 0, ctx->stream, buf, lo, hi);
-        hi = lo;
-    }
-    hipLaunchKernelGGL(k_rows_widen_small, dim3(1), dim3(kBlock), 0, ctx->stream, buf, (uint32_t)hi);
-    JG_HIP(hipGetLastError());
-}
-
-// One host array of n int64 cells into `buf` (8 n bytes) as codes.  Chunk k is copied into staging slot k & 1 of the
-// upper half and narrowed into the lower half on one and the same stream, and the chunks alternate between ctx->stream
-// and ctx->copy (`turn` runs on across P and N): a chunk's narrowing runs under the next chunk's copy, a slot's next
-// copy is ordered behind the kernel that reads it by its stream alone, and between two copies the host issues nothing
-// but one launch (a copy from pageable memory holds the host, so every call between two of them idles the link).
-void upload_narrow_array(jg_ctx* ctx, unsigned& turn, void* buf, const void* host, uint64_t n) {
-    auto* flag = reinterpret_cast<unsigned*>(ctx->flags.as<char>() + kNarrowFlagAt);
-    const uint64_t stage_at = jg::round_up(n * 4, 16);                      // behind the codes, vector-aligned
-    const uint64_t room = n * 8 > stage_at ? n * 8 - stage_at : 0;          // n = 1: the aligned end lies past the buffer
-    const uint64_t chunk = std::min<uint64_t>(room / 16, kNarrowChunkCap);  // two slots of `chunk` cells
-    if (chunk == 0) {  // n <= 3: no room to stage
-        JG_HIP(hipMemcpyAsync(buf, host, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_rows_narrow_small, dim3(1), dim3(kBlock), 0, ctx->stream, buf, (uint32_t)n, flag);
-        JG_HIP(hipGetLastError());
-        return;
-    }
-    char* const stage = static_cast<char*>(buf) + stage_at;
-    uint64_t k = 0;
-    for (uint64_t c0 = 0; c0 < n; c0 += chunk, ++k, ++turn) {
-        const uint64_t len = std::min(chunk, n - c0);
-        hipStream_t st = (turn & 1) ? ctx->copy : ctx->stream;
-        long long* const dst = reinterpret_cast<long long*>(stage + (k & 1) * chunk * 8);
-        JG_HIP(hipMemcpyAsync(dst, static_cast<const char*>(host) + c0 * 8, len * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_rows_narrow, dim3(jg::grid_for(ctx, len, kBlock, 8)), dim3(kBlock), 0, st, dst, static_cast<int*>(buf) + c0, len, flag);
-    }
-    JG_HIP(hipGetLastError());
-}
-
-// jg_rows_upload of an int64 identity batch with narrowing on.  true: every cell fitted and the batch holds its codes;
-// false: a cell did not fit (the buffers hold partial codes: the caller uploads wide).  Both streams have drained.
-bool upload_narrow(jg_rows* r, const void* P, const void* N) {
-    jg_ctx* ctx = r->ctx;
-    const uint64_t n = r->n_rows * r->R;
-    JG_HIP(hipStreamSynchronize(ctx->stream));  // an asynchronous merge may still read the buffers ctx->copy is about to write
-    unsigned turn = 0;
-    upload_narrow_array(ctx, turn, r->P_.p, P, n);
-    upload_narrow_array(ctx, turn, r->N_.p, N, n);
-    JG_HIP(hipStreamSynchronize(ctx->copy));
-    jg::pin_get(ctx, 0, ctx->flags.as<char>() + kNarrowFlagAt, sizeof(unsigned));
-    jg::pin_sync(ctx);
-    if (*static_cast<const unsigned*>(jg::pin_at(ctx, 0)) == 0) return true;
-    JG_HIP(hipMemsetAsync(ctx->flags.as<char>() + kNarrowFlagAt, 0, sizeof(unsigned), ctx->stream));
-    return false;
-}
-
 }  // namespace
-
-jg::WideRows jg::rows_wide(const jg_rows* r) {
-    if (r->narrow) {
-        const uint64_t n = r->n_rows * r->R;
-        widen_in_place(r->ctx, r->P_.p, n);
-        widen_in_place(r->ctx, r->N_.p, n);
-        r->narrow = false;
-    }
-    return WideRows{r->P_.p, r->N_.p};
-}
 
 void jg::pnc_merge_indexed(jg_pnc* p, const void* BP, const void* BN, const uint32_t* d_keys, uint64_t n_rows) {
     Groups g;
@@ -849,7 +456,7 @@ void jg::pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
     swap_buf(p->N_, nN);
     if (table) swap_buf(p->cols, nC), swap_buf(p->ncols, nNc);
     if (nk != ok) p->head.release();  // the grouped merge's heads follow n_keys: first use recreates them (groups_of)
-    drop_shadow(p);  // the dense merge's shadow follows the shape (both streams have drained: nothing reads it)
+    p->shadow.drop();  // the dense merge's shadow follows the shape (both streams have drained: nothing reads it)
     p->n_keys = nk;
     p->R = nr;
     if (trace) {
@@ -941,28 +548,6 @@ int jg_pnc_set_max_replicas(jg_pnc* p, uint32_t max_replicas) {
     });
 }
 
-int jg_pnc_set_dense_filter(jg_pnc* p, int on) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
-        check_store(p, "jg_pnc_set_dense_filter");
-        p->filt_on = on != 0;
-        if (!p->filt_on) {
-            jg::ensure_device(p->ctx);
-            JG_HIP(hipStreamSynchronize(p->ctx->stream));  // an asynchronous merge may still read the shadow
-            drop_shadow(p);
-        }
-    });
-}
-
-int jg_pnc_dense_filter_state(jg_pnc* p, int* state) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
-        check_store(p, "jg_pnc_dense_filter_state");
-        JG_REQUIRE(state, JG_EINVAL, "jg_pnc_dense_filter_state: NULL output");
-        *state = p->filt_on ? p->filt : 0;
-    });
-}
-
 int jg_pnc_write_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, const void* P, const void* N) {
     return jg::guard([&] {
         auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
@@ -1050,7 +635,7 @@ int jg_pnc_merge_rows(jg_pnc* p, const uint32_t* key_idx, uint64_t n_rows, const
         JG_HIP(hipMemcpyAsync((char*)st + bytes, N, bytes, hipMemcpyHostToDevice, ctx->stream));
         Groups g;
         if (dk) launch_merge_indexed(ctx, p->eb, p->rw_P(), p->rw_N(), st, (char*)st + bytes, dk, n_rows, p->R, groups_of(p, n_rows, g));
-        else merge_dense_store(p, st, (char*)st + bytes, n_rows);
+        else jg::pnc_merge_dense(p, st, (char*)st + bytes, n_rows, false);
         JG_HIP(hipStreamSynchronize(ctx->stream));
     });
 }
@@ -1106,113 +691,6 @@ int jg_pnc_values(jg_pnc* p, const uint32_t* key_idx, uint64_t n, int64_t* out, 
         JG_HIP(hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipMemcpyAsync(overflow, dovf, n, hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipStreamSynchronize(ctx->stream));
-    });
-}
-
-int jg_rows_create(jg_ctx* ctx, uint64_t n_rows, uint32_t n_replicas, uint32_t elem_bytes, jg_rows** out) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(ctx);  // calls on one context are serialised (shared scratch, stream)
-        JG_REQUIRE(ctx && out, JG_EINVAL, "jg_rows_create: NULL argument");
-        JG_REQUIRE(elem_bytes == 4 || elem_bytes == 8, JG_EINVAL, "jg_rows_create: elem_bytes must be 4 or 8");
-        JG_REQUIRE(n_rows > 0 && n_replicas > 0, JG_EINVAL, "jg_rows_create: empty shape");
-        jg::ensure_device(ctx);
-        auto* r = new jg_rows();
-        r->ctx = ctx; r->n_rows = n_rows; r->R = n_replicas; r->eb = elem_bytes;
-        try {
-            const size_t bytes = (size_t)n_rows * n_replicas * elem_bytes;
-            r->P_.alloc(bytes);
-            r->N_.alloc(bytes);
-        } catch (...) {
-            delete r;
-            throw;
-        }
-        *out = r;
-    });
-}
-
-int jg_rows_destroy(jg_rows* r) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(r);  // calls on one context are serialised (shared scratch, stream)
-        if (!r) return;
-        jg::ensure_device(r->ctx);
-        JG_HIP(hipStreamSynchronize(r->ctx->stream));
-        delete r;
-    });
-}
-
-int jg_rows_upload(jg_rows* r, const uint32_t* key_idx, const void* P, const void* N) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(r);  // calls on one context are serialised (shared scratch, stream)
-        JG_REQUIRE(r && P && N, JG_EINVAL, "jg_rows_upload: NULL argument");
-        jg_ctx* ctx = r->ctx;
-        jg::ensure_device(ctx);
-        const size_t bytes = (size_t)r->n_rows * r->R * r->eb;
-        r->narrow = false;
-        // an int64 identity batch is narrowed chunk by chunk as it lands; one that holds a cell that does not fit is
-        // copied again, wide (rare: correct, not fast), as every keyed and every int32 batch is in the first place
-        if (!key_idx && r->eb == 8 && r->narrow_on) r->narrow = upload_narrow(r, P, N);
-        if (!r->narrow) {
-            JG_HIP(hipMemcpyAsync(r->P_.p, P, bytes, hipMemcpyHostToDevice, ctx->stream));
-            JG_HIP(hipMemcpyAsync(r->N_.p, N, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (key_idx) {
-            uint32_t mx = 0;
-            for (uint64_t i = 0; i < r->n_rows; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
-            r->max_key = mx;
-            if (r->keys.bytes < r->n_rows * 4) r->keys.alloc(r->n_rows * 4);
-            JG_HIP(hipMemcpyAsync(r->keys.p, key_idx, r->n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-            r->has_keys = true;
-        } else {
-            r->has_keys = false;
-        }
-        JG_HIP(hipStreamSynchronize(ctx->stream));
-    });
-}
-
-int jg_pnc_merge_batch(jg_pnc* p, const jg_rows* r, int async) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
-        jg::require_writable(p, "jg_pnc_merge_batch");
-        check_store(p, "jg_pnc_merge_batch");
-        JG_REQUIRE(r, JG_EINVAL, "jg_pnc_merge_batch: rows is NULL");
-        JG_REQUIRE(r->ctx == p->ctx, JG_EINVAL, "jg_pnc_merge_batch: rows and store belong to different contexts");
-        JG_REQUIRE(r->R == p->R && r->eb == p->eb, JG_ETYPE, "jg_pnc_merge_batch: row shape (%u x %uB) != store (%u x %uB)", r->R, r->eb,
-                   p->R, p->eb);
-        jg_ctx* ctx = p->ctx;
-        jg::ensure_device(ctx);
-        if (r->has_keys) {
-            JG_REQUIRE(r->max_key < p->n_keys, JG_EINVAL, "jg_pnc_merge_batch: batch addresses key %u >= n_keys %llu", r->max_key,
-                       (unsigned long long)p->n_keys);
-            Groups g;
-            const jg::WideRows w = jg::rows_wide(r);  // a keyed batch is wide already
-            launch_merge_indexed(ctx, p->eb, p->rw_P(), p->rw_N(), w.P, w.N, r->keys.as<uint32_t>(), r->n_rows, p->R, groups_of(p, r->n_rows, g));
-        } else {
-            JG_REQUIRE(r->n_rows <= p->n_keys, JG_EINVAL, "jg_pnc_merge_batch: identity batch of %llu rows > n_keys",
-                       (unsigned long long)r->n_rows);
-            merge_dense_store(p, r->P_.p, r->N_.p, r->n_rows, r->narrow);  // the one reader of either form in place
-        }
-        if (!async) JG_HIP(hipStreamSynchronize(ctx->stream));
-    });
-}
-
-int jg_rows_set_narrow(jg_rows* r, int on) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(r);  // calls on one context are serialised (shared scratch, stream)
-        JG_REQUIRE(r, JG_EINVAL, "jg_rows_set_narrow: rows is NULL");
-        r->narrow_on = on != 0;
-        if (!r->narrow_on && r->narrow) {
-            jg::ensure_device(r->ctx);
-            jg::rows_wide(r);
-            JG_HIP(hipStreamSynchronize(r->ctx->stream));
-        }
-    });
-}
-
-int jg_rows_form(jg_rows* r, int* form) {
-    return jg::guard([&] {
-        auto lk_ = jg::lock(r);  // calls on one context are serialised (shared scratch, stream)
-        JG_REQUIRE(r && form, JG_EINVAL, "jg_rows_form: NULL argument");
-        *form = r->narrow ? 1 : 0;
     });
 }
 

@@ -1,6 +1,6 @@
 // pnc_filter.hpp — the per-cell arithmetic of the dense PN-Counter merge's 32-bit shadow (HIP-free: the filtered
-// kernel and the build launch in pnc_filter_kernels.hpp and host/test_pnc_filter.cpp share this one definition), and
-// of the narrow form of a received cell (fits / narrow / widen: pnc.hip's batch kernels, host/test_pnc_narrow.cpp).
+// kernel and the build launch in pnc_dense_kernels.hpp and host/test_pnc_filter.cpp share this one definition), and
+// of the narrow form of a received cell (fits / narrow / widen: pnc_dense_kernels.hpp's batch kernels, host/test_pnc_narrow.cpp).
 //
 // The shadow of an int64 cell a is s = clamp32(a).  Strictly inside the int32 range the shadow IS the cell
 // (a == (int64)s), so a merge needs no read of a; at the two clamp values ("escapes") it only bounds it:

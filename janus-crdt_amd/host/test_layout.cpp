@@ -1,6 +1,7 @@
-// test_layout.cpp — csrc/layout.hpp on the CPU (no device code): the layout builder, pow2_at_least and the checked
-// narrowings blocks_for / cub_count; and csrc/orset_layouts.hpp, the OR-Set wave path's carved blocks.  Prints one
-// "ok <check>" line per check and "PASS" at the end; exits 1 at the first failure.  tests/test_layout.py runs it.
+// test_layout.cpp — csrc/layout.hpp on the CPU (no device code): the layout builder, pow2_at_least, the checked
+// narrowings blocks_for / cub_count and the dense merges' two-halves grid (halves_of); and csrc/orset_layouts.hpp,
+// the OR-Set wave path's carved blocks.  Prints one "ok <check>" line per check and "PASS" at the end; exits 1 at the
+// first failure.  tests/test_layout.py runs it.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -151,6 +152,46 @@ void test_cub_count() {
     std::printf("ok cub_count\n");
 }
 
+// halves_of for the (cells per unit, units per workgroup) pairs the dense merge launches (csrc/pnc_dense.hip), held
+// to the arithmetic written out: whole units, the cells past them, workgroups per half (at least one: a half's first
+// workgroup owns the trailing cells), and whether both halves fit one launch.
+void test_halves_of() {
+    struct Shape { const char* name; uint32_t cells; uint64_t units; };
+    const Shape shapes[] = {
+        {"k_merge_dense<4>", 4, 256},             // a 16-B vector of int32 cells
+        {"k_merge_dense<8>", 2, 256},             // of int64 cells
+        {"k_merge_filtered, wide", 2, 512},       // kFiltCells, kFiltVecs x kFiltBlock
+        {"k_merge_filtered, narrow", 2, 2 * 256},  // kNarrowCells, kNarrowVecs x kNarrowBlock
+        {"k_merge_build", 2, 256},                // 2, kBuildBlock
+    };
+    for (const Shape& sh : shapes) {
+        const uint64_t c = sh.cells, u = sh.units, group = c * u;  // one workgroup's cells
+        const uint64_t most = 0x7FFFFFFFull * group + (c - 1);     // 2^31 - 1 workgroups per half and a full tail
+        const uint64_t counts[] = {0, 1, c - 1, c, group - 1, group, group + 1, 3 * group + c + (c - 1), most, most + 1};
+        for (uint64_t n : counts) {
+            const jg::Halves h = jg::halves_of(n, sh.cells, sh.units);
+            CHECK(h.n_units == n / c && h.tail == n % c && h.n_units * c + h.tail == n);
+            const uint64_t covering = (n / c + u - 1) / u;
+            CHECK(h.blocks == (covering ? covering : 1));
+            CHECK(h.blocks * u >= h.n_units && (h.blocks - 1) * u <= h.n_units);
+            CHECK(h.fits() == (n <= most));
+        }
+        CHECK(jg::halves_of(0, sh.cells, sh.units).blocks == 1 && jg::halves_of(c - 1, sh.cells, sh.units).tail == c - 1);
+        CHECK(jg::halves_of(group, sh.cells, sh.units).blocks == 1 && jg::halves_of(group + 1, sh.cells, sh.units).blocks == 1);
+        CHECK(jg::halves_of(group + c, sh.cells, sh.units).blocks == 2);
+        CHECK(jg::halves_of(3 * group + c + (c - 1), sh.cells, sh.units).tail == c - 1 && c - 1 != 0);
+        CHECK(jg::halves_of(most, sh.cells, sh.units).blocks == 0x7FFFFFFFull && jg::halves_of(most + 1, sh.cells, sh.units).blocks == 0x80000000ull);
+    }
+    // k_merge_dense's unit is a 16-B vector of eb-byte cells: the byte arithmetic its launch used before halves_of
+    for (uint64_t eb : {4ull, 8ull})
+        for (uint64_t n : {0ull, 1ull, 3ull, 4ull, 5ull, 15ull, 1023ull, 1024ull, 1025ull, 640000000ull, (1ull << 40) + 3}) {
+            const jg::Halves h = jg::halves_of(n, (uint32_t)(16 / eb), 256);
+            const uint64_t bytes = n * eb, nv = bytes / 16;
+            CHECK(h.n_units == nv && h.tail == (bytes - nv * 16) / eb);
+        }
+    std::printf("ok halves_of\n");
+}
+
 // csrc/orset_layouts.hpp: the three carved blocks of the OR-Set wave path, held to their formulas written out
 uint64_t al(uint64_t b) { return (b + 255) & ~255ull; }
 
@@ -241,6 +282,7 @@ int main() {
     test_round_pow2();
     test_blocks_for();
     test_cub_count();
+    test_halves_of();
     test_orset_layouts();
     std::printf("PASS %d checks\n", g_checks);
     return 0;

@@ -2,7 +2,7 @@
 // C2 shape (10M keys x 64 replicas, int64), one process, hipEvents per launch, median of rounds.
 // `tune_pnc <rounds> elide`: the store-elision sweep instead (granularity x share of cells changed per launch).
 // `tune_pnc <rounds> steady`: the read-only steady state bench.py times (data x cadence, then the read-side shapes).
-// `tune_pnc <rounds> filter`: the merge by the 32-bit shadow (csrc/pnc_filter_kernels.hpp, the library's own kernels
+// `tune_pnc <rounds> filter`: the merge by the 32-bit shadow (csrc/pnc_dense_kernels.hpp, the library's own kernels
 // in several shapes) and its build launch beside the parent's kernel.
 // `tune_pnc <rounds> narrow`: the same merge of a batch held as 4-byte codes (the narrow form) in 2- and 4-cell shapes
 // beside the wide batch's kernel.
@@ -16,7 +16,10 @@
 #include <string>
 #include <vector>
 
-#include "pnc_filter_kernels.hpp"
+#include "layout.hpp"
+#include "pnc_dense_kernels.hpp"
+
+using namespace jg::filt;  // the library's kernels, their shape constants and group_any
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { std::printf("%s: %s\n", #x, hipGetErrorString(e)); std::exit(1); } } while (0)
 
@@ -112,11 +115,6 @@ __global__ __launch_bounds__(B) void k_flat(v2* AP, v2* AN, const v2* BP, const 
     }
 }
 
-template <int G> __device__ __forceinline__ bool group_changed(unsigned long long mask, unsigned lane) {
-    if constexpr (G == 64) return mask != 0;
-    else return ((mask >> (lane & (64 - G))) & ((1ull << G) - 1)) != 0;
-}
-
 template <int G, int B>
 __global__ __launch_bounds__(B) void k_elide(v2* AP, v2* AN, const v2* BP, const v2* BN, unsigned long long nv) {
     const unsigned long long i = (unsigned long long)blockIdx.x * B + threadIdx.x;
@@ -128,8 +126,8 @@ __global__ __launch_bounds__(B) void k_elide(v2* AP, v2* AN, const v2* BP, const
     const unsigned lane = threadIdx.x & 63;
     bool sp = dp, sn = dn;
     if constexpr (G > 1) {
-        sp = in && group_changed<G>(__ballot(dp), lane);
-        sn = in && group_changed<G>(__ballot(dn), lane);
+        sp = in && group_any<G>(__ballot(dp), lane);
+        sn = in && group_any<G>(__ballot(dn), lane);
     }
     if (sp) st<true>(AP + i, mp);
     if (sn) st<true>(AN + i, mn);
@@ -312,8 +310,8 @@ __device__ __forceinline__ void trip_pn(v2* AP, v2* AN, const v2* BP, const v2* 
         const unsigned long long i = base + u * B + threadIdx.x;
         const v2 mp = vmax(ap[u], bp[u]), mn = vmax(an[u], bn[u]);
         const unsigned long long cp = __ballot(in[u] && vdiff(mp, ap[u])), cn = __ballot(in[u] && vdiff(mn, an[u]));
-        if (in[u] && group_changed<8>(cp, lane)) st<true>(AP + i, mp);
-        if (in[u] && group_changed<8>(cn, lane)) st<true>(AN + i, mn);
+        if (in[u] && group_any<8>(cp, lane)) st<true>(AP + i, mp);
+        if (in[u] && group_any<8>(cn, lane)) st<true>(AN + i, mn);
     }
 }
 
@@ -335,7 +333,7 @@ __device__ __forceinline__ void trip_one(v2* A, const v2* Bv, unsigned long long
         const unsigned long long i = base + u * B + threadIdx.x;
         const v2 m = vmax(a[u], b[u]);
         const unsigned long long c = __ballot(in[u] && vdiff(m, a[u]));
-        if (in[u] && group_changed<8>(c, lane)) st<true>(A + i, m);
+        if (in[u] && group_any<8>(c, lane)) st<true>(A + i, m);
     }
 }
 
@@ -398,38 +396,16 @@ __global__ __launch_bounds__(B) void k_rlds(v2* AP, v2* AN, const v2* BP, const 
     if (in) ap = img[0][threadIdx.x], bp = img[1][threadIdx.x], an = img[2][threadIdx.x], bn = img[3][threadIdx.x];
     const v2 mp = vmax(ap, bp), mn = vmax(an, bn);
     const unsigned long long cp = __ballot(in && vdiff(mp, ap)), cn = __ballot(in && vdiff(mn, an));
-    if (in && group_changed<8>(cp, lane)) st<true>(AP + i, mp);
-    if (in && group_changed<8>(cn, lane)) st<true>(AN + i, mn);
+    if (in && group_any<8>(cp, lane)) st<true>(AP + i, mp);
+    if (in && group_any<8>(cn, lane)) st<true>(AN + i, mn);
 }
 
-// csrc/pnc.hip's k_merge_dense<8> as it stands (uint4 vectors, __restrict__, the tail cells' branch; tail = 0
-// here): the library's own instructions beside k_elide<8,256>, which the sweeps take for them
-__global__ __launch_bounds__(256) void k_lib(uint4* __restrict__ AP, uint4* __restrict__ AN, const uint4* __restrict__ BP,
-                                             const uint4* __restrict__ BN, unsigned long long nv, unsigned tail) {
-    const auto ldv = [](const uint4* p) { return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v2*>(p))); };
-    const auto stv = [](uint4* p, uint4 v) { __builtin_nontemporal_store(__builtin_bit_cast(v2, v), reinterpret_cast<v2*>(p)); };
-    const auto mx = [](uint4 a, uint4 b) { return __builtin_bit_cast(uint4, vmax(__builtin_bit_cast(v2, a), __builtin_bit_cast(v2, b))); };
-    const auto differs = [](uint4 a, uint4 b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0; };
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    const bool in = i < nv;
-    uint4 ap{}, bp{}, an{}, bn{};
-    if (in) ap = ldv(AP + i), bp = ldv(BP + i), an = ldv(AN + i), bn = ldv(BN + i);
-    const uint4 mp = mx(ap, bp), mn = mx(an, bn);
-    const unsigned long long cp = __ballot(in && differs(mp, ap)), cn = __ballot(in && differs(mn, an));
-    const unsigned lane = threadIdx.x & 63;
-    if (in && group_changed<8>(cp, lane)) stv(AP + i, mp);
-    if (in && group_changed<8>(cn, lane)) stv(AN + i, mn);
-    if (blockIdx.x == 0 && threadIdx.x < tail) {
-        long long* a = reinterpret_cast<long long*>(AP + nv) + threadIdx.x;
-        long long* b = reinterpret_cast<long long*>(AN + nv) + threadIdx.x;
-        const long long p = reinterpret_cast<const long long*>(BP + nv)[threadIdx.x];
-        const long long n = reinterpret_cast<const long long*>(BN + nv)[threadIdx.x];
-        if (p > *a) *a = p;
-        if (n > *b) *b = n;
-    }
-}
+// The library's own k_merge_dense<8> (csrc/pnc_dense_kernels.hpp) on the library's grid (halves_of).  Until round 12 this
+// row timed a hand copy of the kernel's round-7 body, four streams per workgroup: profiles/r08's figures are that shape's.
 void L_lib(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
-    hipLaunchKernelGGL(k_lib, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, (uint4*)a, (uint4*)b, (const uint4*)c, (const uint4*)d, nv, 0u);
+    const jg::Halves h = jg::halves_of(nv * 2, 2, (uint64_t)kDenseVecs * kDenseBlock);
+    hipLaunchKernelGGL(k_merge_dense<8>, dim3(2 * (unsigned)h.blocks), dim3(kDenseBlock), 0, s, (uint4*)a, (uint4*)b, (const uint4*)c,
+                       (const uint4*)d, h.n_units, h.tail, (unsigned)h.blocks);
 }
 
 unsigned blocks_of(unsigned long long nv, unsigned long long per) { return (unsigned)((nv + per - 1) / per); }
@@ -450,7 +426,7 @@ void L_rchunk(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hip
 }
 template <int U, int B>
 void L_rhalves(v2* a, v2* b, const v2* c, const v2* d, unsigned long long nv, hipStream_t s, int) {
-    const unsigned half = blocks_of(nv, B * U);
+    const unsigned half = (unsigned)jg::halves_of(nv, 1, B * U).blocks;
     hipLaunchKernelGGL((k_rhalves<U, B>), dim3(2 * half), dim3(B), 0, s, a, b, c, d, nv, half);
 }
 template <int U, int B>
@@ -532,7 +508,7 @@ int steady_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int roun
 
     const std::vector<Variant> vs = {
         parent,
-        {"csrc/pnc.hip's own body", L_lib},
+        {"csrc/pnc.hip's own body", L_lib},  // the label of the earlier tables, kept: now pnc_dense_kernels.hpp's k_merge_dense<8>
         {"flat U2 B256",L_rflat<2, 256, true, true>},
         {"flat U4 B256", L_rflat<4, 256, true, true>},
         {"flat U1 B512", L_rflat<1, 512, true, true>},
@@ -637,16 +613,14 @@ void LF_parent(v2* ap, v2* an, int*, int*, const v2* bp, const v2* bn, unsigned 
 }
 template <int CPL, int VECS, int BLOCK>
 void LF(v2* ap, v2* an, int* sp, int* sn, const v2* bp, const v2* bn, unsigned long long n_cells, hipStream_t s) {
-    const unsigned long long nu = n_cells / CPL;
-    const unsigned half = blocks_of(nu, (unsigned long long)VECS * BLOCK);
-    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CPL, VECS, BLOCK>), dim3(2 * half), dim3(BLOCK), 0, s, (long long*)ap, (long long*)an, sp, sn,
-                       (const long long*)bp, (const long long*)bn, nu, (unsigned)(n_cells - nu * CPL), half);
+    const jg::Halves h = jg::halves_of(n_cells, CPL, (uint64_t)VECS * BLOCK);
+    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CPL, VECS, BLOCK>), dim3(2 * (unsigned)h.blocks), dim3(BLOCK), 0, s, (long long*)ap,
+                       (long long*)an, sp, sn, (const long long*)bp, (const long long*)bn, h.n_units, h.tail, (unsigned)h.blocks);
 }
 void LF_build(v2* ap, v2* an, int* sp, int* sn, const v2* bp, const v2* bn, unsigned long long n_cells, hipStream_t s) {
-    const unsigned long long nu = n_cells / 2;
-    const unsigned half = blocks_of(nu, 256);
-    hipLaunchKernelGGL(jg::filt::k_merge_build<256>, dim3(2 * half), dim3(256), 0, s, (long long*)ap, (long long*)an, sp, sn, (const long long*)bp,
-                       (const long long*)bn, nu, (unsigned)(n_cells - nu * 2), half);
+    const jg::Halves h = jg::halves_of(n_cells, 2, kBuildBlock);
+    hipLaunchKernelGGL(jg::filt::k_merge_build<kBuildBlock>, dim3(2 * (unsigned)h.blocks), dim3(kBuildBlock), 0, s, (long long*)ap, (long long*)an,
+                       sp, sn, (const long long*)bp, (const long long*)bn, h.n_units, h.tail, (unsigned)h.blocks);
 }
 
 int filter_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int rounds) {
@@ -667,11 +641,11 @@ int filter_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int roun
         {"filtered 2 cells U1 B256", true, LF<2, 1, 256>},
         {"filtered 2 cells U2 B256", true, LF<2, 2, 256>},
         {"filtered 2 cells U4 B256", true, LF<2, 4, 256>},
-        {"filtered 2 cells U1 B512", true, LF<2, 1, 512>},
+        {"filtered 2 cells U1 B512", true, LF<kFiltCells, kFiltVecs, kFiltBlock>},  // the library's shape
         {"filtered 4 cells U1 B256", true, LF<4, 1, 256>},
         {"filtered 4 cells U2 B256", true, LF<4, 2, 256>},
         {"filtered 4 cells U1 B512", true, LF<4, 1, 512>},
-        {"build launch (2 cells B256)", true, LF_build},
+        {"build launch (2 cells B256)", true, LF_build},  // the library's (kBuildBlock)
         {"parent (again)", false, LF_parent},
     };
     const size_t nvar = vs.size();
@@ -756,14 +730,13 @@ struct NVariant {
     void (*launch)(v2*, v2*, int*, int*, const v2*, const v2*, const int*, const int*, unsigned long long, hipStream_t);
 };
 void LN_parent(v2* ap, v2* an, int* sp, int* sn, const v2* bp, const v2* bn, const int*, const int*, unsigned long long n_cells, hipStream_t s) {
-    LF<2, 1, 512>(ap, an, sp, sn, bp, bn, n_cells, s);
+    LF<kFiltCells, kFiltVecs, kFiltBlock>(ap, an, sp, sn, bp, bn, n_cells, s);
 }
 template <int CPL, int VECS, int BLOCK>
 void LN(v2* ap, v2* an, int* sp, int* sn, const v2*, const v2*, const int* cp, const int* cn, unsigned long long n_cells, hipStream_t s) {
-    const unsigned long long nu = n_cells / CPL;
-    const unsigned half = blocks_of(nu, (unsigned long long)VECS * BLOCK);
-    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CPL, VECS, BLOCK, int>), dim3(2 * half), dim3(BLOCK), 0, s, (long long*)ap, (long long*)an, sp, sn,
-                       cp, cn, nu, (unsigned)(n_cells - nu * CPL), half);
+    const jg::Halves h = jg::halves_of(n_cells, CPL, (uint64_t)VECS * BLOCK);
+    hipLaunchKernelGGL((jg::filt::k_merge_filtered<CPL, VECS, BLOCK, int>), dim3(2 * (unsigned)h.blocks), dim3(BLOCK), 0, s, (long long*)ap,
+                       (long long*)an, sp, sn, cp, cn, h.n_units, h.tail, (unsigned)h.blocks);
 }
 
 int narrow_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int rounds) {
@@ -783,7 +756,7 @@ int narrow_sweep(v2* AP, v2* AN, v2* BP, v2* BN, unsigned long long nv, int roun
         {"parent (wide B, 2 cells B512)", LN_parent},
         {"narrow 2 cells U1 B256", LN<2, 1, 256>},
         {"narrow 2 cells U1 B512", LN<2, 1, 512>},
-        {"narrow 2 cells U2 B256", LN<2, 2, 256>},
+        {"narrow 2 cells U2 B256", LN<kNarrowCells, kNarrowVecs, kNarrowBlock>},  // the library's shape
         {"narrow 2 cells U4 B256", LN<2, 4, 256>},
         {"narrow 2 cells U2 B512", LN<2, 2, 512>},
         {"narrow 4 cells U1 B256", LN<4, 1, 256>},
@@ -901,7 +874,6 @@ int main(int argc, char** argv) {
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             t[k].push_back(ms);
         }
-    // copy reference: 3 x (read 16B write 16B) ~ same 48 B/cell? no: report copy GB/s separately
     std::vector<float> tc;
     for (int r = 0; r < rounds; ++r) {
         CK(hipEventRecord(e0, s));

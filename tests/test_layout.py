@@ -6,7 +6,7 @@ process."""
 import subprocess
 from pathlib import Path
 
-CHECKS = ("layout", "pow2_at_least", "blocks_for", "cub_count", "orset_layouts")
+CHECKS = ("layout", "pow2_at_least", "blocks_for", "cub_count", "halves_of", "orset_layouts")
 
 
 def _run(name):
@@ -25,7 +25,10 @@ def test_layout_helpers_on_cpu():
     """The layout builder over counts 0, 1 and 2^31 + 5 at alignments 8, 16 and 256 (aligned offsets, no overlap, a
     total that covers the last array, zero-count arrays that take only padding and bind to a usable pointer);
     pow2_at_least at its floor, at a power of two and one past it; blocks_for at 0, 1, block, block + 1 and failing
-    (not wrapping) past 2^31 - 1 workgroups; cub_count at INT_MAX and INT_MAX + 1.  The OR-Set wave path's blocks:
+    (not wrapping) past 2^31 - 1 workgroups; cub_count at INT_MAX and INT_MAX + 1; halves_of (the dense PN-Counter merges'
+    two-halves grid) for each (cells per unit, units per workgroup) pair the library launches at 0 cells, 1, a unit less
+    one, one unit, a workgroup's cells - 1 / exactly / + 1, a count with trailing cells and the largest count that fits
+    one launch (and one past it), and k_merge_dense's units against its byte arithmetic.  The OR-Set wave path's blocks:
     the claims' counts at caps 0, 1, 62, 63, 1023, 1024, 2^20 and 0x7FFFFFF0 - 1, the bucket commit's seven arrays at
     table sizes {4096, 2^20, 2^30}^2, the names staging at n in {0, 1, 3, 4, 5} x nb in {0, 1, 17} and its copy-out."""
     _run("test_layout")

@@ -1,4 +1,4 @@
-"""The dense PN-Counter merge by its 32-bit shadow (csrc/pnc.hip merge_dense_store, csrc/pnc_filter_kernels.hpp): an
+"""The dense PN-Counter merge by its 32-bit shadow (csrc/pnc_dense.hip pnc_merge_dense, csrc/pnc_dense_kernels.hpp): an
 int64 store whose last writes were dense identity merges builds sP / sN = clamp32(P / N) at the second such merge
 and reads them instead of P / N from the third on.  Every expected result is numpy.maximum on the host (or the
 lowering the test applied), compared bit for bit through read_rows; the path a call took is observed through
@@ -23,7 +23,7 @@ G = FILT_CELLS * FILT_VECS * FILT_BLOCK
 LINE = 16
 WAVE = 64 * FILT_CELLS
 
-PNC_HIP = Path(__file__).resolve().parent.parent / "janus-crdt_amd" / "csrc" / "pnc.hip"
+KERNELS_HPP = Path(__file__).resolve().parent.parent / "janus-crdt_amd" / "csrc" / "pnc_dense_kernels.hpp"
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -31,11 +31,11 @@ EDGES = [I64_MIN, I32_MIN - 1, I32_MIN, I32_MIN + 1, -1, 0, 1, I32_MAX - 1, I32_
 
 
 def test_constants_match_the_kernel():
-    src = PNC_HIP.read_text()
+    src = KERNELS_HPP.read_text()
     got = {}
     for name in ("kFiltCells", "kFiltVecs", "kFiltBlock"):
         m = re.findall(r"^constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, src, re.M)
-        assert len(m) == 1, f"{name}: expected one `constexpr <type> {name} = <literal>;` line in csrc/pnc.hip"
+        assert len(m) == 1, f"{name}: expected one `constexpr <type> {name} = <literal>;` line in csrc/pnc_dense_kernels.hpp"
         got[name] = int(m[0])
     assert got == {"kFiltCells": FILT_CELLS, "kFiltVecs": FILT_VECS, "kFiltBlock": FILT_BLOCK}
 
@@ -127,6 +127,77 @@ def test_states_cold_armed_valid(ctx):
             assert s.dense_filter_state() == 0
         P, N = s.read_rows()
         assert np.array_equal(P, A4 + 2) and np.array_equal(N, A4 + 2)
+    finally:
+        s.close()
+
+
+# ---- the store's file and the dense merge's file meet -----------------------------------------------------------------
+
+def _tiny_valid(ctx, rng):
+    """An int64 store of 3 keys x 5 replicas (15 cells: a trailing cell, less than one workgroup) made valid by three
+    jg_pnc_merge_batch calls; returns the store and the host's [P, N]."""
+    n_keys, R = 3, 5
+    cur = [_cells(rng, n_keys, R), _cells(rng, n_keys, R)]
+    s = jg.PNCStore(ctx, n_keys, R, 8)
+    b = jg.Rows(ctx, n_keys, R, 8)
+    try:
+        s.write_rows(cur[0], cur[1])
+        for want in (1, 2, 2):
+            BP, BN = _cells(rng, n_keys, R), _cells(rng, n_keys, R)
+            b.upload(BP, BN)
+            s.merge_batch(b)
+            cur = [np.maximum(cur[0], BP), np.maximum(cur[1], BN)]
+            assert s.dense_filter_state() == want
+        _same(s, cur[0], cur[1], "tiny, valid")
+    except BaseException:
+        s.close()
+        raise
+    finally:
+        b.close()
+    return s, cur
+
+
+@pytest.mark.gpu
+def test_reserve_between_batch_merges(ctx):
+    """jg_pnc_reserve (the store's file) drops a shadow that jg_pnc_merge_batch (the dense merge's file) built: the
+    state reads cold at 4 x 6, and the next batch merges by the cells, not by a shadow of the old shape."""
+    rng = np.random.default_rng(31)
+    s, cur = _tiny_valid(ctx, rng)
+    b = jg.Rows(ctx, 4, 6, 8)
+    try:
+        s.reserve(4, 6)
+        assert s.dense_filter_state() == 0
+        grown = []
+        for c in cur:
+            g = np.zeros((4, 6), np.int64)
+            g[:3, :5] = c
+            grown.append(g)
+        BP, BN = _cells(rng, 4, 6), _cells(rng, 4, 6)
+        b.upload(BP, BN)
+        s.merge_batch(b)
+        eP, eN = np.maximum(grown[0], BP), np.maximum(grown[1], BN)
+        assert s.dense_filter_state() == 1
+        _same(s, eP, eN, "after reserve")
+        v, o = s.values()
+        assert np.array_equal(v, eP.sum(1) - eN.sum(1)) and not o.any()
+    finally:
+        b.close()
+        s.close()
+
+
+@pytest.mark.gpu
+def test_merge_rows_into_a_valid_store(ctx):
+    """jg_pnc_merge_rows without key indices (the store's file, staged through scratch) reaches the filtered kernel
+    through jg::pnc_merge_dense: one cell at INT32_MAX + 1 and one at INT32_MIN, and the state stays valid."""
+    rng = np.random.default_rng(32)
+    s, cur = _tiny_valid(ctx, rng)
+    try:
+        BP, BN = cur[0] - 1, cur[1] - 1
+        BP[1, 2] = I32_MAX + 1
+        BN[2, 4] = I32_MIN  # the trailing cell
+        _merge(s, cur, BP, BN, "escape values")
+        assert cur[0][1, 2] == I32_MAX + 1
+        _merge(s, cur, BP, BN, "again")
     finally:
         s.close()
 

@@ -1,4 +1,4 @@
-"""The edges of k_merge_dense's shape (csrc/pnc.hip): kDenseVecs 16-B vectors of each array per lane, kDenseBlock
+"""The edges of k_merge_dense's shape (csrc/pnc_dense_kernels.hpp): kDenseVecs 16-B vectors of each array per lane, kDenseBlock
 lanes per workgroup, so a workgroup takes W = kDenseVecs x kDenseBlock vectors per trip, a wave-instruction reads
 64 consecutive vectors, a lane's vectors lie kDenseBlock apart, an aligned group of 8 lanes is one 128-B line (written
 whole or not at all), and the cells behind the last whole vector are block 0's.  P and N are merged by different
@@ -26,15 +26,15 @@ DENSE_VECS = 1     # kDenseVecs
 DENSE_BLOCK = 256  # kDenseBlock
 W = DENSE_VECS * DENSE_BLOCK
 
-PNC_HIP = Path(__file__).resolve().parent.parent / "janus-crdt_amd" / "csrc" / "pnc.hip"
+KERNELS_HPP = Path(__file__).resolve().parent.parent / "janus-crdt_amd" / "csrc" / "pnc_dense_kernels.hpp"
 
 
 def test_constants_match_the_kernel():
-    src = PNC_HIP.read_text()
+    src = KERNELS_HPP.read_text()
     got = {}
     for name in ("kDenseVecs", "kDenseBlock"):
         m = re.findall(r"^constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, src, re.M)
-        assert len(m) == 1, f"{name}: expected one `constexpr <type> {name} = <literal>;` line in csrc/pnc.hip"
+        assert len(m) == 1, f"{name}: expected one `constexpr <type> {name} = <literal>;` line in csrc/pnc_dense_kernels.hpp"
         got[name] = int(m[0])
     assert got == {"kDenseVecs": DENSE_VECS, "kDenseBlock": DENSE_BLOCK}
     assert W == got["kDenseVecs"] * got["kDenseBlock"]

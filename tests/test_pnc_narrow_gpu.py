@@ -1,4 +1,4 @@
-"""The narrow form of a received PN-Counter batch (csrc/pnc.hip, jg_rows): an int64 batch without key indices whose
+"""The narrow form of a received PN-Counter batch (csrc/pnc_dense.hip, jg_rows): an int64 batch without key indices whose
 every cell is ABSENT or in (INT32_MIN, INT32_MAX] is held as 4-byte codes, decided at jg_rows_upload (chunk by chunk) or
 jg_synth_pnc_rows, and the dense merge reads it in that form.  The form a batch took is observed through jg_rows_form
 (0 wide, 1 narrow) and switched with jg_rows_set_narrow; every merged result is numpy.maximum on the host, compared bit
@@ -6,7 +6,8 @@ for bit through read_rows.
 
 G = the cells one workgroup of the filtered kernel takes of a narrow batch (kNarrowCells x kNarrowVecs x
 kNarrowBlock), mirrored here as literals with the upload's chunk rule; test_constants_match_the_source (no GPU) reads
-the constexpr lines.  A 128-B line of A is 16 cells."""
+the constexpr lines: the shape's in csrc/pnc_dense_kernels.hpp, kNarrowChunkCap's beside the upload in
+csrc/pnc_dense.hip.  A 128-B line of A is 16 cells."""
 import re
 from pathlib import Path
 
@@ -23,7 +24,9 @@ G = NARROW_CELLS * NARROW_VECS * NARROW_BLOCK
 LINE = 16
 WAVE = 64 * NARROW_CELLS
 
-PNC_HIP = Path(__file__).resolve().parent.parent / "janus-crdt_amd" / "csrc" / "pnc.hip"
+CSRC = Path(__file__).resolve().parent.parent / "janus-crdt_amd" / "csrc"
+HOMES = {"kNarrowCells": "pnc_dense_kernels.hpp", "kNarrowVecs": "pnc_dense_kernels.hpp", "kNarrowBlock": "pnc_dense_kernels.hpp",
+         "kNarrowChunkCap": "pnc_dense.hip"}
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -41,11 +44,11 @@ def chunk_cells(n):
 
 
 def test_constants_match_the_source():
-    src = PNC_HIP.read_text()
     got = {}
     for name in ("kNarrowCells", "kNarrowVecs", "kNarrowBlock", "kNarrowChunkCap"):
+        src = (CSRC / HOMES[name]).read_text()
         m = re.findall(r"^constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, src, re.M)
-        assert len(m) == 1, f"{name}: expected one `constexpr <type> {name} = <literal>;` line in csrc/pnc.hip"
+        assert len(m) == 1, f"{name}: expected one `constexpr <type> {name} = <literal>;` line in csrc/{HOMES[name]}"
         got[name] = int(m[0])
     assert got == {"kNarrowCells": NARROW_CELLS, "kNarrowVecs": NARROW_VECS, "kNarrowBlock": NARROW_BLOCK, "kNarrowChunkCap": CHUNK_CAP}
 
