@@ -182,4 +182,21 @@ int jg_stream(jg_ctx* ctx, void** s) {
     });
 }
 
+int jg_host_alloc(jg_ctx* ctx, uint64_t bytes, void** out) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(ctx);  // calls on one context are serialised (shared scratch, stream)
+        JG_REQUIRE(ctx && out, JG_EINVAL, "jg_host_alloc: NULL argument");
+        jg::ensure_device(ctx);
+        *out = nullptr;
+        if (bytes == 0) return;
+        JG_HIP(hipHostMalloc(out, bytes, hipHostMallocDefault));
+    });
+}
+
+int jg_host_free(void* p) {
+    return jg::guard([&] {
+        if (p) JG_HIP(hipHostFree(p));
+    });
+}
+
 }  // extern "C"

@@ -18,7 +18,7 @@ namespace jg {
 // Row / set id of a message of another kind in a node wave (csrc/node.hip): the PN-Counter and OR-Set
 // passes run over the same uploaded wave and skip each other's messages.
 constexpr uint32_t kSkipIdx = 0xFFFFFFFFu;
-// Replicas per key the replica table holds (json.hip: per-vector duplicate masks are 4 x 64 bits).
+// Replicas per key the replica table holds (pnc_wire.hpp: per-vector duplicate masks are 4 x 64 bits).
 constexpr uint32_t kMaxTableReplicas = 256;
 
 // ---- the one owner rule of a sharded node -------------------
@@ -126,6 +126,20 @@ private:
     friend void pnc_merge_dense(jg_pnc*, const void*, const void*, uint64_t, bool);
     State state_ = kCold;
 };
+
+// The wave of PNCounterMsg payloads a store is decoding and merging (json.hip): host state under the context lock.
+// json.hip is its only writer; other files may only ask is_open().
+struct PncWave {
+    DevBuf bytes, off, rows;  // an open streamed wave (jg_pnc_wave_*): payload, offsets, rows
+    DevBuf stat;              // status words, pass A's deferred marks, pass C's roll-back slots (pnc_wave_layout.hpp)
+    DevBuf emit, guid, slow;  // pass A's record per message, the deferred records' Guids, the messages pass B parses again
+    uint64_t n = 0, nb = 0;   // messages and bytes appended to the streamed wave; n alone: a node wave's capacity
+    uint64_t scan_hi = 0;     // messages pass A scanned since the wave began (its fused applies are undone below this)
+    bool open = false;        // between jg_pnc_wave_begin and _commit / _abort
+    bool fuse = true;         // the wave's pass A applies what it proves (JANUS_JSON_FUSE, latched when the wave begins)
+    bool status_clean = false;  // the status words hold their initial values (the last wave ended clean): no reset
+    bool is_open() const { return open; }
+};
 }  // namespace jg
 
 // ---- handle types (opaque at the ABI) ------------------------------------------------------------
@@ -172,20 +186,13 @@ struct jg_pnc {
     void* rw_P() { shadow.invalidate(); return P_.p; }
     void* rw_N() { shadow.invalidate(); return N_.p; }
     jg::DenseShadow shadow;  // eb == 8 only
-    // replica table (json.hip): [n_keys x R] 16-byte Guids + [n_keys] column counts, first use only
+    // replica table (pnc_table.hpp): [n_keys x R] 16-byte Guids + [n_keys] column counts, first use only
     jg::DevBuf cols, ncols;
     // grouped indexed merge (k_group_*): per-key list head of the batch being merged (gen << 32 | row,
     // generation-tagged: no reset between calls) and a next[] link per received row; first use
     jg::DevBuf head, next;
     unsigned long long head_gen = 0;  // generation of the last grouped batch (heads hold gen << 32 | row)
-    // open streamed wave (jg_pnc_wave_*): payload, offsets, rows, status + deferred list; pass A's
-    // resolved entries per message and its list of messages pass B must parse again (json.hip)
-    jg::DevBuf wbytes, woff, wrows, wstat, wemit, wguid, wslow;
-    uint64_t wn = 0, wnb = 0;
-    uint64_t scan_hi = 0;  // messages pass A scanned since the wave began (its fused applies are undone below this)
-    bool wopen = false;
-    bool fuse = true;       // the wave's pass A applies what it proves (JANUS_JSON_FUSE, latched when the wave begins)
-    bool status_clean = false;  // the wave status words hold their initial values (the last wave ended clean): no reset
+    jg::PncWave wave;        // the wave of state messages in flight (json.hip)
     bool node_open = false;  // a node wave (node.hip) holds the store: see jg::require_writable
 };
 

@@ -27,6 +27,17 @@
 // of what the serial parser accepts, with identical entries, and never rejects.
 #pragma once
 
+#include <cstdlib>
+
+#include "layout.hpp"
+#include "pnc_wire.hpp"
+
+namespace {
+
+// SWAR / LDS helpers shared with orset_wire.hip
+using jgw::wave_sync, jgw::zero_bytes, jgw::ge_bytes, jgw::le_bytes, jgw::digit_bytes, jgw::bits4, jgw::hex4, jgw::hex_pairs, jgw::hex_be16,
+    jgw::hex_le16, jgw::lds_words, jgw::lds_words_b64;
+
 constexpr uint32_t kGroupBytes = 512;              // LDS bytes per message: payload + its 16-B alignment offset
 constexpr uint32_t kGroupTok = 16;                 // token slots (an entry spans >= 41 bytes, a name 11)
 constexpr uint32_t kCompactMin = 27;               // {"pVector":{},"nVector":{}}
@@ -86,8 +97,6 @@ __device__ __forceinline__ uint32_t group_last(uint32_t x) {
     else return __shfl(x, G - 1, G);
 }
 
-__device__ __forceinline__ bool same(const Guid16& a, const Guid16& b) { return a.lo == b.lo && a.hi == b.hi; }
-
 // Lanes with `want` get consecutive slots of *counter, one returning atomic per wave (rare paths only:
 // a counter every wave waits on serialises the grid).  Every lane of the wave calls it.
 __device__ __forceinline__ unsigned long long wave_slot(bool want, unsigned long long* counter) {
@@ -100,7 +109,6 @@ __device__ __forceinline__ unsigned long long wave_slot(bool want, unsigned long
     base = __shfl(base, leader);
     return base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
 }
-
 
 // `<36-char Guid>":<int>` at LDS byte q (the byte after the opening quote), read_guid's and read_int's
 // grammar without whitespace; *tend = offset from q of the byte after the number.
@@ -217,13 +225,13 @@ template <int G>
 __device__ __forceinline__ uint32_t cached_col(const Guid16* cache, const Guid16* __restrict__ gcols, uint32_t nc, const Guid16& x,
                                                uint32_t hint) {
     const uint32_t ncache = nc < (uint32_t)G ? nc : (uint32_t)G;
-    if (hint < ncache && same(cache[hint], x)) return hint;
+    if (hint < ncache && same_guid(cache[hint], x)) return hint;
     for (uint32_t j = 0; j < ncache; ++j)
-        if (same(cache[j], x)) return j;
+        if (same_guid(cache[j], x)) return j;
     for (uint32_t j = ncache; j < nc; ++j) {
         const Guid16 h = gcols[j];
         if ((h.lo | h.hi) == 0) break;
-        if (same(h, x)) return j;
+        if (same_guid(h, x)) return j;
     }
     return UINT32_MAX;
 }
@@ -632,9 +640,9 @@ __global__ __launch_bounds__(kBlock) void k_resolve_rows(const unsigned long lon
             uint32_t col = UINT32_MAX;
 #pragma unroll
             for (uint32_t c = 0; c < kRC; ++c)
-                if (c < nc && same(rcol[c], x)) col = c;
+                if (c < nc && same_guid(rcol[c], x)) col = c;
             for (uint32_t c = kRC; col == UINT32_MAX && c < nc; ++c)
-                if (same(gcols[c], x)) col = c;
+                if (same_guid(gcols[c], x)) col = c;
             if (col == UINT32_MAX) {
                 if (nc >= t.R) { err = kErrFull; break; }
                 col = nc++;
@@ -732,3 +740,4 @@ void launch_scan_g(int G, hipStream_t st, const uint8_t* bytes, const uint64_t* 
 #undef JG_SCAN
 }
 
+}  // namespace

@@ -535,7 +535,7 @@ int jg_pnc_reserve(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas) {
         auto lk_ = jg::lock(p);  // calls on one context are serialised (shared scratch, stream)
         jg::require_writable(p, "jg_pnc_reserve");
         check_store(p, "jg_pnc_reserve");
-        JG_REQUIRE(!p->wopen, JG_EINVAL, "jg_pnc_reserve: a wave (jg_pnc_wave_begin) is open on this store");
+        JG_REQUIRE(!p->wave.is_open(), JG_EINVAL, "jg_pnc_reserve: a wave (jg_pnc_wave_begin) is open on this store");
         jg::pnc_grow(p, n_keys, n_replicas);
     });
 }

@@ -848,7 +848,7 @@ __global__ void k_enc_len(Store S, uint64_t n_add, uint64_t n_rem, uint32_t* __r
     len[e] = l;
 }
 
-// The write pass, staged as json.hip's: a block's 256 pieces are contiguous on the wire, so its lanes write their
+// The write pass, staged as pnc_encode.hip's: a block's 256 pieces are contiguous on the wire, so its lanes write their
 // bytes into an LDS window of kStage bytes (aligned to 16 in output coordinates) and the block then stores the window
 // as whole 16-byte chunks, bytes only at the two ragged ends it shares with its neighbours.  A block whose pieces
 // run past one window (a long string, or just 256 long entries) takes window after window: a lane keeps its place

@@ -1,7 +1,7 @@
 // test_layout.cpp — csrc/layout.hpp on the CPU (no device code): the layout builder, pow2_at_least, the checked
 // narrowings blocks_for / cub_count and the dense merges' two-halves grid (halves_of); and csrc/orset_layouts.hpp,
-// the OR-Set wave path's carved blocks.  Prints one "ok <check>" line per check and "PASS" at the end; exits 1 at the
-// first failure.  tests/test_layout.py runs it.
+// the OR-Set wave path's carved blocks; and csrc/pnc_wave_layout.hpp, the PN-Counter wave's status block.  Prints one
+// "ok <check>" line per check and "PASS" at the end; exits 1 at the first failure.  tests/test_layout.py runs it.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +11,7 @@
 
 #include "layout.hpp"
 #include "orset_layouts.hpp"
+#include "pnc_wave_layout.hpp"
 
 namespace jg {
 struct Error {
@@ -275,6 +276,65 @@ void test_orset_layouts() {
     std::printf("ok orset_layouts\n");
 }
 
+// csrc/pnc_wave_layout.hpp: the PN-Counter wave's status block — 64 bytes of status words, an 8-byte deferred mark
+// per message from byte 64, a 4-byte roll-back slot per message from the next multiple of 16 past the marks of the
+// capacity the block has — for blocks of exactly the bytes asked and of the bytes a growth allocates (half as much
+// again: launch.hpp grow_keep)
+struct WaveStatus {
+    unsigned long long *status = nullptr, *deferred = nullptr;
+    uint32_t* saved = nullptr;
+};
+
+void test_pnc_wave_layout() {
+    void* const far = reinterpret_cast<void*>(uintptr_t(1) << 40);
+    const uint64_t ns[] = {0, 1, 2, 3, 7, 8, 1000, 131072};
+    const size_t kN = sizeof ns / sizeof ns[0];
+    for (size_t k = 0; k < kN; ++k) {
+        const uint64_t n = ns[k];
+        const size_t need = 64 + n * 8 + n * 4 + 256;
+        CHECK(jg::wave_status_bytes(n) == need);
+        for (size_t bytes : {need, need + need / 2}) {
+            const uint64_t cap = (bytes - 64 - 256) / 12;
+            CHECK(jg::wave_status_capacity(bytes) == cap && cap >= n);  // the capacity read back covers what was asked
+            WaveStatus w;
+            const size_t end = jg::carve_wave_status(cap, far, w);
+            CHECK(off_of(w.status, far) == 0 && off_of(w.deferred, far) == 64);
+            CHECK(off_of(w.saved, far) == 64 + ((cap * 8 + 15) & ~15ull));
+            CHECK(off_of(w.saved, far) >= 64 + cap * 8);                     // the slots start past the last mark
+            CHECK(end == off_of(w.saved, far) + cap * 4 && end <= bytes);  // and end inside the block
+        }
+        // grown to hold the next size while `keep` messages' marks are live: what is carried over is the status words
+        // and those marks, they lie inside the old block's list, and the new block's list starts where the old one did
+        if (k + 1 < kN) {
+            const size_t old_bytes = need + need / 2, grown = jg::wave_status_bytes(ns[k + 1]) + jg::wave_status_bytes(ns[k + 1]) / 2;
+            const uint64_t old_cap = jg::wave_status_capacity(old_bytes);
+            WaveStatus a, b;
+            jg::carve_wave_status(old_cap, far, a);
+            jg::carve_wave_status(jg::wave_status_capacity(grown), far, b);
+            CHECK(off_of(b.deferred, far) == off_of(a.deferred, far) && off_of(b.status, far) == off_of(a.status, far));
+            for (uint64_t keep : {(uint64_t)0, n}) {
+                CHECK(jg::wave_status_keep(keep) == 64 + keep * 8);
+                CHECK(jg::wave_status_keep(keep) <= off_of(a.deferred, far) + old_cap * 8);
+                CHECK(jg::wave_status_keep(keep) <= off_of(b.saved, far));  // nothing carried over lands in the new slots
+            }
+        }
+    }
+    CHECK(jg::wave_status_capacity(0) == 0 && jg::wave_status_capacity(319) == 0 && jg::wave_status_capacity(320 + 11) == 0);
+    {  // bound to a real block of the bytes a growth allocates: the last mark and the last slot lie inside it
+        const size_t bytes = jg::wave_status_bytes(7) + jg::wave_status_bytes(7) / 2;
+        const uint64_t cap = jg::wave_status_capacity(bytes);
+        std::vector<unsigned char> block(bytes);
+        WaveStatus w;
+        jg::carve_wave_status(cap, block.data(), w);
+        CHECK((void*)w.status == block.data());
+        w.status[4] = ~0ull, w.deferred[cap - 1] = ~0ull, w.saved[cap - 1] = ~0u;
+        CHECK(block[39] == 0xFF && block[64 + cap * 8 - 1] == 0xFF && block[off_of(w.saved, block.data()) + cap * 4 - 1] == 0xFF);
+        WaveStatus u;
+        CHECK(jg::carve_wave_status(cap, nullptr, u) <= bytes && u.status == nullptr && u.saved == nullptr);  // size only
+    }
+    std::printf("ok pnc_wave_layout\n");
+}
+
 }  // namespace
 
 int main() {
@@ -284,6 +344,7 @@ int main() {
     test_cub_count();
     test_halves_of();
     test_orset_layouts();
+    test_pnc_wave_layout();
     std::printf("PASS %d checks\n", g_checks);
     return 0;
 }

@@ -736,6 +736,80 @@ def test_apply_ops_encode_edges(ctx, eb):
 
 
 @pytest.mark.parametrize("eb", [4, 8])
+def test_encode_write_pass_staged_and_direct(ctx, eb):
+    """Both branches of the encoder's write pass in one call, through every entry point that runs it.  The write pass
+    takes 64 rows per workgroup and stages them in LDS when their states fit 32,768 bytes, else writes them directly.
+    130 rows in query order at R = 64: rows 0-63 hold 2 replicas each (~64 x 150 B: staged), rows 64-127 hold 40
+    replicas each with values at the type's extremes (~64 x 4 KB: direct), rows 128-129 are a partial last workgroup.
+    jg_pnc_encode_json, jg_pnc_encode_json_before (non-zero dp / dn, hashes on) and jg_pnc_apply_ops_encode over the
+    same rows each equal the oracle's encoder byte for byte, and the hashes equal hashlib's SHA-256."""
+    rng = np.random.default_rng(130 + eb)
+    n_keys, R = 130, 64
+    lim = 2**31 if eb == 4 else 2**63
+    bits = 32 if eb == 4 else 64
+    stable = random_guids(rng, n_keys)
+    pr = Pair(ctx, n_keys, R, eb, stable)
+    keys = np.arange(n_keys, dtype=np.uint32)
+    msgs = []
+    for k in range(n_keys):
+        wide = 64 <= k < 128
+        gs = [stable[k]] + random_guids(rng, 39 if wide else 1)
+        if wide:  # the longest numbers the type prints (negative ones arrive with the rewinds and the ops below)
+            pv, nv = [lim - 1] * len(gs), [lim - 1 if j % 2 else 0 for j in range(len(gs))]
+        else:
+            pv, nv = [int(v) for v in rng.integers(0, 1000, len(gs))], [int(v) for v in rng.integers(0, 1000, len(gs))]
+        msgs.append(encode_pnc(gs, pv, nv))
+    pr.oracle(keys, msgs)
+    pr.s.merge_json(keys, msgs)
+    pr.check()
+    assert (pr.ncols[:64] == 2).all() and (pr.ncols[64:128] == 40).all() and (pr.ncols[128:] == 2).all()
+
+    def wrap(x):
+        x = int(x) % (1 << bits)
+        return x - (1 << bits) if x >= 1 << (bits - 1) else x
+
+    def expect(k, p0, n0):  # row k with column 0 at p0 / n0
+        c = int(pr.ncols[k])
+        P, N = pr.P[k, :c].astype(object).copy(), pr.N[k, :c].astype(object).copy()
+        P[0], N[0] = p0, n0
+        return orc.json_encode_pnc(pr.cols[k, :c]["lo"], pr.cols[k, :c]["hi"], np.array(P, dtype=pr.P.dtype), np.array(N, dtype=pr.N.dtype), eb)
+
+    def check_plain():
+        got = pr.s.encode_json(keys)
+        sizes = [len(b) for b in got]
+        assert sum(sizes[:64]) < 32768 < sum(sizes[64:128]) and sum(sizes[128:]) < 32768  # staged, direct, staged
+        for k in range(n_keys):
+            assert got[k] == expect(k, pr.P[k, 0], pr.N[k, 0]), f"key {k}"
+
+    check_plain()
+    # the rows before dp / dn of own-column amounts: -1 takes lim - 1 to the type's most negative value
+    dp = rng.integers(1, 2**20, n_keys).astype(np.int64)
+    dn = rng.integers(-2**20, 2**20, n_keys).astype(np.int64)
+    dp[64:128:2], dn[dn == 0] = -1, 7
+    got, h = pr.s.encode_json_before(keys, dp, dn, sha=True)
+    for k in range(n_keys):
+        assert got[k] == expect(k, wrap(int(pr.P[k, 0]) - int(dp[k])), wrap(int(pr.N[k, 0]) - int(dn[k]))), f"key {k}"
+        assert h[k].tobytes() == hashlib.sha256(got[k]).digest()
+    # one op per row, snapshots and hashes in the same call: +1 wraps lim - 1 to the most negative value
+    delta = rng.integers(1, 1000, n_keys).astype(np.int64)
+    delta[64:128:2] = 1
+    is_n = (rng.random(n_keys) < 0.3).astype(np.uint8)
+    is_n[64:128:2] = 0
+    got, h = pr.s.apply_ops_encode(keys, delta, is_n)
+    P, N = pr.P.astype(object), pr.N.astype(object)
+    for k in range(n_keys):
+        M = N if is_n[k] else P
+        M[k, 0] = wrap(M[k, 0] + int(delta[k]))
+        assert got[k] == expect(k, P[k, 0], N[k, 0]), f"op {k}"
+        assert h[k].tobytes() == hashlib.sha256(got[k]).digest()
+    pr.P, pr.N = np.array(P, dtype=pr.P.dtype), np.array(N, dtype=pr.N.dtype)
+    assert (pr.P[64:128:2, 0] == -lim).all()
+    pr.check()
+    check_plain()  # and the rows as they stand now, the negative extremes in the store
+    pr.close()
+
+
+@pytest.mark.parametrize("eb", [4, 8])
 @pytest.mark.parametrize("n_keys,n_ops", [(40, 3000), (200000, 100000), (3, 1)])
 def test_apply_ops_rewind_matches_walk(ctx, eb, n_keys, n_ops):
     """jg_pnc_apply_ops_rewind (round 6): a batch of own-column Increment / Decrement ops (PNCounters.cs:96-112)

@@ -6,7 +6,7 @@ process."""
 import subprocess
 from pathlib import Path
 
-CHECKS = ("layout", "pow2_at_least", "blocks_for", "cub_count", "halves_of", "orset_layouts")
+CHECKS = ("layout", "pow2_at_least", "blocks_for", "cub_count", "halves_of", "orset_layouts", "pnc_wave_layout")
 
 
 def _run(name):
@@ -30,7 +30,10 @@ def test_layout_helpers_on_cpu():
     one, one unit, a workgroup's cells - 1 / exactly / + 1, a count with trailing cells and the largest count that fits
     one launch (and one past it), and k_merge_dense's units against its byte arithmetic.  The OR-Set wave path's blocks:
     the claims' counts at caps 0, 1, 62, 63, 1023, 1024, 2^20 and 0x7FFFFFF0 - 1, the bucket commit's seven arrays at
-    table sizes {4096, 2^20, 2^30}^2, the names staging at n in {0, 1, 3, 4, 5} x nb in {0, 1, 17} and its copy-out."""
+    table sizes {4096, 2^20, 2^30}^2, the names staging at n in {0, 1, 3, 4, 5} x nb in {0, 1, 17} and its copy-out.
+    The PN-Counter wave's status block (csrc/pnc_wave_layout.hpp) at n in {0, 1, 2, 3, 7, 8, 1000, 131072} and grown
+    from each to the next: offsets and sizes, the roll-back slots inside the block, the capacity read back >= n, a
+    grown block's deferred list where the old one was."""
     _run("test_layout")
 
 
