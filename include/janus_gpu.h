@@ -784,6 +784,61 @@ int jg_node_query_keys(jg_node* node, jg_keyspace* ks, uint64_t n,
                        int64_t* value, uint8_t* status, uint8_t* kind, jg_guid* guid);
 
 /* ---------------------------------------------------------------------------------------------
+ * Client writes by key name (csrc/update.hip) — additive to ABI v10.
+ * PNCounterCommand "i" / "d" and ORSetCommand "a" / "r" / "c" for a batch (CRDTCommands/PNCounterCommand.cs:42-53,
+ * ORSetCommand.cs:43-61): KeySpaceManager.GetKVPair -> SafeCRDT.Update(operationID, args) (SafeCRDT.cs:39-47) ->
+ * prospectiveState.Update(operationID, args) in PNCounterWrapper (PNCounterWrapper.cs:33-48) or ORSetWrapper
+ * (ORSetWrapper.cs:30-47).  One call resolves every key on the device through the key space's dictionary and the node's
+ * uid table (as jg_node_query_keys; pending jg_node_register entries are uploaded first) and applies what resolved.
+ *
+ * Command i names key key_bytes[key_off[i], key_off[i+1]) (off[0] = 0 as elsewhere) on `node`, usually the prospective
+ * copy's node (either copy is accepted).  op[i] is SafeCRDT.Update's operationID; arg_flag[i]: 0 = no argument, 1 = the
+ * string elem_bytes[elem_off[i], elem_off[i+1]), 2 = the C# null, 3 = the integer amount[i].  tag_lo / tag_hi [i] is the
+ * Guid.NewGuid() of an ORSet.Add (read for OR-Set commands only); col is the copy's own replica column
+ * (PNCounters.cs:73-81).  Commands take effect in batch order.
+ *   Type.      The key's CRDT decides what runs, not the command, as for reads.
+ *   PN-Counter key.  PNCounterWrapper.Update evaluates (int)args[0] before its switch: an arg_flag other than 3 is
+ *              JG_U_BAD_ARG (flag 0 or 2: NullReferenceException, flag 1: InvalidCastException).  With an integer, op 1
+ *              is Increment(amount): the row's P cell at column col += amount; op 2 is Decrement(amount), the same on
+ *              the N cell; both wrap at the store's width as jg_pnc_apply_ops does.  Any other op with an integer is
+ *              JG_U_BAD_OP.  result[i] = 1 for an applied command.
+ *   OR-Set key.  ORSetWrapper.Update switches first: an op outside 1..3 is JG_U_BAD_OP whatever the argument; op 3 is
+ *              Clear and ignores the argument; op 1 is Add, op 2 Remove, both of the string (flag 1) or the null element
+ *              (flag 2); flag 0 or 3 is JG_U_BAD_ARG.  Effects, result, elem, add_lim and rem_lim are exactly
+ *              jg_orset_apply_ops_names' for the applied OR-Set commands, in batch order: its id rule, its Clear epochs,
+ *              its ord limits.
+ *   JG_U_NO_KEY / JG_U_NO_CRDT: as JG_Q_NO_KEY / JG_Q_NO_CRDT (a key of a kind whose store the node lacks is NO_CRDT).
+ *   A failed command applies nothing and disturbs no other command (the reference catches per command): result 0,
+ *              idx 0xFFFFFFFF, elem JG_NULL_ELEM - 1; kind is 0, 1 or 255 as for jg_node_query_keys.
+ * Outputs: status[i], result[i]; optional: kind[i], idx[i] (the row or set the command touched: what a producer needs
+ * to encode the snapshot SafeCRDT.Update ships next), elem[i] (the id an OR-Set command addressed, JG_NULL_ELEM - 1 for
+ * every other command), guid[i] (keySpaces[key]), add_lim / rem_lim (both or neither; 0 for a command that is not an
+ * applied OR-Set command).
+ * DEPARTURE: keys are resolved by Guid, not by key string: the departure stated at jg_node_query_keys.
+ * JG_EINVAL, decided from the arguments before anything is copied or written, every output and both stores untouched:
+ * NULL node, ks, op, arg_flag, status or result with n > 0; offsets that decrease (or off[0] != 0); an arg_flag above 3;
+ * an arg_flag 3 with amount NULL; an arg_flag 1 with elem_off or elem_bytes NULL; an arg_flag 1 or 2 with tag_lo or
+ * tag_hi NULL (a PN-Counter-only batch may leave tags and elements NULL); col not below the PN-Counter store's replica
+ * count (when the node has one); only one of add_lim / rem_lim; a key space and a node of different contexts; n >=
+ * 2^31 - 16; a store held by an open wave; a streamed wave of `node` open with registrations pending.  n == 0 returns
+ * JG_OK.
+ * All or nothing: the resolve only reads; the OR-Set side, which can still refuse as jg_orset_apply_ops_names does (a set
+ * out of element ids, an allocation), runs before any PN-Counter cell is written, and the PN-Counter adds cannot refuse
+ * once launched: a refusal leaves both stores, the element table, the names log and every output as they were. */
+#define JG_U_OK        0  /* applied (an OR-Set command's result[i] says whether it changed the set)            */
+#define JG_U_NO_KEY    1  /* keySpaces[key] throws KeyNotFoundException                                          */
+#define JG_U_NO_CRDT   2  /* the dictionary holds the key, the node has no CRDT under its guid                   */
+#define JG_U_BAD_ARG   3  /* args[0] absent, null or of the wrong type for the key's CRDT                        */
+#define JG_U_BAD_OP    4  /* the wrapper's switch has no case for the operation id                               */
+int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n,
+                        const uint64_t* key_off, const uint8_t* key_bytes,
+                        const uint8_t* op, const uint8_t* arg_flag, const int64_t* amount,
+                        const uint64_t* elem_off, const uint8_t* elem_bytes,
+                        const uint64_t* tag_lo, const uint64_t* tag_hi, uint32_t col,
+                        uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem,
+                        jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim);
+
+/* ---------------------------------------------------------------------------------------------
  * Synthetic workloads (bench / size-independent parity): device-side counter-based generators,
  * defined in DESIGN.md §Synthetic inputs and mirrored on the host by the test oracle.
  * ------------------------------------------------------------------------------------------- */

@@ -149,6 +149,7 @@ int jg_close(jg_ctx* ctx) {
         ctx->scratch.release();
         ctx->scratch2.release();
         ctx->scratch3.release();
+        ctx->scratch_u.release();
         ctx->flags.release();
         if (ctx->hstat) (void)hipHostFree(ctx->hstat);
         (void)hipStreamDestroy(ctx->stream);

@@ -150,7 +150,8 @@ struct jg_ctx {
     jg::DevBuf scratch;  // reusable per-call device scratch (key indices, query keys, staging)
     jg::DevBuf scratch2;
     jg::DevBuf scratch3;
-    jg::DevBuf flags;    // small zero-initialised status words (error flags)
+    jg::DevBuf scratch_u;  // update.hip's batch: it outlives the OR-Set side of the call, which uses the three above
+    jg::DevBuf flags;   // small zero-initialised status words (error flags)
     // page-locked bytes for small status reads and writes (a pageable copy is staged by the runtime: a blit
     // kernel plus a host copy, ~30-40 us of host gap per round trip): reads at [0, kPinRead), writes from
     // kPinRead (jg::pin_get / pin_sync / pin_at)
@@ -320,6 +321,11 @@ bool pnc_auto_widen(jg_pnc* p);
 // d_count (query.hip): answer q into slot d_at[q], for the first *d_count rows only; an overflow is written as of_code.
 void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long* d_out, uint8_t* d_ovf, const uint32_t* d_at,
                        const unsigned long long* d_count, uint8_t of_code);
+// pnc.hip: jg_pnc_apply_ops' wrapping atomic adds over a device list (update.hip): entry i adds d_amount[i] to P (or N
+// where d_is_n[i]) at (d_row[i], col), for the first min(*d_count, n_max) entries; queued on the store's stream.  The
+// rows are the caller's to check; the column is checked here.  Writes through rw_P / rw_N.
+void pnc_add_list_device(jg_pnc* p, const uint32_t* d_row, const long long* d_amount, const uint8_t* d_is_n, const unsigned long long* d_count,
+                         uint64_t n_max, uint32_t col);
 // orset.hip: merge n_runs sorted, duplicate-free runs (device SoA, run after run) into the store.
 void orset_merge_runs(jg_orset* s, uint32_t n_runs, const uint64_t* add_counts, const uint64_t* rem_counts, const unsigned long long* add_key,
                       const uint4* add_tag, const uint32_t* add_ord, const unsigned long long* rem_key, const uint4* rem_tag,

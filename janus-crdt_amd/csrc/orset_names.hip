@@ -648,145 +648,156 @@ int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint
     });
 }
 
+}  // extern "C"
+
+// jg_orset_apply_ops_names under the context lock, for it and for update.hip (the OR-Set commands of a batch by key).
+void jg::orset_apply_ops_names_locked(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint8_t* op, const uint64_t* off, const uint8_t* bytes,
+                                      const uint8_t* is_null, const uint64_t* tag_lo, const uint64_t* tag_hi, uint8_t* result, uint32_t* elem_out,
+                                      uint64_t* add_lim, uint64_t* rem_lim) {
+    jg::require_writable(s, "jg_orset_apply_ops_names");
+    JG_REQUIRE(s, JG_EINVAL, "jg_orset_apply_ops_names: store is NULL");
+    if (n_ops == 0) return;
+    const uint64_t n = n_ops;
+    JG_REQUIRE(op && tag_lo && tag_hi && result, JG_EINVAL, "jg_orset_apply_ops_names: NULL argument");
+    JG_REQUIRE(!add_lim == !rem_lim, JG_EINVAL, "jg_orset_apply_ops_names: add_lim and rem_lim go together");
+    JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_orset_apply_ops_names: at most 2^31 ops per call");
+    const uint64_t n_sets = check_names("jg_orset_apply_ops_names", n, set, off, bytes, is_null);
+    for (uint64_t i = 0; i < n; ++i)
+        JG_REQUIRE(op[i] >= 1 && op[i] <= 3, JG_EINVAL, "jg_orset_apply_ops_names: op[%llu] = %u is not 1 (Add), 2 (Remove) or 3 (Clear)",
+                   (unsigned long long)i, op[i]);
+    jg_ctx* ctx = s->ctx;
+    jg::ensure_device(ctx);
+    jg::sync_counts(s);
+
+    // each op's Clear epoch (the Clears of its set before it) and the sets Cleared, with their counts
+    std::vector<uint32_t> epoch(n), cset, ccnt;
+    uint64_t n_add = 0;
+    {
+        const bool dense = n_sets < 4 * n + 65536;
+        std::vector<uint32_t> cnt(dense ? n_sets : 0, 0u);
+        std::unordered_map<uint32_t, uint32_t> sparse;
+        for (uint64_t i = 0; i < n; ++i) {
+            uint32_t& c = dense ? cnt[set[i]] : sparse[set[i]];
+            epoch[i] = c;
+            if (op[i] == 3 && c++ == 0) cset.push_back(set[i]);
+            n_add += op[i] == 1 && !is_null[i];
+        }
+        for (uint32_t c : cset) ccnt.push_back(dense ? cnt[c] : sparse[c]);
+    }
+    const uint64_t nc = cset.size();
+    Packed P(n, nc, set, off, bytes);
+    std::memcpy(P.epoch(), epoch.data(), n * 4);
+    if (nc) std::memcpy(P.cset(), cset.data(), nc * 4), std::memcpy(P.ccnt(), ccnt.data(), nc * 4);
+    for (uint64_t i = 0; i < n; ++i) P.meta()[i] = (uint8_t)((is_null[i] ? 1 : 0) | op[i] << 1);
+
+    // every allocation first: room for the sets, the tables, the call's own block
+    jg::ElemTable& T = *jg::orset_elem_table(s, true);
+    T.ensure_sets(ctx, n_sets);
+    T.ensure_names(ctx, 0, 0);
+    JG_REQUIRE(!jg::orset_wave_open(s), JG_EINVAL, "jg_orset_apply_ops_names: a wave is open");
+    const uint64_t ccap = jg::pow2_at_least(2 * n_add, 64);
+    // the winners' sort orders on the set's bits and the op index (an unset key, all ones, sorts last either way)
+    int key_bits = 32;
+    while (key_bits < 64 && (n_sets - 1) >> (key_bits - 32)) ++key_bits;
+    using ull = unsigned long long;
+    const int n_i = jg::cub_count(n, "ops"), n1_i = jg::cub_count(n + 1, "ops");
+    // the two scans and the sort share one workspace, one after the other on the stream
+    const size_t tb = std::max(jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                                   return hipcub::DeviceRadixSort::SortKeys(temp, bytes, (const ull*)nullptr, (ull*)nullptr, n_i, 0, key_bits, ctx->stream);
+                               }),
+                               jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                                   return hipcub::DeviceScan::ExclusiveSum(temp, bytes, (ull*)nullptr, (ull*)nullptr, n1_i, ctx->stream);
+                               }));
+    uint8_t *dstage, *dtmp;
+    Cand C{nullptr, nullptr, ccap - 1};
+    ull *nkey, *cnt, *len, *wkey, *skey, *st;
+    uint32_t *rid, *slot, *newid, *delem;
+    jg::Layout L;
+    L.add(dstage, P.h.size(), 8), L.add(C.slot, ccap, 8), L.add(nkey, n, 8), L.add(cnt, n + 1, 8), L.add(len, n + 1, 8), L.add(wkey, n, 8);
+    L.add(skey, n, 8), L.add(st, 2, 8), L.add(C.first, ccap, 8), L.add(rid, n, 8), L.add(slot, n, 8), L.add(newid, n, 8), L.add(delem, n, 8);
+    L.add(dtmp, tb + 64);
+    jg::DevBuf blk;  // the call's own block: the record side below reuses the context's scratch
+    blk.alloc(L.bytes());
+    L.bind(blk.p);
+    const Staged S = P.on(dstage);
+    const auto* dcset = reinterpret_cast<const uint32_t*>(dstage + P.at_cset);
+    const auto* dccnt = reinterpret_cast<const uint32_t*>(dstage + P.at_ccnt);
+
+    // JANUS_TRACE_APPLY (as jg_orset_apply_ops): the launches' device time beside the record side's host line
+    static const bool tr = std::getenv("JANUS_TRACE_APPLY") != nullptr;
+    hipEvent_t ev[5] = {};
+    auto stamp = [&](int k) {
+        if (!tr) return;
+        JG_HIP(hipEventCreate(&ev[k]));
+        JG_HIP(hipEventRecord(ev[k], ctx->stream));
+    };
+
+    // resolve and intern (the table itself is only read)
+    stamp(0);
+    JG_HIP(hipMemcpyAsync(dstage, P.h.data(), P.h.size(), hipMemcpyHostToDevice, ctx->stream));
+    stamp(1);
+    JG_HIP(hipMemsetAsync(C.slot, 0, ccap * 8, ctx->stream));
+    JG_HIP(hipMemsetAsync(C.first, 0xFF, ccap * 4, ctx->stream));
+    JG_HIP(hipMemsetAsync(st, 0, 16, ctx->stream));
+    const dim3 grid(blocks_for(n + 1)), block(kBlock);
+    hipLaunchKernelGGL(k_nm_claim, grid, block, 0, ctx->stream, T.view(), T.kmask, T.salt, S, n, C, rid, nkey, slot);
+    hipLaunchKernelGGL(k_nm_win, grid, block, 0, ctx->stream, S, n, C, slot, cnt, len, wkey);
+    JG_HIP(hipGetLastError());
+    const auto tmp = jg::cub_in(dtmp, tb);
+    jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, cnt, n1_i, ctx->stream); });
+    jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, len, len, n1_i, ctx->stream); });
+    jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
+        return hipcub::DeviceRadixSort::SortKeys(temp, bytes, wkey, skey, n_i, 0, key_bits, ctx->stream);
+    });
+    hipLaunchKernelGGL(k_nm_assign, grid, block, 0, ctx->stream, T.view(), skey, n, newid, st);
+    hipLaunchKernelGGL(k_nm_ids, grid, block, 0, ctx->stream, S, n, C, rid, nkey, slot, newid, delem);
+    JG_HIP(hipGetLastError());
+    stamp(2);
+    std::vector<uint32_t> elem(n);
+    JG_HIP(hipMemcpyAsync(elem.data(), delem, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    jg::pin_get(ctx, 0, cnt + n, 8);
+    jg::pin_get(ctx, 8, len + n, 8);
+    jg::pin_get(ctx, 16, st, 16);
+    jg::pin_sync(ctx);
+    const auto* hw = static_cast<const uint64_t*>(jg::pin_at(ctx, 0));
+    const uint64_t n_new = hw[0], new_bytes = hw[1], over = hw[2], id_bound = hw[3];
+    JG_REQUIRE(!over, JG_ESTATE, "jg_orset_apply_ops_names: a set has no element ids left");
+    if (n_new) T.ensure_names(ctx, n_new, new_bytes);  // growing rebuilds, it changes no content
+
+    // the record side over the ids: jg_orset_apply_ops' walk and union; the table is unchanged if it refuses
+    jg::orset_apply_ops_ids(s, n, set, elem.data(), op, tag_lo, tag_hi, result, add_lim, rem_lim);
+    if (elem_out) std::memcpy(elem_out, elem.data(), n * 4);
+
+    // the table: what jg_orset_names_sync would have been told
+    stamp(3);
+    if (n_new || nc) {
+        if (n_new) hipLaunchKernelGGL(k_nm_put, grid, block, 0, ctx->stream, T.view(), T.n_names, T.pool_used, S, n, cnt, len, nkey, newid);
+        hipLaunchKernelGGL(k_nm_sets, dim3(blocks_for(std::max(n, nc))), block, 0, ctx->stream, T.view(), skey, n, dcset, dccnt, nc);
+        JG_HIP(hipGetLastError());
+        stamp(4);
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+        T.names_added(n_new, T.pool_used + new_bytes, id_bound);
+    }
+    if (tr) {
+        float up = 0, res = 0, put = 0;
+        JG_HIP(hipEventElapsedTime(&up, ev[0], ev[1]));
+        JG_HIP(hipEventElapsedTime(&res, ev[1], ev[2]));
+        if (ev[4]) JG_HIP(hipEventElapsedTime(&put, ev[3], ev[4]));
+        std::fprintf(stderr, "orset apply_ops_names(%llu ops, %llu name bytes, %llu new names): upload %.3f ms, resolve + intern launches %.3f ms, "
+                     "put launches %.3f ms\n", (unsigned long long)n, (unsigned long long)off[n], (unsigned long long)n_new, up, res, put);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+}
+
+extern "C" {
+
 int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint8_t* op, const uint64_t* off, const uint8_t* bytes,
                              const uint8_t* is_null, const uint64_t* tag_lo, const uint64_t* tag_hi, uint8_t* result, uint32_t* elem_out,
                              uint64_t* add_lim, uint64_t* rem_lim) {
     return jg::guard([&] {
         auto lk_ = jg::lock(s);
-        jg::require_writable(s, "jg_orset_apply_ops_names");
-        JG_REQUIRE(s, JG_EINVAL, "jg_orset_apply_ops_names: store is NULL");
-        if (n_ops == 0) return;
-        const uint64_t n = n_ops;
-        JG_REQUIRE(op && tag_lo && tag_hi && result, JG_EINVAL, "jg_orset_apply_ops_names: NULL argument");
-        JG_REQUIRE(!add_lim == !rem_lim, JG_EINVAL, "jg_orset_apply_ops_names: add_lim and rem_lim go together");
-        JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_orset_apply_ops_names: at most 2^31 ops per call");
-        const uint64_t n_sets = check_names("jg_orset_apply_ops_names", n, set, off, bytes, is_null);
-        for (uint64_t i = 0; i < n; ++i)
-            JG_REQUIRE(op[i] >= 1 && op[i] <= 3, JG_EINVAL, "jg_orset_apply_ops_names: op[%llu] = %u is not 1 (Add), 2 (Remove) or 3 (Clear)",
-                       (unsigned long long)i, op[i]);
-        jg_ctx* ctx = s->ctx;
-        jg::ensure_device(ctx);
-        jg::sync_counts(s);
-
-        // each op's Clear epoch (the Clears of its set before it) and the sets Cleared, with their counts
-        std::vector<uint32_t> epoch(n), cset, ccnt;
-        uint64_t n_add = 0;
-        {
-            const bool dense = n_sets < 4 * n + 65536;
-            std::vector<uint32_t> cnt(dense ? n_sets : 0, 0u);
-            std::unordered_map<uint32_t, uint32_t> sparse;
-            for (uint64_t i = 0; i < n; ++i) {
-                uint32_t& c = dense ? cnt[set[i]] : sparse[set[i]];
-                epoch[i] = c;
-                if (op[i] == 3 && c++ == 0) cset.push_back(set[i]);
-                n_add += op[i] == 1 && !is_null[i];
-            }
-            for (uint32_t c : cset) ccnt.push_back(dense ? cnt[c] : sparse[c]);
-        }
-        const uint64_t nc = cset.size();
-        Packed P(n, nc, set, off, bytes);
-        std::memcpy(P.epoch(), epoch.data(), n * 4);
-        if (nc) std::memcpy(P.cset(), cset.data(), nc * 4), std::memcpy(P.ccnt(), ccnt.data(), nc * 4);
-        for (uint64_t i = 0; i < n; ++i) P.meta()[i] = (uint8_t)((is_null[i] ? 1 : 0) | op[i] << 1);
-
-        // every allocation first: room for the sets, the tables, the call's own block
-        jg::ElemTable& T = *jg::orset_elem_table(s, true);
-        T.ensure_sets(ctx, n_sets);
-        T.ensure_names(ctx, 0, 0);
-        JG_REQUIRE(!jg::orset_wave_open(s), JG_EINVAL, "jg_orset_apply_ops_names: a wave is open");
-        const uint64_t ccap = jg::pow2_at_least(2 * n_add, 64);
-        // the winners' sort orders on the set's bits and the op index (an unset key, all ones, sorts last either way)
-        int key_bits = 32;
-        while (key_bits < 64 && (n_sets - 1) >> (key_bits - 32)) ++key_bits;
-        using ull = unsigned long long;
-        const int n_i = jg::cub_count(n, "ops"), n1_i = jg::cub_count(n + 1, "ops");
-        // the two scans and the sort share one workspace, one after the other on the stream
-        const size_t tb = std::max(jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
-                                       return hipcub::DeviceRadixSort::SortKeys(temp, bytes, (const ull*)nullptr, (ull*)nullptr, n_i, 0, key_bits, ctx->stream);
-                                   }),
-                                   jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
-                                       return hipcub::DeviceScan::ExclusiveSum(temp, bytes, (ull*)nullptr, (ull*)nullptr, n1_i, ctx->stream);
-                                   }));
-        uint8_t *dstage, *dtmp;
-        Cand C{nullptr, nullptr, ccap - 1};
-        ull *nkey, *cnt, *len, *wkey, *skey, *st;
-        uint32_t *rid, *slot, *newid, *delem;
-        jg::Layout L;
-        L.add(dstage, P.h.size(), 8), L.add(C.slot, ccap, 8), L.add(nkey, n, 8), L.add(cnt, n + 1, 8), L.add(len, n + 1, 8), L.add(wkey, n, 8);
-        L.add(skey, n, 8), L.add(st, 2, 8), L.add(C.first, ccap, 8), L.add(rid, n, 8), L.add(slot, n, 8), L.add(newid, n, 8), L.add(delem, n, 8);
-        L.add(dtmp, tb + 64);
-        jg::DevBuf blk;  // the call's own block: the record side below reuses the context's scratch
-        blk.alloc(L.bytes());
-        L.bind(blk.p);
-        const Staged S = P.on(dstage);
-        const auto* dcset = reinterpret_cast<const uint32_t*>(dstage + P.at_cset);
-        const auto* dccnt = reinterpret_cast<const uint32_t*>(dstage + P.at_ccnt);
-
-        // JANUS_TRACE_APPLY (as jg_orset_apply_ops): the launches' device time beside the record side's host line
-        static const bool tr = std::getenv("JANUS_TRACE_APPLY") != nullptr;
-        hipEvent_t ev[5] = {};
-        auto stamp = [&](int k) {
-            if (!tr) return;
-            JG_HIP(hipEventCreate(&ev[k]));
-            JG_HIP(hipEventRecord(ev[k], ctx->stream));
-        };
-
-        // resolve and intern (the table itself is only read)
-        stamp(0);
-        JG_HIP(hipMemcpyAsync(dstage, P.h.data(), P.h.size(), hipMemcpyHostToDevice, ctx->stream));
-        stamp(1);
-        JG_HIP(hipMemsetAsync(C.slot, 0, ccap * 8, ctx->stream));
-        JG_HIP(hipMemsetAsync(C.first, 0xFF, ccap * 4, ctx->stream));
-        JG_HIP(hipMemsetAsync(st, 0, 16, ctx->stream));
-        const dim3 grid(blocks_for(n + 1)), block(kBlock);
-        hipLaunchKernelGGL(k_nm_claim, grid, block, 0, ctx->stream, T.view(), T.kmask, T.salt, S, n, C, rid, nkey, slot);
-        hipLaunchKernelGGL(k_nm_win, grid, block, 0, ctx->stream, S, n, C, slot, cnt, len, wkey);
-        JG_HIP(hipGetLastError());
-        const auto tmp = jg::cub_in(dtmp, tb);
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, cnt, n1_i, ctx->stream); });
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, len, len, n1_i, ctx->stream); });
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceRadixSort::SortKeys(temp, bytes, wkey, skey, n_i, 0, key_bits, ctx->stream);
-        });
-        hipLaunchKernelGGL(k_nm_assign, grid, block, 0, ctx->stream, T.view(), skey, n, newid, st);
-        hipLaunchKernelGGL(k_nm_ids, grid, block, 0, ctx->stream, S, n, C, rid, nkey, slot, newid, delem);
-        JG_HIP(hipGetLastError());
-        stamp(2);
-        std::vector<uint32_t> elem(n);
-        JG_HIP(hipMemcpyAsync(elem.data(), delem, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        jg::pin_get(ctx, 0, cnt + n, 8);
-        jg::pin_get(ctx, 8, len + n, 8);
-        jg::pin_get(ctx, 16, st, 16);
-        jg::pin_sync(ctx);
-        const auto* hw = static_cast<const uint64_t*>(jg::pin_at(ctx, 0));
-        const uint64_t n_new = hw[0], new_bytes = hw[1], over = hw[2], id_bound = hw[3];
-        JG_REQUIRE(!over, JG_ESTATE, "jg_orset_apply_ops_names: a set has no element ids left");
-        if (n_new) T.ensure_names(ctx, n_new, new_bytes);  // growing rebuilds, it changes no content
-
-        // the record side over the ids: jg_orset_apply_ops' walk and union; the table is unchanged if it refuses
-        jg::orset_apply_ops_ids(s, n, set, elem.data(), op, tag_lo, tag_hi, result, add_lim, rem_lim);
-        if (elem_out) std::memcpy(elem_out, elem.data(), n * 4);
-
-        // the table: what jg_orset_names_sync would have been told
-        stamp(3);
-        if (n_new || nc) {
-            if (n_new) hipLaunchKernelGGL(k_nm_put, grid, block, 0, ctx->stream, T.view(), T.n_names, T.pool_used, S, n, cnt, len, nkey, newid);
-            hipLaunchKernelGGL(k_nm_sets, dim3(blocks_for(std::max(n, nc))), block, 0, ctx->stream, T.view(), skey, n, dcset, dccnt, nc);
-            JG_HIP(hipGetLastError());
-            stamp(4);
-            JG_HIP(hipStreamSynchronize(ctx->stream));
-            T.names_added(n_new, T.pool_used + new_bytes, id_bound);
-        }
-        if (tr) {
-            float up = 0, res = 0, put = 0;
-            JG_HIP(hipEventElapsedTime(&up, ev[0], ev[1]));
-            JG_HIP(hipEventElapsedTime(&res, ev[1], ev[2]));
-            if (ev[4]) JG_HIP(hipEventElapsedTime(&put, ev[3], ev[4]));
-            std::fprintf(stderr, "orset apply_ops_names(%llu ops, %llu name bytes, %llu new names): upload %.3f ms, resolve + intern launches %.3f ms, "
-                         "put launches %.3f ms\n", (unsigned long long)n, (unsigned long long)off[n], (unsigned long long)n_new, up, res, put);
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
+        jg::orset_apply_ops_names_locked(s, n_ops, set, op, off, bytes, is_null, tag_lo, tag_hi, result, elem_out, add_lim, rem_lim);
     });
 }
 

@@ -172,6 +172,23 @@ __global__ __launch_bounds__(kBlock) void k_apply_ops(typename Elem<EB>::T* __re
     }
 }
 
+// The same adds over a device list of (row, amount, P | N) on one column (update.hip): the list's length is read from
+// device memory, so the grid is fixed by the batch and no count visits the host.  The rows were checked against the
+// store by the kernel that wrote the list, the column by the host.
+template <int EB>
+__global__ __launch_bounds__(kBlock) void k_add_list(typename Elem<EB>::T* __restrict__ P, typename Elem<EB>::T* __restrict__ N,
+                                                     const uint32_t* __restrict__ row, const long long* __restrict__ amount,
+                                                     const uint8_t* __restrict__ is_n, const unsigned long long* __restrict__ count, uint64_t n_max,
+                                                     uint32_t col, uint32_t R) {
+    const uint64_t n = *count < n_max ? *count : n_max;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t at = (uint64_t)row[i] * R + col;
+        auto* base = is_n[i] ? N : P;
+        if constexpr (EB == 4) atomicAdd(reinterpret_cast<unsigned int*>(base + at), (unsigned int)amount[i]);
+        else atomicAdd(reinterpret_cast<unsigned long long*>(base + at), (unsigned long long)amount[i]);
+    }
+}
+
 // ---- PNCounter.Get: checked Sum in column order -------------------------------------------------
 template <int EB> struct Acc;
 template <> struct Acc<4> { using T = long long; };  // 64 x 2^31 fits easily
@@ -610,6 +627,19 @@ void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long*
         using T = typename Elem<EB()>::T;
         hipLaunchKernelGGL(k_values<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const T*)p->ro_P(), (const T*)p->ro_N(), p->R, d_keys, n, d_out,
                            d_ovf, d_at, d_count, of_code);
+    });
+    JG_HIP(hipGetLastError());
+}
+
+void pnc_add_list_device(jg_pnc* p, const uint32_t* d_row, const long long* d_amount, const uint8_t* d_is_n, const unsigned long long* d_count,
+                         uint64_t n_max, uint32_t col) {
+    jg_ctx* ctx = p->ctx;
+    JG_REQUIRE(col < p->R, JG_EINVAL, "pnc_add_list_device: column %u outside the store's %u", col, p->R);
+    const unsigned grid = jg::grid_for(ctx, n_max, kBlock, 16);
+    dispatch_eb(p->eb, [&](auto EB) {
+        using T = typename Elem<EB()>::T;
+        hipLaunchKernelGGL(k_add_list<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (T*)p->rw_P(), (T*)p->rw_N(), d_row, d_amount, d_is_n, d_count,
+                           n_max, col, p->R);
     });
     JG_HIP(hipGetLastError());
 }

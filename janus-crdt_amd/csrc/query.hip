@@ -27,6 +27,7 @@
 #include "orset_names.hpp"
 #include "tpset_dict.hpp"
 #include "uid_table.hpp"
+#include "wave_append.hpp"
 
 namespace {
 
@@ -48,16 +49,7 @@ struct QOut {
     ull* count;  // [0] PN-Counter reads, [1] OR-Set reads (zeroed before the launch)
 };
 
-// slot of this lane in a list the wave appends `take` lanes to: one atomic per wave
-__device__ __forceinline__ ull wave_append(bool take, ull* count) {
-    const ull mask = __ballot(take);
-    if (mask == 0) return 0;
-    const int lane = threadIdx.x & 63, first = __ffsll(mask) - 1;
-    ull base = 0;
-    if (lane == first) base = atomicAdd(count, (ull)__popcll(mask));
-    base = __shfl(base, first, 64);
-    return base + __popcll(mask & ((1ull << lane) - 1));
-}
+using jg::wave_append;
 
 __global__ __launch_bounds__(kBlock) void k_q_resolve(jgt::Store S, jgt::Dict D, jg::DevUids U, uint64_t pnc_rows, jgn::Names N, uint64_t set_cap,
                                                       uint64_t kmask, uint64_t nsalt, QIn in, uint64_t n, QOut o) {

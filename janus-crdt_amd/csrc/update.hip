@@ -1,0 +1,271 @@
+// update.hip — client writes by key name, resolved on the device: jg_node_update_keys.
+//
+// The reference's "i" / "d" / "a" / "r" / "c" commands (CRDTCommands/PNCounterCommand.cs:42-53, ORSetCommand.cs:43-61) go
+// KeySpaceManager.GetKVPair -> SafeCRDT.Update (SafeCRDT.cs:39-47) -> prospectiveState.Update(operationID, args) in
+// PNCounterWrapper (PNCounterWrapper.cs:33-48) or ORSetWrapper (ORSetWrapper.cs:30-47).  The tables that chain is made
+// of are resident (§9, §11, §12); this file walks them for a batch of commands and applies what resolved:
+//
+//   k_u_resolve  one lane per command: FNV-1a of the key -> dict_find in the key space's dictionary (tpset_dict.hpp)
+//                -> uid_find in the node's uid table (uid_table.hpp) -> (type, row | set), the chain of k_q_resolve,
+//                then the two wrappers' status rules.  It writes status, kind, idx and guid, and each wave appends its
+//                resolved PN-Counter ops (row, amount, P | N) to one list with one ballot and one atomic
+//                (wave_append.hpp).  It reads only: the element table is not touched and no store is written.
+//   OR-Set side  the set ids have to reach the host (the Clear epochs and the record walk of apply_ops_names are host
+//                work, §11): one D2H of idx | status | kind, the OR-Set commands compacted in batch order, the body of
+//                jg_orset_apply_ops_names over them, results scattered back by command index.  It can refuse (a set out
+//                of ids, an allocation) and runs before any PN-Counter cell is written.  A node without an OR-Set store
+//                skips the round trip; a batch without an OR-Set command launches nothing of it.
+//   adds         jg_pnc_apply_ops' wrapping atomic adds over the list (pnc.hip k_add_list), its length read from device
+//                memory: a fixed grid, no count on the host.  They cannot refuse once launched.
+//
+// The resolve is a dependent chain of random lines: the kernel waits on memory, uses no LDS and few registers, so
+// occupancy is what hides the latency.  Nothing is published inside a launch: the kernel boundaries publish the list
+// and its count.
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "launch.hpp"
+#include "orset_names.hpp"
+#include "tpset_dict.hpp"
+#include "uid_table.hpp"
+#include "wave_append.hpp"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr uint32_t kNever = JG_NULL_ELEM - 1;  // "never allocated": the id no record carries (orset_names.hip)
+constexpr uint32_t kNoIdx = 0xFFFFFFFFu;       // idx of a command that applied nothing
+using ull = unsigned long long;
+
+struct UIn {  // the staged batch
+    const ull* koff;
+    const long long* amount;  // NULL: no command carries an integer
+    const uint8_t *kbytes, *op, *flag;
+};
+struct UOut {
+    uint8_t *status, *kind;
+    uint32_t* idx;
+    jg_guid* guid;
+    uint32_t* prow;  // resolved PN-Counter ops: row, amount, 0 = P | 1 = N
+    long long* pamt;
+    uint8_t* pisn;
+    ull* count;  // their number (zeroed before the launch)
+};
+
+__global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D, jg::DevUids U, uint64_t pnc_rows, bool has_orset, UIn in, uint64_t n,
+                                                      UOut o) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool is_p = false;
+    uint32_t row = 0;
+    long long amt = 0;
+    uint8_t isn = 0;
+    if (i < n) {
+        uint8_t st = JG_U_NO_KEY, kd = 255;
+        uint32_t ix = kNoIdx;
+        ull glo = 0, ghi = 0;
+        const uint8_t* k = in.kbytes + in.koff[i];
+        const uint32_t klen = (uint32_t)(in.koff[i + 1] - in.koff[i]);
+        const uint32_t d = jgt::dict_find(S, D, jgt::key_hash(k, klen, S.salt), k, klen);
+        if (d != jgt::kNone) {
+            glo = D.glo[d], ghi = D.ghi[d];
+            const uint32_t v = (glo | ghi) != 0 ? jg::uid_find(U, glo, ghi) : jg::kNoSlot;
+            const uint32_t op = in.op[i], flag = in.flag[i];
+            if (v == jg::kNoSlot) {
+                st = JG_U_NO_CRDT;
+            } else if (!(v & jg::kOrSetBit)) {
+                kd = 0;
+                if (v >= pnc_rows) st = JG_U_NO_CRDT;  // jg_node_register checked the row and stores never shrink
+                else if (flag != 3) st = JG_U_BAD_ARG;  // (int)args[0] comes before the switch
+                else if (op != 1 && op != 2) st = JG_U_BAD_OP;
+                else {
+                    st = JG_U_OK;
+                    is_p = true;
+                    ix = row = v;
+                    amt = in.amount[i];
+                    isn = op == 2;
+                }
+            } else {
+                kd = 1;
+                if (!has_orset) st = JG_U_NO_CRDT;
+                else if (op < 1 || op > 3) st = JG_U_BAD_OP;  // the switch comes before args[0]
+                else if (op != 3 && flag != 1 && flag != 2) st = JG_U_BAD_ARG;
+                else {
+                    st = JG_U_OK;
+                    ix = v & ~jg::kOrSetBit;
+                }
+            }
+        }
+        o.status[i] = st;
+        o.kind[i] = kd;
+        o.idx[i] = ix;
+        if (o.guid) o.guid[i] = jg_guid{glo, ghi};
+    }
+    const ull sp = jg::wave_append(is_p, o.count);
+    if (is_p) o.prow[sp] = row, o.pamt[sp] = amt, o.pisn[sp] = isn;
+}
+
+void check_offsets(const char* what, uint64_t n, const uint64_t* off) {
+    JG_REQUIRE(off[0] == 0, JG_EINVAL, "jg_node_update_keys: %s_off[0] must be 0", what);
+    for (uint64_t i = 0; i < n; ++i)
+        JG_REQUIRE(off[i] <= off[i + 1] && off[i + 1] - off[i] < 0x7FFFFFFFull, JG_EINVAL, "jg_node_update_keys: %s offsets decrease at %llu", what,
+                   (ull)i);
+    JG_REQUIRE(off[n] < (1ull << 40), JG_EINVAL, "jg_node_update_keys: batch too large");
+}
+
+}  // namespace
+
+extern "C" {
+
+int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                        const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
+                        const uint64_t* tag_hi, uint32_t col, uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem,
+                        jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(ks);  // calls on one context are serialised (shared scratch, stream)
+        if (n == 0) return;
+        // every refusal below is decided from the arguments: nothing has been copied or written yet
+        JG_REQUIRE(node && ks && op && arg_flag && status && result, JG_EINVAL, "jg_node_update_keys: NULL argument");
+        JG_REQUIRE(jg::node_ctx(node) == ks->ctx, JG_EINVAL, "jg_node_update_keys: the key space and the node belong to different contexts");
+        JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_node_update_keys: at most 2^31 commands per call");
+        JG_REQUIRE(!add_lim == !rem_lim, JG_EINVAL, "jg_node_update_keys: add_lim and rem_lim go together");
+        JG_REQUIRE(key_off, JG_EINVAL, "jg_node_update_keys: key_off is NULL");
+        check_offsets("key", n, key_off);
+        JG_REQUIRE(key_off[n] == 0 || key_bytes, JG_EINVAL, "jg_node_update_keys: key_bytes is NULL");
+        if (elem_off) check_offsets("elem", n, elem_off);
+        uint64_t n_flag[4] = {0, 0, 0, 0};
+        for (uint64_t i = 0; i < n; ++i) {
+            JG_REQUIRE(arg_flag[i] <= 3, JG_EINVAL, "jg_node_update_keys: arg_flag[%llu] = %u (0 none, 1 string, 2 null, 3 integer)", (ull)i,
+                       arg_flag[i]);
+            ++n_flag[arg_flag[i]];
+        }
+        JG_REQUIRE(n_flag[3] == 0 || amount, JG_EINVAL, "jg_node_update_keys: a command carries an integer and amount is NULL");
+        JG_REQUIRE(n_flag[1] == 0 || (elem_off && elem_bytes), JG_EINVAL,
+                   "jg_node_update_keys: a command carries a string and elem_off or elem_bytes is NULL");
+        JG_REQUIRE(n_flag[1] + n_flag[2] == 0 || (tag_lo && tag_hi), JG_EINVAL,
+                   "jg_node_update_keys: a command carries an element and tag_lo or tag_hi is NULL");
+        jg_ctx* ctx = ks->ctx;
+        jg::ensure_device(ctx);
+        const jg::NodeRef nd = jg::node_query_ref(node, "jg_node_update_keys");  // pending registrations to the device
+        JG_REQUIRE(!nd.pnc || col < nd.pnc->R, JG_EINVAL, "jg_node_update_keys: column %u outside the PN-Counter store's %u", col,
+                   nd.pnc ? nd.pnc->R : 0);
+        jg::require_writable(nd.pnc, "jg_node_update_keys");
+        jg::require_writable(nd.orset, "jg_node_update_keys");
+        JG_REQUIRE(!nd.orset || !jg::orset_wave_open(nd.orset), JG_EINVAL, "jg_node_update_keys: a wave is open on the OR-Set store");
+
+        // keys, ops, flags and amounts in one staging copy: koff | amount | key bytes | op | flag.  The elements stay on the
+        // host: only the OR-Set side reads them, compacted.
+        const uint64_t kb = key_off[n];
+        const bool ints = n_flag[3] != 0;
+        UIn in{};
+        UOut o{};
+        jg::Layout L;
+        L.add(in.koff, n + 1, 8), L.add(in.amount, ints ? n : 0, 8), L.add(in.kbytes, kb, 8), L.add(in.op, n, 1), L.add(in.flag, n, 1);
+        const size_t stage = L.skip(0, 8);
+        std::vector<uint8_t> h(stage);
+        L.bind(h.data());  // the host image first: the same offsets as on the device
+        std::memcpy(h.data(), key_off, (n + 1) * 8);
+        if (ints) std::memcpy(const_cast<long long*>(in.amount), amount, n * 8);
+        if (kb) std::memcpy(const_cast<uint8_t*>(in.kbytes), key_bytes, kb);
+        std::memcpy(const_cast<uint8_t*>(in.op), op, n);
+        std::memcpy(const_cast<uint8_t*>(in.flag), arg_flag, n);
+        // behind it (16 bytes on): count | guid | pamt | prow | idx | status | kind | pisn; idx, status and kind are one
+        // stretch of 6 n bytes (one copy out)
+        L.skip(16);
+        L.add(o.count, 1, 8), L.add(o.guid, guid ? n : 0, 8), L.add(o.pamt, n, 8), L.add(o.prow, n, 4);
+        L.add(o.idx, n, 4), L.add(o.status, n, 1), L.add(o.kind, n, 1), L.add(o.pisn, n, 1);
+        auto* d = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch_u, L.bytes() + 64));
+        L.bind(d);
+        if (!ints) in.amount = nullptr;
+        if (!guid) o.guid = nullptr;
+
+        // JANUS_TRACE_UPDATE (as JANUS_TRACE_QUERY): the upload, the launches and the copies out by hipEvents
+        static const bool tr = std::getenv("JANUS_TRACE_UPDATE") != nullptr;
+        hipEvent_t ev[6] = {};
+        auto stamp = [&](int k) {
+            if (!tr) return;
+            JG_HIP(hipEventCreate(&ev[k]));
+            JG_HIP(hipEventRecord(ev[k], ctx->stream));
+        };
+        stamp(0);
+        JG_HIP(hipMemcpyAsync(d, h.data(), stage, hipMemcpyHostToDevice, ctx->stream));
+        stamp(1);
+        JG_HIP(hipMemsetAsync(o.count, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_u_resolve, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
+                           nd.pnc ? nd.pnc->n_keys : 0, nd.orset != nullptr, in, n, o);
+        JG_HIP(hipGetLastError());
+        stamp(2);
+
+        // idx | status | kind on the host: before the OR-Set side where the node has one, else with the other copies out
+        std::vector<uint8_t> hres(n * 6);
+        const auto* h_idx = reinterpret_cast<const uint32_t*>(hres.data());
+        const uint8_t *h_status = hres.data() + n * 4, *h_kind = hres.data() + n * 5;
+        std::vector<uint8_t> res(n, 0);
+        std::vector<uint32_t> el(elem ? n : 0, kNever);
+        std::vector<uint64_t> al(add_lim ? n : 0, 0), rl(add_lim ? n : 0, 0);
+        double host_ms = 0;
+        uint64_t n_o = 0;
+        if (nd.orset) {
+            JG_HIP(hipMemcpyAsync(hres.data(), o.idx, n * 6, hipMemcpyDeviceToHost, ctx->stream));
+            JG_HIP(hipStreamSynchronize(ctx->stream));
+            const double t0 = jg::now_us();
+            std::vector<uint32_t> at;  // the OR-Set commands, in batch order
+            for (uint64_t i = 0; i < n; ++i)
+                if (h_status[i] == JG_U_OK && h_kind[i] == 1) at.push_back((uint32_t)i);
+            n_o = at.size();
+            if (n_o) {
+                std::vector<uint32_t> oset(n_o), oel(n_o);
+                std::vector<uint8_t> oop(n_o), onull(n_o), ores(n_o), obytes;
+                std::vector<uint64_t> ooff(n_o + 1, 0), olo(n_o), ohi(n_o), oal(add_lim ? n_o : 0), orl(add_lim ? n_o : 0);
+                for (uint64_t k = 0; k < n_o; ++k) {
+                    const uint32_t i = at[k];
+                    const bool str = op[i] != 3 && arg_flag[i] == 1;  // a Clear ignores its argument
+                    oset[k] = h_idx[i], oop[k] = op[i], onull[k] = op[i] != 3 && arg_flag[i] == 2;
+                    olo[k] = tag_lo ? tag_lo[i] : 0, ohi[k] = tag_hi ? tag_hi[i] : 0;  // NULL: the batch's OR-Set commands are all Clears
+                    if (str) obytes.insert(obytes.end(), elem_bytes + elem_off[i], elem_bytes + elem_off[i + 1]);
+                    ooff[k + 1] = obytes.size();
+                }
+                if (obytes.empty()) obytes.push_back(0);
+                // all or nothing: a refusal here has written no PN-Counter cell, and apply_ops_names leaves its own store,
+                // the element table and the names log as they were
+                jg::orset_apply_ops_names_locked(nd.orset, n_o, oset.data(), oop.data(), ooff.data(), obytes.data(), onull.data(), olo.data(),
+                                                 ohi.data(), ores.data(), oel.data(), add_lim ? oal.data() : nullptr, add_lim ? orl.data() : nullptr);
+                for (uint64_t k = 0; k < n_o; ++k) {
+                    const uint32_t i = at[k];
+                    res[i] = ores[k];
+                    if (elem) el[i] = oel[k];
+                    if (add_lim) al[i] = oal[k], rl[i] = orl[k];
+                }
+            }
+            host_ms = (jg::now_us() - t0) * 1e-3;
+        }
+        stamp(3);
+        if (nd.pnc) jg::pnc_add_list_device(nd.pnc, o.prow, o.pamt, o.pisn, o.count, n, col);
+        stamp(4);
+        if (!nd.orset) JG_HIP(hipMemcpyAsync(hres.data(), o.idx, n * 6, hipMemcpyDeviceToHost, ctx->stream));
+        if (guid) JG_HIP(hipMemcpyAsync(guid, o.guid, n * sizeof(jg_guid), hipMemcpyDeviceToHost, ctx->stream));
+        stamp(5);
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint64_t i = 0; i < n; ++i)
+            if (h_status[i] == JG_U_OK && h_kind[i] == 0) res[i] = 1;
+        std::memcpy(status, h_status, n);
+        std::memcpy(result, res.data(), n);
+        if (kind) std::memcpy(kind, h_kind, n);
+        if (idx) std::memcpy(idx, h_idx, n * 4);
+        if (elem) std::memcpy(elem, el.data(), n * 4);
+        if (add_lim) std::memcpy(add_lim, al.data(), n * 8), std::memcpy(rem_lim, rl.data(), n * 8);
+        if (tr) {
+            float up = 0, run = 0, add = 0, down = 0;
+            JG_HIP(hipEventElapsedTime(&up, ev[0], ev[1]));
+            JG_HIP(hipEventElapsedTime(&run, ev[1], ev[2]));
+            JG_HIP(hipEventElapsedTime(&add, ev[3], ev[4]));
+            JG_HIP(hipEventElapsedTime(&down, ev[4], ev[5]));
+            std::fprintf(stderr, "update_keys(%llu commands, %llu bytes up, %llu bytes down): upload %.3f ms, resolve launch %.3f ms, "
+                         "PN-Counter adds %.3f ms, copies out %.3f ms; OR-Set side (%llu commands, after a copy of 6 bytes per command) %.3f ms\n",
+                         (ull)n, (ull)stage, (ull)(n * (6 + (guid ? 16 : 0))), up, run, add, down, (ull)n_o, host_ms);
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        }
+    });
+}
+
+}  // extern "C"

@@ -808,6 +808,59 @@ std::vector<KeyAnswer> GpuStableStore::QueryKeys(GpuKeySpace& ks, const std::vec
     return out;
 }
 
+std::vector<KeyUpdate> GpuStableStore::UpdateKeys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands) {
+    const size_t n = commands.size();
+    std::vector<KeyUpdate> out(n);
+    if (n == 0) return out;
+    flush_registrations();  // CreateSafeCRDTs not yet sent: the node's uid table
+    flush_names();          // names interned here that the engine's element table has not seen
+    std::vector<uint64_t> key_off(n + 1, 0), elem_off(n + 1, 0), tag_lo(n), tag_hi(n);
+    std::vector<uint8_t> key_bytes, elem_bytes, op(n), flag(n);
+    std::vector<int64_t> amount(n);
+    for (size_t i = 0; i < n; ++i) {
+        const KeyCommand& c = commands[i];
+        key_bytes.insert(key_bytes.end(), c.key.begin(), c.key.end());
+        key_off[i + 1] = key_bytes.size();
+        op[i] = c.opId < 0 || c.opId > 255 ? 255 : (uint8_t)c.opId;  // no wrapper has a case past 3
+        flag[i] = c.arg;
+        amount[i] = eb_ == 4 ? (int64_t)(int32_t)c.amount : c.amount;
+        if (c.arg == 1) elem_bytes.insert(elem_bytes.end(), c.elem.begin(), c.elem.end());
+        elem_off[i + 1] = elem_bytes.size();
+        tag_lo[i] = c.tag.lo, tag_hi[i] = c.tag.hi;
+    }
+    if (key_bytes.empty()) key_bytes.push_back(0);
+    if (elem_bytes.empty()) elem_bytes.push_back(0);
+    std::vector<uint8_t> status(n), result(n), kind(n);
+    std::vector<uint32_t> idx(n), elem(n);
+    check(jg_node_update_keys(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(), elem_off.data(),
+                              elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, status.data(), result.data(), kind.data(), idx.data(), elem.data(),
+                              nullptr, nullptr, nullptr));
+    // The per-set tables.  A set's ids only grow, so the names this batch interned are ids names.size().. in the order of
+    // their first Add; those issued before the set's last Clear are dead, as is every older id (the Clear path of
+    // PrepareOps: elems emptied, indexed = the ids issued so far).  The engine's table knows the Clear already, so
+    // nothing is left pending for jg_orset_names_sync.
+    std::unordered_map<uint32_t, std::pair<uint32_t, uint32_t>> walk;  // set -> (ids issued so far, ids dead at its last Clear)
+    for (size_t i = 0; i < n; ++i) {
+        out[i] = KeyUpdate{status[i], result[i], kind[i], idx[i]};
+        if (status[i] != JG_U_OK || kind[i] != 1) continue;
+        auto it = walk.find(idx[i]);
+        if (it == walk.end()) {
+            if (idx[i] >= sets_.size()) throw EngineError(JG_ESTATE, "UpdateKeys: a set this mirror never created");
+            const uint32_t have = (uint32_t)sets_[idx[i]].names.size();
+            it = walk.emplace(idx[i], std::make_pair(have, UINT32_MAX)).first;
+        }
+        if (op[i] == 3) it->second.second = it->second.first;
+        else if (op[i] == 1 && flag[i] == 1 && elem[i] == it->second.first) ++it->second.first;
+    }
+    for (const auto& [set, w] : walk) {
+        if (w.second == UINT32_MAX) continue;  // no Clear: the new names are indexed lazily (elem_id_in)
+        sets_[set].elems.clear();
+        sets_[set].indexed = w.second;
+    }
+    materialize_names();  // the names the call interned, from the engine's log
+    return out;
+}
+
 std::vector<std::string> GpuStableStore::EncodePNCStates(const std::vector<Guid>& uids) {
     flush_registrations();
     std::vector<uint32_t> rows;

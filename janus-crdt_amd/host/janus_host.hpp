@@ -155,6 +155,23 @@ struct PackedKeyQueries {
 };
 PackedKeyQueries PackKeyQueries(const std::vector<KeyQuery>& queries);
 
+// One write by key name, "i" / "d" / "a" / "r" / "c" (PNCounterCommand.cs:42-53, ORSetCommand.cs:43-61): SafeCRDT.Update's
+// operationID and args as the command handler passes them, and what jg_node_update_keys reports for it.
+struct KeyCommand {
+    std::string key;
+    int opId = 0;                     // SafeCRDT.Update's operationID (the reference's "d" handler passes 1)
+    uint8_t arg = 0;                  // args[0]: 0 none, 1 the string `elem`, 2 the C# null, 3 the integer `amount`
+    int64_t amount = 0;
+    std::string elem;
+    Guid tag;                         // ORSet.Add's Guid.NewGuid()
+};
+struct KeyUpdate {
+    uint8_t status = 0;       // JG_U_*
+    uint8_t result = 0;       // Update's bool; 0 for a failed command
+    uint8_t kind = 255;       // 0 PNCounter, 1 ORSet, 255 unresolved
+    uint32_t idx = 0xFFFFFFFFu;  // the row or set the command touched
+};
+
 class GpuKeySpace;  // keyspace.hpp
 
 // One CRDT copy (stable or prospective) of every key of one node, resident on one GPU.
@@ -265,6 +282,13 @@ class GpuStableStore {
     // space must live on this store's context.  Statuses are reported, not thrown: the caller maps them to the
     // reference's outputs.
     std::vector<KeyAnswer> QueryKeys(GpuKeySpace& ks, const std::vector<KeyQuery>& queries);
+    // A batch of writes by key NAME on this copy (the prospective copy of a node): ONE jg_node_update_keys on this
+    // copy's own replica column (column 0), which resolves key -> Guid -> (type, row | set) on the device and applies
+    // prospectiveState.Update(opId, args) per command, in order.  Registrations and names not yet sent are flushed
+    // first; the names the call interned are pulled afterwards, and every applied Clear is recorded in the per-set
+    // tables, so a later SubmitClientUpdates / EncodeORSetStates on the same sets sees what the engine holds.
+    // Statuses are reported, not thrown.
+    std::vector<KeyUpdate> UpdateKeys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands);
     // GetLastSynchronizedUpdate().Encode() of PN-Counter keys, encoded on the device — the payload
     // SafeCRDT.Update ships after a client op (SafeCRDT.cs:49; batch producer).
     std::vector<std::string> EncodePNCStates(const std::vector<Guid>& uids);
@@ -437,6 +461,11 @@ class GpuStableStore {
 // "gp" / "gs" for a batch of key names on the chosen copy of a node (the prospective or the stable store).
 inline std::vector<KeyAnswer> QueryKeys(GpuKeySpace& ks, GpuStableStore& copy, const std::vector<KeyQuery>& queries) {
     return copy.QueryKeys(ks, queries);
+}
+
+// "i" / "d" / "a" / "r" / "c" for a batch of key names on a copy of a node (usually the prospective store).
+inline std::vector<KeyUpdate> UpdateKeys(GpuKeySpace& ks, GpuStableStore& copy, const std::vector<KeyCommand>& commands) {
+    return copy.UpdateKeys(ks, commands);
 }
 
 }  // namespace janus

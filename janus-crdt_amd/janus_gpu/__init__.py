@@ -45,7 +45,7 @@ EXPORTS = [
     "jg_tpset_create", "jg_tpset_destroy", "jg_tpset_size", "jg_tpset_apply_ops", "jg_tpset_contains", "jg_tpset_lookup_all",
     "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
-    "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys",
+    "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys", "jg_node_update_keys",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
     "jg_rows_set_narrow", "jg_rows_form",
@@ -172,6 +172,7 @@ _SIGS = {
     "jg_keyspace_new_keys": ([_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _vp, _vp, _vp], C.c_int),
     "jg_keyspace_lookup": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
     "jg_node_query_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_node_update_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
@@ -215,6 +216,29 @@ def pack_queries(keys, elems=None):
     if edata.size == 0:
         edata = np.zeros(1, np.uint8)  # all three pointers are given or none is
     return koff, kdata, eoff, edata, flag
+
+
+# jg_node_update_keys: status[i] (kind[i] as for query_keys)
+JG_U_OK, JG_U_NO_KEY, JG_U_NO_CRDT, JG_U_BAD_ARG, JG_U_BAD_OP = range(5)
+
+
+def pack_commands(keys, ops, args):
+    """Node.update_keys' packing: (key_off u64[n+1], key_bytes u8, op u8, arg_flag u8, amount i64 | None, elem_off | None,
+    elem_bytes | None).  keys: str | bytes; ops[i]: SafeCRDT.Update's operationID; args[i]: None = no argument (flag 0),
+    str | bytes = that string (flag 1; "" is a string), NULL_ARG = the C# null (flag 2), int = that integer (flag 3).
+    A batch without integers has amount None; one without strings has both element arrays None."""
+    if not (len(keys) == len(ops) == len(args)):
+        raise ValueError("update_keys: one op and one args entry per key")
+    kdata, koff = pack_wave([_utf8(k) for k in keys])
+    is_int = [isinstance(a, (int, np.integer)) and not isinstance(a, bool) for a in args]
+    flag = np.array([0 if a is None else 2 if a is NULL_ARG else 3 if i else 1 for a, i in zip(args, is_int)], np.uint8)
+    amount = np.array([int(a) if i else 0 for a, i in zip(args, is_int)], np.int64) if any(is_int) else None
+    eoff = edata = None
+    if (flag == 1).any():
+        edata, eoff = pack_wave([_utf8(a) if f == 1 else b"" for a, f in zip(args, flag)])
+        if edata.size == 0:
+            edata = np.zeros(1, np.uint8)  # a batch of "" alone still gives both pointers
+    return koff, kdata, _arr(ops, np.uint8), flag, amount, eoff, edata
 
 
 class JanusError(RuntimeError):
@@ -1012,6 +1036,30 @@ class Node:
         _check(load().jg_node_query_keys(self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(eoff), _ptr(edata), _ptr(flag),
                                          _ptr(value), _ptr(status), _ptr(kind), _ptr(guid)))
         return (value, status, kind, guid) if with_guid else (value, status, kind)
+
+    def update_keys(self, keyspace: "KeySpace", keys, ops, args, tags=None, col: int = 0, with_guid: bool = False, ords: bool = False):
+        """jg_node_update_keys: SafeCRDT.Update(ops[i], args[i]) on the CRDT keys[i] names on this copy, in batch order,
+        resolved on the device.  args as pack_commands takes them; tags: (tag_lo, tag_hi) u64 arrays, one entry per
+        command (needed when a command carries a string or NULL_ARG); col: this copy's replica column.  Returns a dict of
+        status (JG_U_*), result, kind (Q_*), idx (row | set id, 0xFFFFFFFF for a failed command), elem, and with_guid:
+        guid, ords: add_lim, rem_lim."""
+        n = len(keys)
+        koff, kdata, op, flag, amount, eoff, edata = pack_commands(keys, ops, args)
+        lo, hi = (None, None) if tags is None else (_arr(tags[0], np.uint64), _arr(tags[1], np.uint64))
+        if lo is not None and (lo.size != n or hi.size != n):
+            raise ValueError("update_keys: one tag per command")
+        out = {"status": np.zeros(n, np.uint8), "result": np.zeros(n, np.uint8), "kind": np.zeros(n, np.uint8),
+               "idx": np.zeros(n, np.uint32), "elem": np.zeros(n, np.uint32)}
+        guid = np.zeros(n, GUID_DTYPE) if with_guid else None
+        al, rl = (np.zeros(n, np.uint64), np.zeros(n, np.uint64)) if ords else (None, None)
+        _check(load().jg_node_update_keys(self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(op), _ptr(flag), _ptr(amount), _ptr(eoff),
+                                          _ptr(edata), _ptr(lo), _ptr(hi), col, _ptr(out["status"]), _ptr(out["result"]), _ptr(out["kind"]),
+                                          _ptr(out["idx"]), _ptr(out["elem"]), _ptr(guid), _ptr(al), _ptr(rl)))
+        if with_guid:
+            out["guid"] = guid
+        if ords:
+            out["add_lim"], out["rem_lim"] = al, rl
+        return out
 
     def _commit(self, lo, hi, types, seqs, msgs=None, data=None, off=None, pinned=None):
         if msgs is not None:
