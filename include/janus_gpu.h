@@ -626,7 +626,7 @@ int jg_waves_update_digests(const jg_wave* const* waves, uint64_t n_waves, const
 int jg_wave_sha256(const jg_wave* wave, void* d_out, uint8_t async);
 
 /* ---------------------------------------------------------------------------------------------
- * Key-space set (csrc/tpset.hip) — one TPSet<string?> resident on the device
+ * Key-space set (csrc/tpset.hip, csrc/tpset_encode.hip) — one TPSet<string?> resident on the device
  * (MergeSharp/MergeSharp/CRDTs/2P-Set.cs:60-213), the CRDT Janus keeps its own key space in
  * (BFT-CRDT/CRDTManagers/KeySpaceManager.cs:34,87: every key as key + "\0" + guid).  Additive to ABI v10: these
  * entry points are new names, nothing existing changes (JG_ABI_VERSION stays 10); jg_apply_committed /
@@ -690,7 +690,7 @@ typedef struct jg_tpset_stats {
 int jg_tpset_last_stats(jg_tpset* set, jg_tpset_stats* out);
 
 /* ---------------------------------------------------------------------------------------------
- * Key space (csrc/tpset.hip) — KeySpaceManager's state on the device (BFT-CRDT/CRDTManagers/KeySpaceManager.cs): the
+ * Key space (csrc/keyspace.hip) — KeySpaceManager's state on the device (BFT-CRDT/CRDTManagers/KeySpaceManager.cs): the
  * set above, the keySpaces dictionary (key string -> Guid, :30) and the LastKeySpaceSet watermark (:35).  Additive
  * to ABI v10.  Keys are UTF-8 bytes in (off[n + 1], off[0] = 0, bytes) batches; Guids are jg_guid.
  * ------------------------------------------------------------------------------------------- */

@@ -1,6 +1,7 @@
 // tpset_dict.hpp — the resident TPSet<string?> and the key-space dictionary as kernels see them, with their probes:
-// shared by tpset.hip (which owns, fills and grows both) and query.hip (which only reads them).  One definition of
-// the string hash: a lookup that hashed differently from the inserts would find nothing.
+// shared by tpset.hip and keyspace.hip (which own, fill and grow the set and the dictionary), tpset_encode.hip, query.hip
+// and update.hip (which only read them).  One definition of the string hash: a lookup that hashed differently from the
+// inserts would find nothing.  Also the call-wide "first index wins" table both owners resolve a call's duplicates in.
 #pragma once
 
 #include "jg_internal.hpp"
@@ -8,6 +9,8 @@
 namespace jgt {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kNullId = 0xFFFFFFFEu;  // the null element's id in add[] / rem[]
+constexpr uint32_t kBlock = 256;           // lanes per workgroup of every kernel of the set and the key space
 constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3ull;
 using ull = unsigned long long;
 
@@ -42,6 +45,7 @@ struct Store {
     uint64_t salt;
 };
 
+__device__ __forceinline__ uint64_t umin(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ bool same_bytes(const uint8_t* a, const uint8_t* b, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i)
         if (a[i] != b[i]) return false;
@@ -58,7 +62,7 @@ __device__ inline uint32_t store_find(const Store& S, uint64_t key, const uint8_
     }
 }
 
-// ---- the keySpaces dictionary: an entry holds no bytes of its own (tpset.hip, jg_keyspace) ----------
+// ---- the keySpaces dictionary: an entry holds no bytes of its own (keyspace.hip, jg_keyspace) -------
 struct Dict {
     uint32_t* table;  // dictionary id + 1, 0 = empty
     uint64_t mask;
@@ -77,6 +81,31 @@ __device__ inline uint32_t dict_find(const Store& S, const Dict& D, ull key, con
         if (v == 0) return kNone;
         const uint32_t d = v - 1;
         if (D.key[d] == key && D.klen[d] == klen && same_bytes(S.pool + S.soff[D.sid[d]], k, klen)) return d;
+    }
+}
+
+// ---- the call-wide table: one slot per distinct string among a call's items -----------------------
+// prep[slot] = a representative item holding the slot's string, + 1 (0 = empty); same(o) = item o's string equals the
+// one looked for; key = its table key.  The callers take an atomicMin of the item index per slot, so the first item
+// of each distinct string wins.
+// claim_slot: the slot of item i's string, claimed for i if no item holds it yet.  A lost CAS is answered by the value
+// it returned, never by waiting: the slot then holds some item's string, equal to this one or not.
+template <class Same> __device__ __forceinline__ uint32_t claim_slot(uint32_t* prep, uint64_t pmask, ull key, uint32_t i, Same same) {
+    for (uint64_t slot = key & pmask;; slot = (slot + 1) & pmask) {
+        uint32_t r = prep[slot];
+        if (r == 0) {
+            r = atomicCAS(&prep[slot], 0u, i + 1);
+            if (r == 0) return (uint32_t)slot;
+        }
+        if (same(r - 1)) return (uint32_t)slot;
+    }
+}
+// find_slot: the same walk once the table only is read; kNone if no item claimed the string
+template <class Same> __device__ __forceinline__ uint32_t find_slot(const uint32_t* prep, uint64_t pmask, ull key, Same same) {
+    for (uint64_t slot = key & pmask;; slot = (slot + 1) & pmask) {
+        const uint32_t r = prep[slot];
+        if (r == 0) return kNone;
+        if (same(r - 1)) return (uint32_t)slot;
     }
 }
 

@@ -1,4 +1,4 @@
-// host/bench_keyspace.cpp — the key-space set's four shapes on the device (jg_tpset_*, csrc/tpset.hip) beside the same
+// host/bench_keyspace.cpp — the key-space set's four shapes on the device (jg_tpset_*, csrc/tpset.hip, tpset_encode.hip; (e): keyspace.hip) beside the same
 // work on host/tpset_ref.hpp with one thread (a port of the reference's decode + UnionWith, as README's other CPU
 // baselines are).  K entries of the C5 key shape: 11-byte key, NUL, 36-byte Guid.
 //   (a) steady creation: a resident set of K receives one full state of K + 1 entries; also with the serial parser

@@ -1,7 +1,8 @@
 // host/tpset_ref.hpp — TEST INFRASTRUCTURE ONLY: a dictionary-faithful C++ restatement of TPSet<string?>
 // (MergeSharp/MergeSharp/CRDTs/2P-Set.cs), of TPSetMsg.Encode / Decode (:40-52) and of KeySpaceManager's
-// CreateNewKVPair / OnNext (BFT-CRDT/CRDTManagers/KeySpaceManager.cs:121-178): the CPU counterpart of csrc/tpset.hip,
-// the one-thread baseline of host/bench_keyspace.cpp and the checker of host/kat_keyspace.cpp.
+// CreateNewKVPair / OnNext (BFT-CRDT/CRDTManagers/KeySpaceManager.cs:121-178): the CPU counterpart of csrc/tpset.hip
+// (with tpset_encode.hip) and csrc/keyspace.hip, the one-thread baseline of host/bench_keyspace.cpp and the checker
+// of host/kat_keyspace.cpp.
 // A HashSet that nothing is removed from enumerates in first-insertion order: a vector plus an index stands for it.
 // tests/tpset_ref.py is the same restatement in Python; tests/test_tpset.py holds the two to the same bytes.
 #pragma once

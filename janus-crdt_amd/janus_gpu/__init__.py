@@ -1236,7 +1236,7 @@ def _pack_strings(items):
 
 
 class TPSet:
-    """One TPSet<string?> on the device (jg_tpset_*, csrc/tpset.hip): the replicated key-space set.  Strings are
+    """One TPSet<string?> on the device (jg_tpset_*, csrc/tpset.hip, tpset_encode.hip): the replicated key-space set.  Strings are
     bytes (UTF-8), None is the null element."""
 
     def __init__(self, ctx: Context, cap_strings: int, cap_bytes: int):

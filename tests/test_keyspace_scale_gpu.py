@@ -3,11 +3,12 @@ hash, against its restatement (tests/tpset_ref.py KeySpaceRef).  Every compariso
 with test_keyspace_gpu.same(): the journal in order, lookup of every known key and of absent probes, the set's sizes,
 lookup_all with ordinals and the encoded bytes.
 
-What each test is the first in the suite to run in csrc/tpset.hip:
+What each test is the first in the suite to run in csrc/keyspace.hip (excl_scan and its kernels: csrc/tpset.hip,
+csrc/block_scan.hpp; dict_find, claim_slot and find_slot: csrc/tpset_dict.hpp):
   test_scale_scenario[255 | 256 | 257]   k_ks_parse / _find / _win / _commit / _lookup / _journal with a last workgroup
       that is one lane short, full, and a second workgroup of one lane (the `i >= I.n` guards; blocks_for > 1);
-      items_layout's `while (slots < 2 * n)` past its 64 slots; a key's entries in different workgroups, so that
-      k_ks_find's atomicMin and the representative compare decide between lanes that share no workgroup.
+      items_layout's `pow2_at_least(2 * n, 64)` past its 64 slots; a key's entries in different workgroups, so that
+      k_ks_find's atomicMin and claim_slot's representative compare decide between lanes that share no workgroup.
   test_scale_scenario[8191 | 8192 | 8193] excl_scan's `n <= 4 * kScanTile` from both sides: at 8193 dict_insert's two
       scans take k_scan_sum / k_scan_apply, and k_ks_commit's bases `n_keys + oa[i]`, `jn + oj[i]` cross scan tiles.
   test_scale_scenario[10241]             a last scan tile that holds one item.
@@ -20,11 +21,12 @@ What each test is the first in the suite to run in csrc/tpset.hip:
       rejection branch with a non-zero *n_new after 150 applied messages.
   test_exactly_full                      dict_insert's `<= cap + 1` with equality on the journal side (8 keys + null).
   test_one_too_many_in_the_middle_message, test_create_keys_past_capacity
-      JG_ESTATE through jg_keyspace_receive's `rc != JG_OK` branch with rc != JG_EINVAL, and through
-      jg_keyspace_create_keys' `rc != JG_OK` branch; the watermark and n_new after it.
+      JG_ESTATE through jg_keyspace_receive's `catch (const jg::Error&)` with a code other than JG_EINVAL, and out of
+      tpset_apply_ops through jg_keyspace_create_keys' guard; the watermark and n_new after it.
   test_scale_and_random_parity_with_hash_collisions
-      dict_find's, k_ks_find's and k_ks_win's `key == key && klen == klen && same_bytes` with the first conjunct
-      true for a sixteenth of all pairs: prefix families (k, k1, k10) make klen decide, p...a / p...b the last byte.
+      dict_find's and SameKey's (k_ks_find through claim_slot, k_ks_win through find_slot) `key == key && klen == klen
+      && same_bytes` with the first conjunct true for a sixteenth of all pairs: prefix families (k, k1, k10) make
+      klen decide, p...a / p...b the last byte.
 Mutants that could index out of bounds are not run on a device; from the code: a wrong scan base in k_scan_apply
 shifts every `oa[i]` / `oj[i]` of a later tile, so dictionary ids and journal slots collide and same()'s journal and
 lookup compares fail at n >= 8193; dropping `D.klen[d] == klen` makes lookup(b"k") find k1's entry whenever the

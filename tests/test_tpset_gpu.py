@@ -1,6 +1,8 @@
-"""GPU: the device key-space set (jg_tpset_*, csrc/tpset.hip) against the restatement of TPSet<string?> and of
-its wire codec (tests/tpset_ref.py): known answers, random parity, the parallel scanner at its tile edges, bad
-messages among many, the accepted non-flat forms, partial merges, first-insertion order, capacity."""
+"""GPU: the device key-space set (jg_tpset_*: csrc/tpset.hip, its scanner csrc/tpset_scan.hpp, its wire form
+csrc/tpset_wire.hpp, its scans csrc/block_scan.hpp, its encoder csrc/tpset_encode.hip) against the restatement of
+TPSet<string?> and of its wire codec (tests/tpset_ref.py): known answers, random parity, the parallel scanner at its
+tile edges, bad messages among many, the accepted non-flat forms, partial merges, first-insertion order, capacity, and
+the block scan, the count scan and the call-wide table at the sizes where they take another path."""
 import os
 import subprocess
 import sys
@@ -378,6 +380,130 @@ def test_capacity(ctx):
         ref.apply_ops([(1, b"cc"), (2, b"cc"), (2, b"cc")])
         same(s, ref)
         assert s.size() == (3, 1, 10)
+
+
+# ---- the shared block scan, count scan and call-wide table at their edges ---------------------------------------
+@pytest.mark.parametrize("tiles", [255, 256, 257, 513])
+def test_one_flat_message_of_many_tiles(ctx, tiles):
+    """One flat message of exactly `tiles` scanner tiles: k_tile_carry's 256 lanes each fold a run of 1 tile (one lane
+    idle at 255), 1, 2 (lanes past 129 idle at 257) and 3 tiles; k_mark and k_emit run on full tiles; and the tens of
+    thousands of candidates, most of them duplicates, cross many tiles of the count scan."""
+    with jg.TPSet(ctx, 32768, 1 << 20) as s:
+        T = int(s.stats().tile_bytes)
+        assert T == 4096
+        head, mid, tail = b'{"addSet":[', b'],"removeSet":[', b"]}"
+        k = (tiles * T - len(head + mid + tail) - 8) // 8  # elements of 8 wire bytes: "xxxxx" and a comma
+        n_rem = k // 9
+        elems = [b"%05x" % ((i * 7919) % 20011) for i in range(k)]
+        add, rem = elems[n_rem:] + [None], elems[:n_rem][::-1]
+        arr = lambda items: b",".join(b"null" if x is None else b'"' + x + b'"' for x in items)
+        body = head + arr(add) + mid + arr(rem)
+        m = body + b" " * (tiles * T - 3 - len(body) - len(tail)) + tail
+        assert (len(m) + T - 1) // T == tiles and len(m) % T == T - 3
+        ref = R.TPSetRef()
+        ref.merge(add, rem)
+        assert len(ref.add_set) > 15000 and len(ref.rem_set) > 10000
+        s.merge_json([m])
+        st = s.stats()
+        assert (st.msgs_parallel, st.msgs_serial, st.strings_seen) == (1, 0, len(add) + len(rem))
+        same(s, ref)
+
+
+@pytest.fixture(scope="module")
+def ops_set(ctx):
+    """A set the apply_ops cases below leave behind, and its restatement (encoded by the lookup case)."""
+    s, ref = jg.TPSet(ctx, 256, 4096), R.TPSetRef()
+    seed = [(1, b"seed"), (2, b"seed"), (1, b"kept")]
+    assert s.apply_ops(seed) == ref.apply_ops(seed)
+    yield s, ref
+    s.close()
+
+
+@pytest.mark.parametrize("n", [8192, 8193])
+def test_apply_ops_across_the_scan_threshold(ops_set, n):
+    """n ops in one call, the count scan's one-block limit and one past it (k_ops_remove, k_cand_win's bools and the
+    four scans of the winners on either path): Adds and Removes over 60 strings and the null element, so nearly every
+    op is a duplicate; each string's first Remove comes before its first Add for a third of them and after it for the
+    rest, and the null element has both."""
+    s, ref = ops_set
+    rng = np.random.default_rng(n)
+    names = [b"op%d/%d" % (n, i) for i in range(60)] + [None]
+    ops = [(2, None), (2, names[0]), (2, names[3])]
+    ops += [(int(rng.integers(1, 3)) if i % 3 else 2, x) for i, x in enumerate(names)]
+    while len(ops) < n - 2:
+        ops.append((int(rng.integers(1, 3)), names[int(rng.integers(0, len(names)))]))
+    ops += [(1, names[1]), (2, names[1])]
+    assert len(ops) == n
+    exp = ref.apply_ops(ops)
+    assert exp[:3] == [False] * 3 and 30 < sum(exp[i] for i, (op, _) in enumerate(ops) if op == 2) <= 61
+    assert s.apply_ops(ops) == exp
+    same(s, ref)
+
+
+@pytest.mark.parametrize("m", [8192, 8193])
+def test_lookup_all_from_an_odd_ordinal(ctx, ops_set, m):
+    """LookupAll from ordinal 7 with m entries remaining, the count scan's one-block limit and one past it, with
+    ordinals; every fifth entry removed, the null element among them.  The encoder's scan over these more than 8192
+    entries takes the three-launch path, and over ops_set's few entries the one-block path."""
+    items = [b"it%05d" % i for i in range(7 + m)]
+    items[4003] = None
+    ref = R.TPSetRef()
+    ref.merge(items, items[3::5] + [b"never added"])
+    with jg.TPSet(ctx, 16384, 1 << 18) as s:
+        s.merge_json([ref.encode()])
+        assert s.size()[0] == 7 + m
+        for f in (7, 0, 7 + m - 1, 7 + m, 7 + m + 5):
+            assert s.lookup_all(f, with_ords=True) == ref.lookup_all(f, with_ords=True)
+        same(s, ref)
+    small, small_ref = ops_set
+    same(small, small_ref)
+
+
+def call_wide_table_families(ctx):
+    """300 strings in 5 families (a prefix, then x..x of 0 to 29 bytes, then a or b): within a family the length or the
+    last byte alone tells two strings apart.  One merge of three messages holds every string three times and removes
+    some before their second occurrence (more than 1100 candidates in one call-wide table, past one workgroup), then
+    700 ops over the same strings and 60 new ones; mode 0 and mode 1 keep the same set."""
+    rng = np.random.default_rng(300)
+    fam = [p + b"x" * k + e for p in (b"", b"p", b"pp", b"q/", "é".encode()) for k in range(30) for e in (b"a", b"b")]
+    assert len(set(fam)) == 300
+    thrice = [fam[i] for i in rng.permutation(np.repeat(np.arange(300), 3))]
+    msgs = [wire_msg(rng, thrice[i::3] + [None], [thrice[j] for j in rng.integers(0, 900, 80)], ws=bool(i)) for i in range(3)]
+    more = fam + [b"pxxz%d" % i for i in range(60)] + [None]
+    ops = [(int(rng.integers(1, 3)), more[int(i)]) for i in rng.integers(0, len(more), 700)]
+    ref = R.TPSetRef()
+    sets = [jg.TPSet(ctx, 512, 1 << 14), jg.TPSet(ctx, 512, 1 << 14)]
+    try:
+        assert ref.merge_json(msgs) == (None, False)
+        exp = ref.apply_ops(ops)
+        for mode, s in enumerate(sets):
+            s.merge_json(msgs, mode=mode)
+            assert s.stats().strings_seen == 3 * 301 + 3 * 80
+            assert s.apply_ops(ops) == exp
+            assert s.contains(more) == [ref.contains(x) for x in more]
+            same(s, ref)
+        assert len(ref.add_set) > 320 and len(ref.rem_set) > 100
+    finally:
+        for s in sets:
+            s.close()
+
+
+def test_call_wide_table_past_one_workgroup(ctx):
+    call_wide_table_families(ctx)
+
+
+def test_call_wide_table_with_hash_collisions():
+    """The same against the test build's 4-bit string hash: the call-wide table's and the resident table's probes run
+    through long chains of other strings, many of them of the same family.  In a child process through JANUS_GPU_LIB."""
+    lib = ROOT / "janus-crdt_amd" / "lib" / "libjanusgpu_test.so"
+    assert lib.exists(), "the test build is made by __graft_entry__.build()"
+    code = ("import sys; sys.path[:0] = [%r, %r]\n"
+            "import janus_gpu as jg, test_tpset_gpu as t\n"
+            "assert 'libjanusgpu_test' in str(jg.LIB_PATH)\n"
+            "ctx = jg.Context(0)\nt.call_wide_table_families(ctx)\nctx.close()\nprint('FAMILIES OK')\n" % (str(ROOT / "janus-crdt_amd"), str(ROOT / "tests")))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=240, env=dict(os.environ, JANUS_GPU_LIB=str(lib)),
+                         cwd=str(ROOT / "tests"))
+    assert out.returncode == 0 and "FAMILIES OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 
 
 def test_bad_arguments(ctx):

@@ -386,9 +386,9 @@ def collision_scenario(ctx):
 
 
 def test_statuses_with_hash_collisions():
-    """The test build's string hash keeps 4 bits (-DJANUS_TEST_HOOKS; tpset_dict.hpp's str_key, which tpset.hip's inserts
-    and update.hip's lookups share): a lookup that hashed differently from the inserts would find no key, and every probe
-    chain is long.  In a child process through JANUS_GPU_LIB, as test_query_keys_gpu's."""
+    """The test build's string hash keeps 4 bits (-DJANUS_TEST_HOOKS; tpset_dict.hpp's str_key, which tpset.hip's and
+    keyspace.hip's inserts and update.hip's lookups share): a lookup that hashed differently from the inserts would find
+    no key, and every probe chain is long.  In a child process through JANUS_GPU_LIB, as test_query_keys_gpu's."""
     lib = ROOT / "janus-crdt_amd" / "lib" / "libjanusgpu_test.so"
     assert lib.exists(), "the test build is made by __graft_entry__.build()"
     code = ("import sys; sys.path[:0] = [%r, %r]\n"
