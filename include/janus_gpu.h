@@ -839,6 +839,51 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n,
                         jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim);
 
 /* ---------------------------------------------------------------------------------------------
+ * Client writes by key name that also ship their PN-Counter snapshots (csrc/update.hip, csrc/pnc_encode.hip) —
+ * additive to ABI v10.
+ * Both halves of SafeCRDT.Update (SafeCRDT.cs:39-62) for a batch: prospectiveState.Update(operationID, args), which is
+ * jg_node_update_keys, and syncMsg.message = prospectiveState.crdt.GetLastSynchronizedUpdate().Encode(), the bytes
+ * the client batcher hashes and submits.  Every argument jg_node_update_keys takes means here what it means there:
+ * the same statuses, refusals, outputs and all-or-nothing rule.  Added: snap (one byte per command; NULL = 1 for every
+ * command), snap_off (n + 1 entries, snap_off[0] = 0, always filled), out / cap (the snapshots' bytes and the room
+ * for them), sha (NULL, or n x 32 bytes).
+ *   Snapshot.  Command i's snapshot is out[snap_off[i], snap_off[i+1]): GetLastSynchronizedUpdate().Encode()
+ *              (PNCounters.cs:115-118, 46-49) of the key's row right after command i, i.e. the row before the call plus
+ *              every applied PN-Counter command j <= i of the batch on the same row (whatever snap[j] says), wrapping at
+ *              the store's width.  The bytes are exactly jg_pnc_apply_ops_encode's for the same ops on the same row;
+ *              sha + 32 i is their SHA-256 (ComputeDigest's first level) when sha is given.
+ *   Who gets one.  Command i, iff it is an applied PN-Counter command (status JG_U_OK, kind 0) and
+ *              snap[i] == 1: a safe update, which the batcher ships individually (SafeCRDTManager.cs:178-181); or
+ *              snap[i] == 2 and no later command j > i of the call with snap[j] == 2 is an applied PN-Counter command on
+ *                            the same row: the batcher's compaction, appearedObjects[np.uid] = np (:179, 186-187), which
+ *                            keeps only the latest non-safe state of an object.  The survivors are decided on the device
+ *                            from the resolved rows (the host never learns which key strings name one object).  A call
+ *                            is ONE batcher batch for this rule: a caller whose batcher flushes mid-batch makes one call
+ *                            per flush.
+ *              snap[i] == 0: none.  Every command without a snapshot (snap 0, a 2 that did not survive, any failed
+ *              status, every OR-Set command) has snap_off[i+1] == snap_off[i] and 32 zero bytes of sha.
+ *   LIMIT: OR-Set commands are applied exactly as jg_node_update_keys applies them and get no bytes here.  Their
+ *              snapshots stay where they are: jg_orset_encode_json at the add_lim / rem_lim this call returns, with the
+ *              caller's rounds around a Clear.
+ * JG_EINVAL in addition to jg_node_update_keys' list, every output and both stores untouched: snap_off NULL; a snap[i]
+ * above 2; out NULL while the batch could ship a snapshot, which is decided from the arguments alone: a command with
+ * arg_flag 3 whose snap is not 0 (or snap NULL).
+ * JG_ESTATE: snap_off[n] > cap.  snap_off is filled and NOTHING is applied (the OR-Set commands, the element table and
+ * the names log included; every other output untouched): the PN-Counter length pass and this check run before the
+ * OR-Set side writes anything, and the OR-Set side, which can still refuse, runs before any PN-Counter cell is written.
+ * The caller calls again with a larger out.
+ * A node without a PN-Counter store, and a batch whose commands all fail, succeed with every snap_off entry 0.
+ * n == 0 returns JG_OK with snap_off[0] = 0. */
+int jg_node_update_keys_encode(jg_node* node, jg_keyspace* ks, uint64_t n,
+                               const uint64_t* key_off, const uint8_t* key_bytes,
+                               const uint8_t* op, const uint8_t* arg_flag, const int64_t* amount,
+                               const uint64_t* elem_off, const uint8_t* elem_bytes,
+                               const uint64_t* tag_lo, const uint64_t* tag_hi, uint32_t col, const uint8_t* snap,
+                               uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem,
+                               jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim,
+                               uint64_t* snap_off, uint8_t* out, uint64_t cap, uint8_t* sha);
+
+/* ---------------------------------------------------------------------------------------------
  * Synthetic workloads (bench / size-independent parity): device-side counter-based generators,
  * defined in DESIGN.md §Synthetic inputs and mirrored on the host by the test oracle.
  * ------------------------------------------------------------------------------------------- */

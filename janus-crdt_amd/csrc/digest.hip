@@ -361,11 +361,11 @@ void run_digests(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, con
 namespace jg {
 // SHA-256 of n payloads already in device memory (d_bytes at d_off[i]..d_off[i+1]) into host `out` (n * 32 digest
 // bytes), queued on ctx->stream: the caller's next sync covers it.  The encoders hash what they just wrote.
-void sha256_device(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* out) {
+void sha256_device(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* out, const uint8_t* d_null) {
     if (n == 0) return;
     auto* D = static_cast<uint4*>(jg::scratch(ctx, ctx->scratch3, n * 32 + 256));
     hipStream_t st = ctx->stream;
-    k_sha_msgs<false><<<jg::blocks_for(n), kBlock, 0, st>>>(d_bytes, d_off, nullptr, n, D);
+    k_sha_msgs<false><<<jg::blocks_for(n), kBlock, 0, st>>>(d_bytes, d_off, d_null, n, D);
     k_bswap_words<<<std::min<uint64_t>(jg::blocks_for(n * 8), 4096), kBlock, 0, st>>>(reinterpret_cast<uint32_t*>(D), n * 8);
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemcpyAsync(out, D, n * 32, hipMemcpyDeviceToHost, st));

@@ -373,7 +373,38 @@ int pnc_node_finish(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const 
 int pnc_node_prefix(jg_pnc* p, const uint8_t* bytes, const uint64_t* off, const uint32_t* rows, uint64_t n, uint64_t* bad, std::string* why);
 void pnc_node_undo(jg_pnc* p, const uint32_t* rows);
 // SHA-256 of n device-resident payloads into host out (n * 32 bytes), queued on ctx->stream (digest.hip)
-void sha256_device(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* out);  // a node wave abandoned after its chunks' (fused) pass A
+// d_null (or NULL): payloads whose flag is set hash to 32 zero bytes
+void sha256_device(jg_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* out, const uint8_t* d_null = nullptr);
+// pnc_encode.hip, for update.hip (jg_node_update_keys_encode): the snapshots SafeCRDT.Update ships for a
+// batch resolved on the device, in two steps with the caller's OR-Set side between them.  The caller holds the
+// context's lock and owns the arrays (ctx->scratch_u: they outlive the OR-Set side, which uses the other three).
+struct PncSnap {
+    // in, one entry per command, in batch order
+    const uint32_t* row;      // the command's row; the store's n_keys for a command that applies no PN-Counter op
+    const long long* amount;  // its amount (0 for those)
+    const uint8_t* is_n;      // 0 = Increment | 1 = Decrement
+    const uint8_t* snap;      // 0 none | 1 this command's | 2 the row's latest of the 2s (NULL: 1 everywhere)
+    // out
+    uint8_t* none;                 // [n] 1: the command ships no snapshot
+    unsigned long long* snap_off;  // [n + 1] the commands' byte offsets
+    // the encode list: the m commands that ship one, in batch order
+    uint32_t* erow;                // [n]
+    long long *edp, *edn;          // [n] the row's rewind to the state right after the command (k_encode subtracts it)
+    unsigned long long* eoff;      // [n + 1] the list's byte offsets
+    template <class L> void carve(L& l, uint64_t n) {
+        l.add(none, n), l.add(snap_off, n + 1), l.add(erow, n), l.add(edp, n), l.add(edn, n), l.add(eoff, n + 1);
+    }
+};
+// Step 1 reads only: per-row prefixes, the survivors of snap == 2, the encode list and its length pass.  Returns with
+// m (the list's length) and h_snap_off [n + 1] on the host: two waits on the stream (m sizes the length pass's grid),
+// which also cover what the caller queued before it.
+// Step 2 queues the write pass into ctx->scratch2, the hashes (sha: n x 32 host bytes or NULL) and the copy to `out`;
+// the caller queues the adds behind it and syncs.
+// ev (or NULL; JANUS_TRACE_UPDATE): five events of the caller's, recorded behind the prefixes, survivors and list [0] and
+// the length pass with the offsets [1] (step 1), the write pass [2], the hashes [3] and the copy of the bytes [4] (step 2).
+void pnc_snap_plan_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint32_t col, uint64_t* m, uint64_t* h_snap_off, hipEvent_t* ev = nullptr);
+void pnc_snap_write_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint64_t m, uint64_t bytes, uint32_t col, uint8_t* out, uint8_t* sha,
+                           hipEvent_t* ev = nullptr);
 // orset_wire.hip (OR-Set):
 void orset_node_begin(jg_orset* s, uint8_t* bytes, uint64_t* off, uint32_t* mset, uint64_t n, uint64_t nbytes, uint32_t max_set);
 void orset_node_parse(jg_orset* s, uint64_t m0, uint64_t m1);

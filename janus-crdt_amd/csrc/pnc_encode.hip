@@ -234,12 +234,10 @@ void launch_apply_ops(jg_pnc* p, const DevOps& d, uint64_t n, uint32_t col) {
 // Host: off [n + 1], out [cap] (NULL: the offsets only, a size query), sha [n x 32] or NULL.
 struct Encode { const uint32_t* rows; const long long *dp, *dn; unsigned long long *len, *doff; uint64_t* off; uint8_t* out; uint64_t cap; uint8_t* sha; };
 
-// The two-pass encode: lengths -> offsets on the host -> cap check (`cap_note`: what fn's error adds) -> bytes
-// (ctx->scratch2), with their hashes if asked, to the host.  n1 = cub_count(n + 1), `tmp` the scan's workspace.  `ops`
-// (or NULL) are applied behind the write pass and in front of the hashes and the copy: both passes read the rows
-// before the adds land.
+// The length pass: each entry's byte length, then the n + 1 offsets of an exclusive scan (e.doff, on the device).
+// n1 = cub_count(n + 1), `tmp` the scan's workspace.
 template <class Tmp>
-void encode_two_pass(jg_pnc* p, uint64_t n, int n1, uint32_t col, const Encode& e, Tmp&& tmp, const char* fn, const char* cap_note, const DevOps* ops) {
+void encode_lengths(jg_pnc* p, uint64_t n, int n1, uint32_t col, const Encode& e, Tmp&& tmp) {
     jg_ctx* ctx = p->ctx;
     const Table t = table_of(p);
     jg::dispatch_eb(p->eb, [&](auto EB) {
@@ -248,15 +246,31 @@ void encode_two_pass(jg_pnc* p, uint64_t n, int n1, uint32_t col, const Encode& 
     JG_HIP(hipGetLastError());
     JG_HIP(hipMemsetAsync(e.len + n, 0, 8, ctx->stream));
     jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, e.len, e.doff, n1, ctx->stream); });
+}
+
+// The write pass at those offsets into dout (device): one wave per workgroup.
+void encode_write(jg_pnc* p, uint64_t n, uint32_t col, const Encode& e, uint8_t* dout) {
+    jg_ctx* ctx = p->ctx;
+    const Table t = table_of(p);
+    jg::dispatch_eb(p->eb, [&](auto EB) {
+        hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(blocks_for(n, kEncLanes)), dim3(kEncLanes), 0, ctx->stream, e.rows, n, t, p->ro_P(), p->ro_N(), e.doff, dout, col, e.dp, e.dn);
+    });
+    JG_HIP(hipGetLastError());
+}
+
+// The two-pass encode: lengths -> offsets on the host -> cap check (`cap_note`: what fn's error adds) -> bytes
+// (ctx->scratch2), with their hashes if asked, to the host.  `ops` (or NULL) are applied behind the write pass and in
+// front of the hashes and the copy: both passes read the rows before the adds land.
+template <class Tmp>
+void encode_two_pass(jg_pnc* p, uint64_t n, int n1, uint32_t col, const Encode& e, Tmp&& tmp, const char* fn, const char* cap_note, const DevOps* ops) {
+    jg_ctx* ctx = p->ctx;
+    encode_lengths(p, n, n1, col, e, tmp);
     JG_HIP(hipMemcpyAsync(e.off, e.doff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     JG_HIP(hipStreamSynchronize(ctx->stream));
     if (!e.out) return;  // size query
     JG_REQUIRE(e.off[n] <= e.cap, JG_ESTATE, "%s: %llu bytes exceed cap %llu%s", fn, (unsigned long long)e.off[n], (unsigned long long)e.cap, cap_note);
     auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, e.off[n] + 64));
-    jg::dispatch_eb(p->eb, [&](auto EB) {  // the write pass: one wave per workgroup
-        hipLaunchKernelGGL((k_encode<EB(), 1>), dim3(blocks_for(n, kEncLanes)), dim3(kEncLanes), 0, ctx->stream, e.rows, n, t, p->ro_P(), p->ro_N(), e.doff, dout, col, e.dp, e.dn);
-    });
-    JG_HIP(hipGetLastError());
+    encode_write(p, n, col, e, dout);
     if (ops) launch_apply_ops(p, *ops, n, col);
     if (e.sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(e.doff), n, e.sha);  // each state's SHA-256 (ComputeDigest's first level)
     JG_HIP(hipMemcpyAsync(e.out, dout, e.off[n], hipMemcpyDeviceToHost, ctx->stream));
@@ -310,15 +324,17 @@ void upload_ops(jg_ctx* ctx, const DevOps& d, uint64_t n, const uint32_t* key, c
 
 // Per key, each op's amounts (vals) and the sum of the amounts ahead of it in its key's run (sums): keys in op order,
 // or (REV) newest first -> stable sort on the row -> amounts -> exclusive scan by key.  Returns the sorted keys
-// (sort_keys: ctx->scratch3); vals, sums and seg are in sorted order.
+// (sort_keys: ctx->scratch3); vals, sums and seg are in sorted order.  n_rows: the rows the sort tells apart (the store's,
+// or one more where d.key marks an entry that addresses no row with the store's n_keys: those sort to the end).
 template <bool REV, class Tmp>
-const unsigned long long* key_amounts(jg_pnc* p, const DevOps& d, uint64_t n, unsigned long long* keys, PN2* vals, PN2* sums, uint32_t* seg, Tmp&& tmp) {
+const unsigned long long* key_amounts(jg_pnc* p, const DevOps& d, uint64_t n, uint64_t n_rows, unsigned long long* keys, PN2* vals, PN2* sums, uint32_t* seg,
+                                      Tmp&& tmp) {
     jg_ctx* ctx = p->ctx;
     const unsigned g = blocks_for(n);
     const int n_i = jg::cub_count(n, "ops");
     hipLaunchKernelGGL(k_make_keys<REV>, dim3(g), dim3(kBlock), 0, ctx->stream, d.key, n, keys);
     JG_HIP(hipGetLastError());
-    const unsigned long long* sorted = sort_keys(ctx, keys, n, p->n_keys);
+    const unsigned long long* sorted = sort_keys(ctx, keys, n, n_rows);
     hipLaunchKernelGGL(k_rewind_vals, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, d.delta, d.is_n, p->eb, vals, seg);
     JG_HIP(hipGetLastError());
     jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
@@ -327,7 +343,145 @@ const unsigned long long* key_amounts(jg_pnc* p, const DevOps& d, uint64_t n, un
     return sorted;
 }
 
+// ---- the snapshots of a batch resolved on the device (jg_node_update_keys_encode) -----------------
+// The batch is sorted with the commands that apply no PN-Counter op under row `none_row` (the store's n_keys), behind
+// every real row.  Sorted position s heads its row's run when its row differs from the one before it; an inclusive
+// max-scan of (head ? s : 0) then gives every position its run's head.
+__global__ void k_snap_heads(const uint32_t* __restrict__ seg, uint64_t n, uint32_t* __restrict__ head) {
+    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s < n) head[s] = s && seg[s] != seg[s - 1] ? (uint32_t)s : 0u;
+}
+
+// the batcher's compaction (SafeCRDTManager.cs:179, 186-187): per run, the latest position with snap == 2, + 1
+__global__ void k_snap_latest(const unsigned long long* __restrict__ sorted, uint64_t n, const uint32_t* __restrict__ seg, uint32_t none_row,
+                              const uint8_t* __restrict__ snap, const uint32_t* __restrict__ head, uint32_t* __restrict__ latest) {
+    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n || seg[s] == none_row) return;
+    if (snap[(uint32_t)sorted[s]] == 2) atomicMax(&latest[head[s]], (uint32_t)s + 1);
+}
+
+// command i ships a snapshot: an applied PN-Counter command with snap 1, or with snap 2 and no later 2 on its row.
+// none[i] = it does not (the hashes' zero flag), take[i] = it does (the flags the positions are scanned from).
+__global__ void k_snap_take(const unsigned long long* __restrict__ sorted, uint64_t n, const uint32_t* __restrict__ seg, uint32_t none_row,
+                            const uint8_t* __restrict__ snap, const uint32_t* __restrict__ head, const uint32_t* __restrict__ latest,
+                            uint8_t* __restrict__ none, uint32_t* __restrict__ take) {
+    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t i = (uint32_t)sorted[s];
+    const uint32_t sn = snap ? snap[i] : 1;
+    const bool t = seg[s] != none_row && (sn == 1 || (sn == 2 && latest[head[s]] == (uint32_t)s + 1));
+    none[i] = !t;
+    take[i] = t;
+}
+
+// the encode list: the taken commands' rows and rewinds at their positions (pos = exclusive count of taken commands)
+__global__ void k_snap_list(const uint32_t* __restrict__ take, const uint32_t* __restrict__ pos, uint64_t n, const uint32_t* __restrict__ row,
+                            const long long* __restrict__ dp, const long long* __restrict__ dn, uint32_t* __restrict__ erow,
+                            long long* __restrict__ edp, long long* __restrict__ edn) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || !take[i]) return;
+    const uint32_t j = pos[i];
+    erow[j] = row[i], edp[j] = dp[i], edn[j] = dn[i];
+}
+
+// the list's offsets back by command index: command i's bytes begin where list entry pos[i] begins (i = n: the total)
+__global__ void k_snap_offsets(const uint32_t* __restrict__ pos, uint64_t n, const unsigned long long* __restrict__ eoff,
+                               unsigned long long* __restrict__ snap_off) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i <= n) snap_off[i] = eoff[pos[i]];
+}
+
 }  // namespace
+
+namespace jg {
+
+void pnc_snap_plan_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint32_t col, uint64_t* m_out, uint64_t* h_snap_off, hipEvent_t* ev) {
+    jg_ctx* ctx = p->ctx;
+    const auto stamp = [&](int k) {
+        if (ev) JG_HIP(hipEventRecord(ev[k], ctx->stream));
+    };
+    JG_REQUIRE(col < p->R, JG_EINVAL, "pnc_snap_plan: column %u past the store's %u replicas", col, p->R);
+    JG_REQUIRE(p->n_keys < 0xFFFFFFFFull, JG_EINVAL, "pnc_snap_plan: the store's %llu rows leave no row id free", (unsigned long long)p->n_keys);
+    ensure_table(p);
+    const uint32_t none_row = (uint32_t)p->n_keys;
+    const int n_i = jg::cub_count(n, "commands"), n1_i = jg::cub_count(n + 1, "commands");
+    const size_t t_all = std::max({scans_temp_bytes<unsigned long long>(ctx, n_i, n1_i), scans_temp_bytes<uint32_t>(ctx, n_i, n1_i),
+                                   jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+                                       return hipcub::DeviceScan::InclusiveScan(temp, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, hipcub::Max(), n_i,
+                                                                                ctx->stream);
+                                   })});
+    // everything that does not outlive this step in ctx->scratch; the sort in scratch3
+    uint32_t *seg, *mark, *head, *latest, *take, *pos;
+    long long *ddp, *ddn;
+    unsigned long long *keys, *len;
+    PN2 *vals, *excl;
+    uint8_t* dtmp;
+    jg::Layout A;
+    A.add(keys, n), A.add(vals, n), A.add(excl, n), A.add(seg, n), A.add(mark, n), A.add(head, n), A.add(latest, n), A.add(take, n + 1), A.add(pos, n + 1);
+    A.add(ddp, n), A.add(ddn, n), A.add(len, n + 1), A.add(dtmp, t_all + 256);
+    A.bind(jg::scratch(ctx, ctx->scratch, A.bytes()));
+    const auto tmp = jg::cub_in(dtmp, t_all);
+    const unsigned g = blocks_for(n);
+    // each command's amounts up to and including it on its row, in batch order (the commands without a row add 0 to a
+    // run of their own)
+    const DevOps d{const_cast<uint32_t*>(s.row), const_cast<long long*>(s.amount), const_cast<uint8_t*>(s.is_n)};
+    const unsigned long long* sorted = key_amounts<false>(p, d, n, p->n_keys + 1, keys, vals, excl, seg, tmp);
+    hipLaunchKernelGGL(k_prefix_scatter, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, vals, excl, ddp, ddn);
+    // the survivors of snap == 2, then who ships a snapshot
+    hipLaunchKernelGGL(k_snap_heads, dim3(g), dim3(kBlock), 0, ctx->stream, seg, n, mark);
+    JG_HIP(hipGetLastError());
+    jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::InclusiveScan(temp, bytes, mark, head, hipcub::Max(), n_i, ctx->stream); });
+    if (s.snap) {
+        JG_HIP(hipMemsetAsync(latest, 0, n * 4, ctx->stream));
+        hipLaunchKernelGGL(k_snap_latest, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, seg, none_row, s.snap, head, latest);
+    }
+    hipLaunchKernelGGL(k_snap_take, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, seg, none_row, s.snap, head, latest, s.none, take);
+    JG_HIP(hipGetLastError());
+    JG_HIP(hipMemsetAsync(take + n, 0, 4, ctx->stream));
+    jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, take, pos, n1_i, ctx->stream); });
+    hipLaunchKernelGGL(k_snap_list, dim3(g), dim3(kBlock), 0, ctx->stream, take, pos, n, s.row, ddp, ddn, s.erow, s.edp, s.edn);
+    JG_HIP(hipGetLastError());
+    stamp(0);
+    jg::pin_get(ctx, 0, pos + n, 4);
+    jg::pin_sync(ctx);
+    const uint64_t m = *static_cast<const uint32_t*>(jg::pin_at(ctx, 0));
+    *m_out = m;
+    if (m == 0) {
+        JG_HIP(hipMemsetAsync(s.snap_off, 0, (n + 1) * 8, ctx->stream));
+        std::fill(h_snap_off, h_snap_off + n + 1, 0);
+        stamp(1);
+        return;
+    }
+    // the list's lengths and offsets (nothing is applied yet), and the offsets by command index to the host
+    encode_lengths(p, m, jg::cub_count(m + 1, "commands"), col, Encode{s.erow, s.edp, s.edn, len, s.eoff, nullptr, nullptr, 0, nullptr}, tmp);
+    hipLaunchKernelGGL(k_snap_offsets, dim3(blocks_for(n + 1)), dim3(kBlock), 0, ctx->stream, pos, n, s.eoff, s.snap_off);
+    JG_HIP(hipGetLastError());
+    stamp(1);
+    JG_HIP(hipMemcpyAsync(h_snap_off, s.snap_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    JG_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+void pnc_snap_write_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint64_t m, uint64_t bytes, uint32_t col, uint8_t* out, uint8_t* sha,
+                           hipEvent_t* ev) {
+    jg_ctx* ctx = p->ctx;
+    const auto stamp = [&](int k) {
+        if (ev) JG_HIP(hipEventRecord(ev[k], ctx->stream));
+    };
+    if (m == 0) {
+        if (sha) std::memset(sha, 0, n * 32);
+        for (int k = 2; k < 5; ++k) stamp(k);
+        return;
+    }
+    auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, bytes + 64));
+    encode_write(p, m, col, Encode{s.erow, s.edp, s.edn, nullptr, s.eoff, nullptr, nullptr, 0, nullptr}, dout);
+    stamp(2);
+    if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(s.snap_off), n, sha, s.none);
+    stamp(3);
+    JG_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    stamp(4);
+}
+
+}  // namespace jg
 
 extern "C" {
 
@@ -375,7 +529,7 @@ int jg_pnc_apply_ops_rewind(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         const unsigned g = blocks_for(n);
         hipLaunchKernelGGL(k_flags_u32, dim3(g), dim3(kBlock), 0, ctx->stream, dneed, n, seg);
         jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, seg, dpos, n_i, ctx->stream); });
-        const unsigned long long* sorted = key_amounts<true>(p, d, n, keys, vals, later, seg, tmp);
+        const unsigned long long* sorted = key_amounts<true>(p, d, n, p->n_keys, keys, vals, later, seg, tmp);
         hipLaunchKernelGGL(k_rewind_scatter, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, later, dneed, dpos, ddp, ddn);
         JG_HIP(hipGetLastError());
         JG_HIP(hipMemcpyAsync(dp, ddp, n_need * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -413,7 +567,7 @@ int jg_pnc_apply_ops_encode(jg_pnc* p, uint64_t n_ops, const uint32_t* key, uint
         const auto tmp = jg::cub_in(dtmp, t_both);
         upload_ops(ctx, d, n, key, delta, is_n);
         // each op's amounts up to and including it, per key (forward keys: a stable sort keeps op order per key)
-        const unsigned long long* sorted = key_amounts<false>(p, d, n, keys, vals, excl, seg, tmp);
+        const unsigned long long* sorted = key_amounts<false>(p, d, n, p->n_keys, keys, vals, excl, seg, tmp);
         hipLaunchKernelGGL(k_prefix_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, sorted, n, vals, excl, ddp, ddn);
         JG_HIP(hipGetLastError());
         // the snapshots from the rows as they stand (nothing applied yet), then the ops

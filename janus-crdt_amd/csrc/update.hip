@@ -1,4 +1,5 @@
-// update.hip — client writes by key name, resolved on the device: jg_node_update_keys.
+// update.hip — client writes by key name, resolved on the device: jg_node_update_keys, and the same
+// call shipping the PN-Counter snapshots SafeCRDT.Update sends next: jg_node_update_keys_encode.
 //
 // The reference's "i" / "d" / "a" / "r" / "c" commands (CRDTCommands/PNCounterCommand.cs:42-53, ORSetCommand.cs:43-61) go
 // KeySpaceManager.GetKVPair -> SafeCRDT.Update (SafeCRDT.cs:39-47) -> prospectiveState.Update(operationID, args) in
@@ -17,6 +18,12 @@
 //                skips the round trip; a batch without an OR-Set command launches nothing of it.
 //   adds         jg_pnc_apply_ops' wrapping atomic adds over the list (pnc.hip k_add_list), its length read from device
 //                memory: a fixed grid, no count on the host.  They cannot refuse once launched.
+//
+//   snapshots    (jg_node_update_keys_encode only) the resolve also writes (row | none, amount, P | N) per command index:
+//                batch order is what a per-command prefix needs, and the appended list has none across waves.
+//                pnc_encode.hip plans them (prefixes per row, the survivors of snap == 2, the encode list, its length
+//                pass) before the OR-Set side, so the size check refuses before anything is written, and writes them
+//                behind it and in front of the adds: both passes read the rows as they stood before the call.
 //
 // The resolve is a dependent chain of random lines: the kernel waits on memory, uses no LDS and few registers, so
 // occupancy is what hides the latency.  Nothing is published inside a launch: the kernel boundaries publish the list
@@ -42,6 +49,7 @@ struct UIn {  // the staged batch
     const ull* koff;
     const long long* amount;  // NULL: no command carries an integer
     const uint8_t *kbytes, *op, *flag;
+    const uint8_t* snap;  // _encode only, NULL: 1 for every command
 };
 struct UOut {
     uint8_t *status, *kind;
@@ -51,8 +59,14 @@ struct UOut {
     long long* pamt;
     uint8_t* pisn;
     ull* count;  // their number (zeroed before the launch)
+    // ORDERED only, one entry per command index: the row (none_row for a command that applies no PN-Counter op), the
+    // amount (0 for those), 0 = P | 1 = N
+    uint32_t* erow;
+    long long* eamt;
+    uint8_t* eisn;
 };
 
+template <bool ORDERED>
 __global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D, jg::DevUids U, uint64_t pnc_rows, bool has_orset, UIn in, uint64_t n,
                                                       UOut o) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -100,6 +114,7 @@ __global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D,
         o.kind[i] = kd;
         o.idx[i] = ix;
         if (o.guid) o.guid[i] = jg_guid{glo, ghi};
+        if constexpr (ORDERED) o.erow[i] = is_p ? row : (uint32_t)pnc_rows, o.eamt[i] = amt, o.eisn[i] = isn;
     }
     const ull sp = jg::wave_append(is_p, o.count);
     if (is_p) o.prow[sp] = row, o.pamt[sp] = amt, o.pisn[sp] = isn;
@@ -113,17 +128,27 @@ void check_offsets(const char* what, uint64_t n, const uint64_t* off) {
     JG_REQUIRE(off[n] < (1ull << 40), JG_EINVAL, "jg_node_update_keys: batch too large");
 }
 
-}  // namespace
+// what jg_node_update_keys_encode adds to jg_node_update_keys' arguments
+struct Enc {
+    const uint8_t* snap;
+    uint64_t* snap_off;
+    uint8_t* out;
+    uint64_t cap;
+    uint8_t* sha;
+};
 
-extern "C" {
-
-int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
-                        const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
-                        const uint64_t* tag_hi, uint32_t col, uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem,
-                        jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim) {
+// Both entry points (enc NULL: jg_node_update_keys, which launches and answers as it did before the other existed).
+int update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
+                const uint64_t* tag_hi, uint32_t col, uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem, jg_guid* guid,
+                uint64_t* add_lim, uint64_t* rem_lim, const Enc* enc) {
     return jg::guard([&] {
         auto lk_ = jg::lock(ks);  // calls on one context are serialised (shared scratch, stream)
-        if (n == 0) return;
+        JG_REQUIRE(!enc || enc->snap_off, JG_EINVAL, "jg_node_update_keys_encode: snap_off is NULL");
+        if (n == 0) {
+            if (enc) enc->snap_off[0] = 0;
+            return;
+        }
         // every refusal below is decided from the arguments: nothing has been copied or written yet
         JG_REQUIRE(node && ks && op && arg_flag && status && result, JG_EINVAL, "jg_node_update_keys: NULL argument");
         JG_REQUIRE(jg::node_ctx(node) == ks->ctx, JG_EINVAL, "jg_node_update_keys: the key space and the node belong to different contexts");
@@ -138,6 +163,15 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
             JG_REQUIRE(arg_flag[i] <= 3, JG_EINVAL, "jg_node_update_keys: arg_flag[%llu] = %u (0 none, 1 string, 2 null, 3 integer)", (ull)i,
                        arg_flag[i]);
             ++n_flag[arg_flag[i]];
+        }
+        if (enc) {  // a snapshot needs an applied PN-Counter command, which needs an integer: decided from the arguments
+            bool may_ship = false;
+            for (uint64_t i = 0; i < n; ++i) {
+                JG_REQUIRE(!enc->snap || enc->snap[i] <= 2, JG_EINVAL, "jg_node_update_keys_encode: snap[%llu] = %u (0 none, 1 this command's, 2 the latest)",
+                           (ull)i, enc->snap[i]);
+                may_ship |= arg_flag[i] == 3 && (!enc->snap || enc->snap[i] != 0);
+            }
+            JG_REQUIRE(!may_ship || enc->out, JG_EINVAL, "jg_node_update_keys_encode: a command may ship a snapshot and out is NULL");
         }
         JG_REQUIRE(n_flag[3] == 0 || amount, JG_EINVAL, "jg_node_update_keys: a command carries an integer and amount is NULL");
         JG_REQUIRE(n_flag[1] == 0 || (elem_off && elem_bytes), JG_EINVAL,
@@ -161,6 +195,8 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
         UOut o{};
         jg::Layout L;
         L.add(in.koff, n + 1, 8), L.add(in.amount, ints ? n : 0, 8), L.add(in.kbytes, kb, 8), L.add(in.op, n, 1), L.add(in.flag, n, 1);
+        const bool snaps = enc && enc->snap;
+        L.add(in.snap, snaps ? n : 0, 1);
         const size_t stage = L.skip(0, 8);
         std::vector<uint8_t> h(stage);
         L.bind(h.data());  // the host image first: the same offsets as on the device
@@ -169,19 +205,27 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
         if (kb) std::memcpy(const_cast<uint8_t*>(in.kbytes), key_bytes, kb);
         std::memcpy(const_cast<uint8_t*>(in.op), op, n);
         std::memcpy(const_cast<uint8_t*>(in.flag), arg_flag, n);
+        if (snaps) std::memcpy(const_cast<uint8_t*>(in.snap), enc->snap, n);
         // behind it (16 bytes on): count | guid | pamt | prow | idx | status | kind | pisn; idx, status and kind are one
         // stretch of 6 n bytes (one copy out)
         L.skip(16);
         L.add(o.count, 1, 8), L.add(o.guid, guid ? n : 0, 8), L.add(o.pamt, n, 8), L.add(o.prow, n, 4);
         L.add(o.idx, n, 4), L.add(o.status, n, 1), L.add(o.kind, n, 1), L.add(o.pisn, n, 1);
+        // _encode: the ops by command index and the snapshots' arrays, which outlive the OR-Set side like the rest
+        const bool plan = enc && nd.pnc;
+        jg::PncSnap sn{};
+        L.add(o.eamt, enc ? n : 0, 8), L.add(o.erow, enc ? n : 0, 4), L.add(o.eisn, enc ? n : 0, 1);
+        if (plan) sn.carve(L, n);
         auto* d = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch_u, L.bytes() + 64));
         L.bind(d);
         if (!ints) in.amount = nullptr;
+        if (!snaps) in.snap = nullptr;
+        sn.row = o.erow, sn.amount = o.eamt, sn.is_n = o.eisn, sn.snap = in.snap;
         if (!guid) o.guid = nullptr;
 
         // JANUS_TRACE_UPDATE (as JANUS_TRACE_QUERY): the upload, the launches and the copies out by hipEvents
         static const bool tr = std::getenv("JANUS_TRACE_UPDATE") != nullptr;
-        hipEvent_t ev[6] = {};
+        hipEvent_t ev[8] = {}, sev[5] = {};  // sev: the snapshot steps' own (pnc_snap_*_locked)
         auto stamp = [&](int k) {
             if (!tr) return;
             JG_HIP(hipEventCreate(&ev[k]));
@@ -191,7 +235,8 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
         JG_HIP(hipMemcpyAsync(d, h.data(), stage, hipMemcpyHostToDevice, ctx->stream));
         stamp(1);
         JG_HIP(hipMemsetAsync(o.count, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_u_resolve, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
+        const auto resolve = enc ? k_u_resolve<true> : k_u_resolve<false>;
+        hipLaunchKernelGGL(resolve, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
                            nd.pnc ? nd.pnc->n_keys : 0, nd.orset != nullptr, in, n, o);
         JG_HIP(hipGetLastError());
         stamp(2);
@@ -205,8 +250,27 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
         std::vector<uint64_t> al(add_lim ? n : 0, 0), rl(add_lim ? n : 0, 0);
         double host_ms = 0;
         uint64_t n_o = 0;
+        // _encode: the snapshots planned and sized before the OR-Set side writes anything.  A batch past `cap` is refused
+        // here with its offsets filled: nothing has been applied.
+        std::vector<uint64_t> hoff(enc ? n + 1 : 0, 0);
+        uint64_t n_snap = 0;
+        if (nd.orset) JG_HIP(hipMemcpyAsync(hres.data(), o.idx, n * 6, hipMemcpyDeviceToHost, ctx->stream));
+        if (plan) {
+            try {
+                if (tr)
+                    for (hipEvent_t& e : sev) JG_HIP(hipEventCreate(&e));
+                jg::pnc_snap_plan_locked(nd.pnc, sn, n, col, &n_snap, hoff.data(), tr ? sev : nullptr);
+            } catch (...) {
+                (void)hipStreamSynchronize(ctx->stream);  // the copy into hres above
+                throw;
+            }
+            if (hoff[n] > enc->cap) {
+                std::memcpy(enc->snap_off, hoff.data(), (n + 1) * 8);
+                jg::fail(JG_ESTATE, "jg_node_update_keys_encode: %llu bytes exceed cap %llu (nothing applied)", (ull)hoff[n], (ull)enc->cap);
+            }
+        }
+        stamp(6);
         if (nd.orset) {
-            JG_HIP(hipMemcpyAsync(hres.data(), o.idx, n * 6, hipMemcpyDeviceToHost, ctx->stream));
             JG_HIP(hipStreamSynchronize(ctx->stream));
             const double t0 = jg::now_us();
             std::vector<uint32_t> at;  // the OR-Set commands, in batch order
@@ -240,6 +304,9 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
             host_ms = (jg::now_us() - t0) * 1e-3;
         }
         stamp(3);
+        // the write pass reads the rows as they stand, the adds land behind it
+        if (plan) jg::pnc_snap_write_locked(nd.pnc, sn, n, n_snap, hoff[n], col, enc->out, enc->sha, tr ? sev : nullptr);
+        stamp(7);
         if (nd.pnc) jg::pnc_add_list_device(nd.pnc, o.prow, o.pamt, o.pisn, o.count, n, col);
         stamp(4);
         if (!nd.orset) JG_HIP(hipMemcpyAsync(hres.data(), o.idx, n * 6, hipMemcpyDeviceToHost, ctx->stream));
@@ -254,18 +321,56 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64
         if (idx) std::memcpy(idx, h_idx, n * 4);
         if (elem) std::memcpy(elem, el.data(), n * 4);
         if (add_lim) std::memcpy(add_lim, al.data(), n * 8), std::memcpy(rem_lim, rl.data(), n * 8);
+        if (enc) {
+            std::memcpy(enc->snap_off, hoff.data(), (n + 1) * 8);
+            if (!plan && enc->sha) std::memset(enc->sha, 0, n * 32);
+        }
         if (tr) {
             float up = 0, run = 0, add = 0, down = 0;
             JG_HIP(hipEventElapsedTime(&up, ev[0], ev[1]));
             JG_HIP(hipEventElapsedTime(&run, ev[1], ev[2]));
-            JG_HIP(hipEventElapsedTime(&add, ev[3], ev[4]));
+            JG_HIP(hipEventElapsedTime(&add, ev[7], ev[4]));
             JG_HIP(hipEventElapsedTime(&down, ev[4], ev[5]));
             std::fprintf(stderr, "update_keys(%llu commands, %llu bytes up, %llu bytes down): upload %.3f ms, resolve launch %.3f ms, "
                          "PN-Counter adds %.3f ms, copies out %.3f ms; OR-Set side (%llu commands, after a copy of 6 bytes per command) %.3f ms\n",
                          (ull)n, (ull)stage, (ull)(n * (6 + (guid ? 16 : 0))), up, run, add, down, (ull)n_o, host_ms);
+            if (plan) {  // the second step waits for the host in front of it (the list's length): that gap is its own
+                float pre = 0, len = 0, wr = 0, sha = 0, cp = 0;
+                JG_HIP(hipEventElapsedTime(&pre, ev[2], sev[0]));
+                JG_HIP(hipEventElapsedTime(&len, sev[0], sev[1]));
+                JG_HIP(hipEventElapsedTime(&wr, ev[3], sev[2]));
+                JG_HIP(hipEventElapsedTime(&sha, sev[2], sev[3]));
+                JG_HIP(hipEventElapsedTime(&cp, sev[3], sev[4]));
+                std::fprintf(stderr, "update_keys_encode(%llu snapshots, %llu bytes): prefixes, survivors and list %.3f ms, length pass and offsets "
+                             "(behind a host wait) %.3f ms, write pass %.3f ms, hashes %.3f ms, copy of the bytes %.3f ms\n", (ull)n_snap, (ull)hoff[n],
+                             pre, len, wr, sha, cp);
+                for (hipEvent_t e : sev) (void)hipEventDestroy(e);
+            }
             for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         }
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                        const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
+                        const uint64_t* tag_hi, uint32_t col, uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem,
+                        jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim) {
+    return update_keys(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, col, status, result, kind, idx, elem,
+                       guid, add_lim, rem_lim, nullptr);
+}
+
+int jg_node_update_keys_encode(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                               const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes,
+                               const uint64_t* tag_lo, const uint64_t* tag_hi, uint32_t col, const uint8_t* snap, uint8_t* status, uint8_t* result,
+                               uint8_t* kind, uint32_t* idx, uint32_t* elem, jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim, uint64_t* snap_off,
+                               uint8_t* out, uint64_t cap, uint8_t* sha) {
+    const Enc enc{snap, snap_off, out, cap, sha};
+    return update_keys(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, col, status, result, kind, idx, elem,
+                       guid, add_lim, rem_lim, &enc);
 }
 
 }  // extern "C"

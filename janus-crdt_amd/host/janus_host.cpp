@@ -809,8 +809,22 @@ std::vector<KeyAnswer> GpuStableStore::QueryKeys(GpuKeySpace& ks, const std::vec
 }
 
 std::vector<KeyUpdate> GpuStableStore::UpdateKeys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands) {
+    return update_keys(ks, commands, nullptr, nullptr);
+}
+
+std::vector<KeyUpdate> GpuStableStore::UpdateKeysEncode(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
+                                                        std::vector<KeyMessage>& messages) {
+    if (!snap.empty() && snap.size() != commands.size()) throw EngineError(JG_EINVAL, "UpdateKeysEncode: one snap entry per command");
+    return update_keys(ks, commands, &snap, &messages);
+}
+
+// Both: messages NULL = jg_node_update_keys, else jg_node_update_keys_encode (once more with room for every byte when
+// the first buffer was too small: nothing was applied).
+std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>* snap,
+                                                   std::vector<KeyMessage>* messages) {
     const size_t n = commands.size();
     std::vector<KeyUpdate> out(n);
+    if (messages) messages->assign(n, KeyMessage{});
     if (n == 0) return out;
     flush_registrations();  // CreateSafeCRDTs not yet sent: the node's uid table
     flush_names();          // names interned here that the engine's element table has not seen
@@ -832,9 +846,30 @@ std::vector<KeyUpdate> GpuStableStore::UpdateKeys(GpuKeySpace& ks, const std::ve
     if (elem_bytes.empty()) elem_bytes.push_back(0);
     std::vector<uint8_t> status(n), result(n), kind(n);
     std::vector<uint32_t> idx(n), elem(n);
-    check(jg_node_update_keys(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(), elem_off.data(),
-                              elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, status.data(), result.data(), kind.data(), idx.data(), elem.data(),
-                              nullptr, nullptr, nullptr));
+    if (!messages) {
+        check(jg_node_update_keys(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(), elem_off.data(),
+                                  elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, status.data(), result.data(), kind.data(), idx.data(),
+                                  elem.data(), nullptr, nullptr, nullptr));
+    } else {
+        std::vector<uint64_t> snap_off(n + 1, 0);
+        std::vector<uint8_t> bytes(std::max<size_t>(16, n * 512)), sha(n * 32);
+        const auto call = [&] {
+            return jg_node_update_keys_encode(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(),
+                                              elem_off.data(), elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, snap->empty() ? nullptr : snap->data(),
+                                              status.data(), result.data(), kind.data(), idx.data(), elem.data(), nullptr, nullptr, nullptr,
+                                              snap_off.data(), bytes.data(), bytes.size(), sha.data());
+        };
+        int rc = call();
+        if (rc == JG_ESTATE && snap_off[n] > bytes.size()) {
+            bytes.resize(snap_off[n]);
+            rc = call();
+        }
+        check(rc);
+        for (size_t i = 0; i < n; ++i) {
+            (*messages)[i].message.assign(reinterpret_cast<const char*>(bytes.data()) + snap_off[i], snap_off[i + 1] - snap_off[i]);
+            std::memcpy((*messages)[i].sha256.data(), sha.data() + 32 * i, 32);
+        }
+    }
     // The per-set tables.  A set's ids only grow, so the names this batch interned are ids names.size().. in the order of
     // their first Add; those issued before the set's last Clear are dead, as is every older id (the Clear path of
     // PrepareOps: elems emptied, indexed = the ids issued so far).  The engine's table knows the Clear already, so

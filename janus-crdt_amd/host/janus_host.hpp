@@ -165,6 +165,11 @@ struct KeyCommand {
     std::string elem;
     Guid tag;                         // ORSet.Add's Guid.NewGuid()
 };
+// What SafeCRDT.Update ships for one command of UpdateKeysEncode: empty where the command ships nothing.
+struct KeyMessage {
+    std::string message;                // syncMsg.message
+    std::array<uint8_t, 32> sha256{};   // its SHA-256 (zeros where there is none)
+};
 struct KeyUpdate {
     uint8_t status = 0;       // JG_U_*
     uint8_t result = 0;       // Update's bool; 0 for a failed command
@@ -289,6 +294,14 @@ class GpuStableStore {
     // tables, so a later SubmitClientUpdates / EncodeORSetStates on the same sets sees what the engine holds.
     // Statuses are reported, not thrown.
     std::vector<KeyUpdate> UpdateKeys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands);
+    // The mirror of SafeCRDT.Update for a batch (SafeCRDT.cs:39-62): what UpdateKeys does, and for every PN-Counter command
+    // that ships one, syncMsg.message = GetLastSynchronizedUpdate().Encode() of the key right after the command with its
+    // SHA-256, from the same call (jg_node_update_keys_encode).  snap[i]: 0 none, 1 this command's (a safe update), 2 the
+    // object's latest of the call's 2s (the batcher's appearedObjects); empty: 1 for every command.  One call is one
+    // batcher batch.  OR-Set commands are applied and get no message here (EncodeORSetStates).  SubmitClientUpdates is
+    // not switched over to it.
+    std::vector<KeyUpdate> UpdateKeysEncode(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
+                                            std::vector<KeyMessage>& messages);
     // GetLastSynchronizedUpdate().Encode() of PN-Counter keys, encoded on the device — the payload
     // SafeCRDT.Update ships after a client op (SafeCRDT.cs:49; batch producer).
     std::vector<std::string> EncodePNCStates(const std::vector<Guid>& uids);
@@ -414,6 +427,9 @@ class GpuStableStore {
     const KeyRef& ref(const Guid& uid, CrdtType want) const;
     void check(int rc) const;
     void flush_registrations();  // pending CreateSafeCRDT registrations -> jg_node_register + jg_pnc_intern
+    // UpdateKeys (messages NULL) and UpdateKeysEncode
+    std::vector<KeyUpdate> update_keys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>* snap,
+                                       std::vector<KeyMessage>* messages);
     // ApplyCommitted / ReceivedBlock: flatten the messages into the jg_commit arrays, one library call.
     std::vector<uint64_t> apply(const std::vector<const UpdateMessage*>& blocks, SafeUpdateTracker* tracker, bool block_mode);
     size_t index_blocks(const std::vector<const UpdateMessage*>& blocks);  // block_off_ + the flattened arrays' room

@@ -45,7 +45,7 @@ EXPORTS = [
     "jg_tpset_create", "jg_tpset_destroy", "jg_tpset_size", "jg_tpset_apply_ops", "jg_tpset_contains", "jg_tpset_lookup_all",
     "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
-    "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys", "jg_node_update_keys",
+    "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys", "jg_node_update_keys", "jg_node_update_keys_encode",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
     "jg_rows_set_narrow", "jg_rows_form",
@@ -173,6 +173,8 @@ _SIGS = {
     "jg_keyspace_lookup": ([_vp, _u64, _vp, _vp, _vp, _vp], C.c_int),
     "jg_node_query_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_node_update_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "jg_node_update_keys_encode": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _u64, _vp], C.c_int),
     "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
@@ -1055,6 +1057,52 @@ class Node:
         _check(load().jg_node_update_keys(self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(op), _ptr(flag), _ptr(amount), _ptr(eoff),
                                           _ptr(edata), _ptr(lo), _ptr(hi), col, _ptr(out["status"]), _ptr(out["result"]), _ptr(out["kind"]),
                                           _ptr(out["idx"]), _ptr(out["elem"]), _ptr(guid), _ptr(al), _ptr(rl)))
+        if with_guid:
+            out["guid"] = guid
+        if ords:
+            out["add_lim"], out["rem_lim"] = al, rl
+        return out
+
+    def update_keys_encode(self, keyspace: "KeySpace", keys, ops, args, snap=None, tags=None, col: int = 0, sha: bool = False, cap=None,
+                           with_guid: bool = False, ords: bool = False):
+        """jg_node_update_keys_encode: update_keys, and the snapshot SafeCRDT.Update ships for each PN-Counter command.
+        snap: None (1 for every command) or one of 0 (none) | 1 (this command's) | 2 (the row's latest of the 2s) per
+        command.  Returns update_keys' dict plus states (bytes per command, b"" where there is none), snap_off (u64[n+1])
+        and with sha: sha (u8[n, 32], zeros where there is none).  cap None: a generous buffer and one retry on
+        JG_ESTATE (nothing was applied); a number: that many bytes, an ESTATE raises with .snap_off on the error."""
+        n = len(keys)
+        koff, kdata, op, flag, amount, eoff, edata = pack_commands(keys, ops, args)
+        lo, hi = (None, None) if tags is None else (_arr(tags[0], np.uint64), _arr(tags[1], np.uint64))
+        if lo is not None and (lo.size != n or hi.size != n):
+            raise ValueError("update_keys_encode: one tag per command")
+        sn = None if snap is None else _arr(snap, np.uint8)
+        if sn is not None and sn.size != n:
+            raise ValueError("update_keys_encode: one snap entry per command")
+        out = {"status": np.zeros(n, np.uint8), "result": np.zeros(n, np.uint8), "kind": np.zeros(n, np.uint8),
+               "idx": np.zeros(n, np.uint32), "elem": np.zeros(n, np.uint32)}
+        guid = np.zeros(n, GUID_DTYPE) if with_guid else None
+        al, rl = (np.zeros(n, np.uint64), np.zeros(n, np.uint64)) if ords else (None, None)
+        soff = np.zeros(n + 1, np.uint64)
+        h = np.zeros((n, 32), np.uint8) if sha else None
+        buf = np.empty(max(16, n * 512 if cap is None else cap), np.uint8)
+        call = lambda: load().jg_node_update_keys_encode(
+            self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(op), _ptr(flag), _ptr(amount), _ptr(eoff), _ptr(edata), _ptr(lo), _ptr(hi), col,
+            _ptr(sn), _ptr(out["status"]), _ptr(out["result"]), _ptr(out["kind"]), _ptr(out["idx"]), _ptr(out["elem"]), _ptr(guid), _ptr(al),
+            _ptr(rl), _ptr(soff), _ptr(buf), buf.size if cap is None else cap, _ptr(h))
+        rc = call()
+        if rc == JG_ESTATE and cap is None and int(soff[-1]) > buf.size:  # nothing applied: again with room for every byte
+            buf = np.empty(int(soff[-1]), np.uint8)
+            rc = call()
+        try:
+            _check(rc)
+        except JanusError as e:
+            e.snap_off = soff
+            raise
+        b = buf[:int(soff[-1])].tobytes()
+        out["states"] = [b[int(soff[i]):int(soff[i + 1])] for i in range(n)]
+        out["snap_off"] = soff
+        if sha:
+            out["sha"] = h
         if with_guid:
             out["guid"] = guid
         if ords:
