@@ -438,8 +438,14 @@ int jg_tracker_destroy(jg_tracker* t);
  * while the apply task runs) and cheap: buffered, the device table takes the adds at the next call that
  * reads the tracker.  An identity already tracked keeps its entry. */
 int jg_tracker_add(jg_tracker* t, uint64_t n, const uint64_t* seq, const uint64_t* origin);
+/* Count: the identities tracked, every jg_tracker_add before the call included.  Both reads first move the buffered
+ * adds into the device table, unless a streamed wave (jg_apply_stream_begin .. _end) is open on the tracker and they
+ * would not fit the table as it stands: that wave classifies against the table it began with and completes into it,
+ * so the table is not rebuilt, cleared or freed under it.  The adds then stay buffered until the wave has ended, and
+ * both reads answer from the device table plus the buffered pairs (an identity in either is tracked, counted once).
+ * An identity added while a wave is open is either completed by that wave or still tracked after it, never both. */
 int jg_tracker_size(jg_tracker* t, uint64_t* n);
-/* ContainsKey: out[i] = 1 while seq[i] is tracked. */
+/* ContainsKey: out[i] = 1 while seq[i] is tracked (see jg_tracker_size for a read while a streamed wave is open). */
 int jg_tracker_contains(jg_tracker* t, uint64_t n, const uint64_t* seq, uint8_t* out);
 
 /* A committed wave in commit order (Consensus.Commit's List<List<UpdateMessage>>, Consensus.cs:123-134,

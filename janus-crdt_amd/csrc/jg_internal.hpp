@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "janus_gpu.h"
+#include "table_hash.hpp"
 
 namespace jg {
 
@@ -26,16 +27,7 @@ constexpr uint32_t kMaxTableReplicas = 256;
 // global key (PN-Counter row / OR-Set set id in the node's key space) is local x world + owner
 // (jg_global_key), so the exchange's routing rule owner_of_key(global) = global % world (route.hip, comm.hip)
 // names the same rank, and the owner stores it as local key global / world.
-__host__ __device__ __forceinline__ uint64_t uid_hash(uint64_t lo, uint64_t hi) {
-    uint64_t x = lo ^ (hi * 0x9E3779B97F4A7C15ull);
-    x ^= x >> 31;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 29;
-    return x;
-}
-__host__ __device__ __forceinline__ uint32_t shard_of_uid(uint64_t lo, uint64_t hi, uint32_t world) {
-    return world <= 1 ? 0u : (uint32_t)((uid_hash(lo, hi) >> 7) % world);
-}
+// (uid_hash and shard_of_uid: table_hash.hpp, which a CPU program compiles too.)
 __host__ __device__ __forceinline__ uint32_t owner_of_key(uint64_t global_key, uint32_t world) { return (uint32_t)(global_key % world); }
 __host__ __device__ __forceinline__ uint64_t local_of_key(uint64_t global_key, uint32_t world) { return global_key / world; }
 

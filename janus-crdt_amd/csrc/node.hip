@@ -23,7 +23,13 @@
 // is never a key, :134); load <= 1/2.  The library keeps the authoritative copy on the host (registration
 // is rare: key creation) and uploads the slots a registration touched before the next wave.
 // Tracker: open addressing over 16-B slots {identity, origin}, 0 = empty, ~0 = removed (a tombstone:
-// concurrent probes never see an entry move); rebuilt without tombstones when live + removed pass 1/2.
+// concurrent probes never see an entry move); rebuilt without tombstones when live + removed pass 1/2, but never
+// while a wave is open on it (jg_tracker::waves > 0: a streamed wave keeps the table pointer, claim pointer and mask
+// of its begin for every later classify, for its completions and its claim reset).  A flush that would rebuild
+// then leaves the pending pairs pending, one that fits goes in, and jg_tracker_size / _contains answer from the
+// device table plus the pending pairs; the first flush after the wave's end rebuilds as usual.  So the only code
+// that reallocates, clears, re-slots or frees a table or a claim array (the rebuild branch of jg_tracker::flush,
+// jg_tracker_destroy) runs with waves == 0.  Both hashes: table_hash.hpp (inverted by tests/node_hash.py).
 #include <cstring>
 #include <hipcub/hipcub.hpp>
 
@@ -54,15 +60,9 @@ using jg::UidSlot;  // uid_table.hpp: the table's layout and probe, shared with 
 struct TrackSlot { unsigned long long key, origin; };
 struct Guid16 { unsigned long long lo, hi; };
 
+using jg::seq_hash;  // table_hash.hpp: both tables' hashes
 using jg::uid_hash;
 __host__ __device__ __forceinline__ uint32_t shard_of(uint64_t lo, uint64_t hi, uint32_t world) { return jg::shard_of_uid(lo, hi, world); }
-__host__ __device__ __forceinline__ uint64_t seq_hash(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33;
-    x *= 0xC4CEB9FE1A85EC53ull;
-    return x ^ (x >> 33);
-}
 
 struct DevTrack { TrackSlot* tab; uint32_t* claim; uint64_t mask; };
 
@@ -319,22 +319,29 @@ struct jg_tracker {
     }
 
     // The pending adds into the device table, queued on the context's stream (under the context lock).
-    void flush() {
+    // false: nothing was moved and the pairs stay pending.  An open wave (waves > 0: a streamed one between its begin and
+    // its end) classifies every part against the table and claim array it began with and completes into them, so while
+    // one is open a flush that would have to rebuild — reallocate, clear or re-slot either array — is put off until
+    // the wave has ended; a flush that fits goes in (inserts fill empty slots only and move no entry).  Meanwhile
+    // jg_tracker_size / _contains answer from the device table plus the pending pairs (pending_keys).
+    bool flush() {
+        if (!count.p) {
+            count.alloc(8);
+            JG_HIP(hipMemsetAsync(count.p, 0, 8, ctx->stream));
+        }
         Pin* b;
         {
             std::lock_guard<std::mutex> g(pend_mu);
+            const uint64_t pending = pin[cur].n;
+            if (waves > 0 && pending && (cap == 0 || 2 * (used + pending) > cap)) return false;
             b = &pin[cur];
             cur ^= 1;
             pin[cur].reset();
             pin[cur].wait = pin[cur].up != nullptr;  // appends to it wait for its previous upload first
         }
-        if (!count.p) {
-            count.alloc(8);
-            JG_HIP(hipMemsetAsync(count.p, 0, 8, ctx->stream));
-        }
         const uint64_t np = b->n;
-        if (np == 0) return;
-        if (cap == 0 || 2 * (used + np) > cap) {  // rebuild without tombstones, into the spare table
+        if (np == 0) return true;
+        if (cap == 0 || 2 * (used + np) > cap) {  // rebuild without tombstones, into the spare table (waves == 0)
             unsigned long long live = 0;
             if (cap) {
                 JG_HIP(hipMemcpyAsync(&live, count.p, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -374,6 +381,35 @@ struct jg_tracker {
         hipLaunchKernelGGL(k_track_origin, dim3(blocks_for(np)), dim3(kBlock), 0, ctx->stream, dev(), dpairs.as<unsigned long long>(), slot_of, np);
         JG_HIP(hipGetLastError());
         used += np;
+        return true;
+    }
+
+    // ContainsKey of n host identities in the device table alone (synchronous; under the context lock).
+    void lookup(uint64_t n, const uint64_t* seq, uint8_t* out) {
+        char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * 9 + 512));
+        auto* ds = reinterpret_cast<unsigned long long*>(st);
+        auto* dout = reinterpret_cast<uint8_t*>(st + jg::round_up(n * 8, 256));
+        JG_HIP(hipMemcpyAsync(ds, seq, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_track_lookup, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, dev(), ds, n, dout);
+        JG_HIP(hipGetLastError());
+        JG_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, ctx->stream));
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+    }
+
+    // The distinct identities of the pairs a flush put off, in add order (the adds go on without the context lock:
+    // this is the buffer as it stands now).
+    std::vector<uint64_t> pending_keys() {
+        std::vector<uint64_t> keys;
+        std::unordered_set<uint64_t> seen;
+        std::lock_guard<std::mutex> g(pend_mu);
+        const Pin& b = pin[cur];
+        keys.reserve(b.n);
+        for (const Block& k : b.blocks) {
+            if (k.n == 0) break;  // blocks fill in order
+            for (size_t i = 0; i < k.n; ++i)
+                if (seen.insert(k.p[2 * i]).second) keys.push_back(k.p[2 * i]);
+        }
+        return keys;
     }
 };
 
@@ -1173,10 +1209,16 @@ int jg_tracker_size(jg_tracker* t, uint64_t* n) {
         JG_REQUIRE(t && n, JG_EINVAL, "jg_tracker_size: NULL argument");
         auto lk_ = jg::lock(t->ctx);
         jg::ensure_device(t->ctx);
-        t->flush();
+        const bool flushed = t->flush();
         unsigned long long c = 0;
         JG_HIP(hipMemcpyAsync(&c, t->count.p, 8, hipMemcpyDeviceToHost, t->ctx->stream));
         JG_HIP(hipStreamSynchronize(t->ctx->stream));
+        if (!flushed) {  // an open wave holds the table: the pending identities it does not hold count too
+            const std::vector<uint64_t> keys = t->pending_keys();
+            std::vector<uint8_t> held(keys.size());
+            if (!keys.empty()) t->lookup(keys.size(), keys.data(), held.data());
+            for (uint8_t h : held) c += h ? 0 : 1;
+        }
         *n = c;
     });
 }
@@ -1189,15 +1231,14 @@ int jg_tracker_contains(jg_tracker* t, uint64_t n, const uint64_t* seq, uint8_t*
         auto lk_ = jg::lock(t->ctx);
         jg_ctx* ctx = t->ctx;
         jg::ensure_device(ctx);
-        t->flush();
-        char* st = static_cast<char*>(jg::scratch(ctx, ctx->scratch, n * 9 + 512));
-        auto* ds = reinterpret_cast<unsigned long long*>(st);
-        auto* dout = reinterpret_cast<uint8_t*>(st + jg::round_up(n * 8, 256));
-        JG_HIP(hipMemcpyAsync(ds, seq, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_track_lookup, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, t->dev(), ds, n, dout);
-        JG_HIP(hipGetLastError());
-        JG_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, ctx->stream));
-        JG_HIP(hipStreamSynchronize(ctx->stream));
+        const bool flushed = t->flush();
+        t->lookup(n, seq, out);
+        if (!flushed) {  // an open wave holds the table: a pending identity is tracked as well
+            const std::vector<uint64_t> keys = t->pending_keys();
+            const std::unordered_set<uint64_t> pending(keys.begin(), keys.end());
+            for (uint64_t i = 0; i < n; ++i)
+                if (!out[i] && pending.count(seq[i])) out[i] = 1;
+        }
     });
 }
 

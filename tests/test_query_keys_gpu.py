@@ -77,8 +77,8 @@ class World:
         for g, t, i in zip(guids, types, idx):
             self.reg[g] = (t, i)
 
-    def add_keys(self, keys, types, idx):
-        self.register(self.create(keys), types, idx)
+    def add_keys(self, keys, types, idx, guids=None):
+        self.register(self.create(keys, guids), types, idx)
 
     def ops(self, ops):
         """[(set, op, name | None)] by name on the store and on the model."""

@@ -78,8 +78,8 @@ class Duo:
     def ks(self):
         return self.a.ks
 
-    def add_keys(self, keys, types, idx):
-        gs = self.a.create(keys)
+    def add_keys(self, keys, types, idx, guids=None):
+        gs = self.a.create(keys, guids)
         self.a.register(gs, types, idx)
         self.b.register(gs, types, idx)
 
