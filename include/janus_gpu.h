@@ -868,9 +868,9 @@ int jg_node_update_keys(jg_node* node, jg_keyspace* ks, uint64_t n,
  *                            per flush.
  *              snap[i] == 0: none.  Every command without a snapshot (snap 0, a 2 that did not survive, any failed
  *              status, every OR-Set command) has snap_off[i+1] == snap_off[i] and 32 zero bytes of sha.
- *   LIMIT: OR-Set commands are applied exactly as jg_node_update_keys applies them and get no bytes here.  Their
- *              snapshots stay where they are: jg_orset_encode_json at the add_lim / rem_lim this call returns, with the
- *              caller's rounds around a Clear.
+ *   OR-Set commands are applied exactly as jg_node_update_keys applies them and get no bytes from this call (add_lim /
+ *              rem_lim say where jg_orset_encode_json would cut).  The LIMIT this was is lifted by
+ *              jg_node_update_keys_ship below, which ships every kind's snapshots from one call.
  * JG_EINVAL in addition to jg_node_update_keys' list, every output and both stores untouched: snap_off NULL; a snap[i]
  * above 2; out NULL while the batch could ship a snapshot, which is decided from the arguments alone: a command with
  * arg_flag 3 whose snap is not 0 (or snap NULL).
@@ -888,6 +888,61 @@ int jg_node_update_keys_encode(jg_node* node, jg_keyspace* ks, uint64_t n,
                                uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem,
                                jg_guid* guid, uint64_t* add_lim, uint64_t* rem_lim,
                                uint64_t* snap_off, uint8_t* out, uint64_t cap, uint8_t* sha);
+
+/* ---------------------------------------------------------------------------------------------
+ * Client writes by key name that ship every snapshot, OR-Set keys included (csrc/update.hip, csrc/pnc_encode.hip,
+ * csrc/orset_encode.hip) — additive to ABI v10.
+ * SafeCRDT.Update (SafeCRDT.cs:39-62) for a whole batcher batch of any mix of keys: one call applies every command and
+ * returns, per command, the bytes of prospectiveState.crdt.GetLastSynchronizedUpdate().Encode() the batcher ships.
+ * Every argument shared with jg_node_update_keys_encode means what it means there: the statuses, the type rule, JG_U_*,
+ * kind / idx / elem / guid, snap (NULL = 1 for every command), snap_off (n + 1 entries, snap_off[0] = 0), sha (NULL or
+ * n x 32 bytes, 32 zero bytes for a command that ships nothing).  There is no add_lim / rem_lim: the snapshots replace
+ * them, and across rounds they would mean nothing.
+ *   PN-Counter commands.  Exactly as in jg_node_update_keys_encode: the same survivors, bytes and hashes.
+ *   OR-Set commands.  Applied exactly as jg_node_update_keys applies them (jg_orset_apply_ops_names' id rule, Clear
+ *              epochs, result and elem).  Command i's snapshot is ORSetMsg.Encode() (ORSet.cs:56-69, 305-308) of its set
+ *              as it stood right after command i: byte for byte jg_orset_encode_json's state of that set at command i's
+ *              ord limits, taken before any later Clear of the set is applied.
+ *   Who gets one.  Command i, iff it is an applied OR-Set command (status JG_U_OK, kind 1) and snap[i] == 1, or
+ *              snap[i] == 2 and no later applied OR-Set command with snap == 2 is on the same set (the batcher's
+ *              appearedObjects[np.uid] = np, SafeCRDTManager.cs:179, 186-187).  The op and its result do not matter: a
+ *              Remove that returned 0 and a Clear both ship (SafeCRDT.Update encodes whatever Update returned).  Both
+ *              kinds' survivors are decided on the device from the resolved object ids.
+ *   Rounds.    A Clear drops records a snapshot taken before it still needs, so the library applies the OR-Set commands
+ *              in rounds: per set, in batch order, a Clear starts a new round iff a shipping command on that set lies
+ *              between the set's previous Clear (or the batch start) and it; a command's round is the number of such
+ *              Clears of its own set at or before it.  Round r's commands are applied in batch order, then the round's
+ *              shipping commands are encoded.  *n_rounds (optional) is the number of rounds run: 0 for a batch without an
+ *              applied OR-Set command.  The stores end as after jg_orset_apply_ops_names over each round in turn.
+ *   The image. out[snap_off[i], snap_off[i+1]) is command i's snapshot, whatever its kind, in command order.  The image is
+ *              merged on the device and crosses the host link once.
+ *   Size.      The lengths of OR-Set snapshots are known only after their round is applied, so this call never refuses
+ *              for cap: *n_bytes (required) always receives snap_off[n]; if *n_bytes <= cap the bytes are copied to out,
+ *              else out is untouched, the call still returns JG_OK with everything applied, snap_off and sha filled,
+ *              and the node HOLDS the image on the device for jg_node_shipped.  out NULL with cap 0 means "hold it".
+ * jg_node_shipped(node, &nb, out, cap) fetches the held image: out NULL = size query; JG_ESTATE if cap is short (the image
+ * stays held); a successful fetch releases it; with nothing held JG_OK with *n_bytes = 0.  The held image is dropped by
+ * the next jg_node_update_keys_ship on the node that ships a byte and by jg_node_destroy.
+ * Refusals, all before anything is written (every output, both stores, the element table and the names log untouched):
+ * jg_node_update_keys' JG_EINVAL list; a snap[i] above 2; snap_off or n_bytes NULL; out NULL with cap > 0.
+ * JG_ESTATE: a set that would ship holds a record whose element id has no name in the store's table (records put
+ * there by jg_orset_load without jg_orset_names_sync) — the same set in a batch that ships nothing from it is applied
+ * as ever; or the batch has more than one round and the fullest set's next element id plus the most Adds the batch
+ * has on one set could pass the id limit (conservative; with one round jg_orset_apply_ops_names' own check decides).
+ * Round 0's apply can still refuse as jg_orset_apply_ops_names does, and then nothing has been written.
+ * ONCE ROUND 0 HAS WRITTEN, only an allocation failure or a HIP error can stop a later round (jg_apply_committed's rule
+ * for its OR-Set commit): the code is returned, the PN-Counter store is untouched (its adds run last) and the OR-Set
+ * store must be reloaded.
+ * n == 0 returns JG_OK with snap_off[0] = 0, *n_bytes = 0 and *n_rounds = 0. */
+int jg_node_update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n,
+                             const uint64_t* key_off, const uint8_t* key_bytes,
+                             const uint8_t* op, const uint8_t* arg_flag, const int64_t* amount,
+                             const uint64_t* elem_off, const uint8_t* elem_bytes,
+                             const uint64_t* tag_lo, const uint64_t* tag_hi, uint32_t col, const uint8_t* snap,
+                             uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx, uint32_t* elem, jg_guid* guid,
+                             uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap, uint8_t* sha,
+                             uint32_t* n_rounds);
+int jg_node_shipped(jg_node* node, uint64_t* n_bytes, uint8_t* out, uint64_t cap);
 
 /* ---------------------------------------------------------------------------------------------
  * Synthetic workloads (bench / size-independent parity): device-side counter-based generators,

@@ -343,6 +343,22 @@ struct OrsetGathered {
     uint8_t* keep;
 };
 OrsetGathered orset_gather_sets(jg_orset* s, uint64_t n, const uint32_t* d_sets, const unsigned long long* d_lim, jg::DevBuf& buf);
+// orset_encode.hip: what the encoder's write phase needs of its size phase (views into jg_orset_wire::enc and ::enc_g),
+// kept on the store's wire state from one to the other.
+struct OrsetEncPlan {
+    uint64_t n = 0;
+    OrsetGathered G{};
+    uint32_t *kidx = nullptr, *rid = nullptr, *rstart = nullptr, *srun = nullptr, *rrank = nullptr, *sfirst = nullptr, *srec = nullptr;
+    unsigned long long *K = nullptr, *nruns = nullptr, *skey = nullptr, *tlen = nullptr, *rpos = nullptr, *cpos = nullptr, *qsec = nullptr, *qoff = nullptr,
+                       *rtags = nullptr;
+    unsigned* err = nullptr;
+};
+// jg_orset_encode_json's size phase over n host set ids at the given ord limits (both NULL: every record), one state per
+// entry: h_off [n + 1] on the host, the same offsets left on the device (orset_encode_offsets).  false: a record names an
+// element id without a name (h_off is then not a state's length).  Synchronous; nothing is written.  Then its write
+// phase at those offsets into d_out (device, h_off[n] bytes), queued on the context's stream.  The caller holds the lock.
+bool orset_encode_size_locked(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* h_off);
+void orset_encode_write_locked(jg_orset* s, uint8_t* d_out);
 void orset_settle_pending(jg_orset* s, size_t at);
 // orset.hip: room in the store's union targets for that many more records (no sync; skipped while counts are pending).
 void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in);
@@ -395,6 +411,12 @@ struct PncSnap {
 // ev (or NULL; JANUS_TRACE_UPDATE): five events of the caller's, recorded behind the prefixes, survivors and list [0] and
 // the length pass with the offsets [1] (step 1), the write pass [2], the hashes [3] and the copy of the bytes [4] (step 2).
 void pnc_snap_plan_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint32_t col, uint64_t* m, uint64_t* h_snap_off, hipEvent_t* ev = nullptr);
+// Step 2's write pass alone (jg_node_update_keys_ship): the list's bytes in ctx->scratch2, at s.eoff, queued.
+const uint8_t* pnc_snap_bytes_locked(jg_pnc* p, const PncSnap& s, uint64_t m, uint64_t bytes, uint32_t col);
+// The survivors rule (snap_survivors.hpp) over any object key, for jg_node_update_keys_ship's OR-Set commands: d_obj[i]
+// is command i's object (none_obj: it touches none), d_snap as PncSnap::snap; d_none[i] = 1: it ships nothing.  Queued;
+// uses ctx->scratch and ctx->scratch3.
+void snap_survivors_locked(jg_ctx* ctx, const uint32_t* d_obj, uint64_t n, uint32_t none_obj, const uint8_t* d_snap, uint8_t* d_none);
 void pnc_snap_write_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint64_t m, uint64_t bytes, uint32_t col, uint8_t* out, uint8_t* sha,
                            hipEvent_t* ev = nullptr);
 // orset_wire.hip (OR-Set):

@@ -461,6 +461,7 @@ struct jg_node {
     std::vector<hipEvent_t> ev;  // pairs around each chunk's kernels and the final phase (device_busy_s)
     hipEvent_t drained = nullptr;  // the compute stream's tail when a wave starts (the copy queue waits on it)
     WaveRun run;                   // the wave in flight (one call, or a streamed wave between begin and end)
+    jg::ShipState ship;            // jg_node_update_keys_ship's held image and regions (update.hip)
 
     ~jg_node() {
         for (auto& a : arenas) (void)hipHostFree(a.first);
@@ -1060,8 +1061,9 @@ NodeRef node_query_ref(jg_node* nd, const char* fn) {
     JG_REQUIRE(!nd->run.active || (!nd->upload_all && nd->dirty.empty()), JG_EINVAL,
                "%s: a streamed wave of the node is open and registrations are pending", fn);
     nd->sync_table();
-    return NodeRef{nd->ctx, nd->pnc, nd->orset, DevUids{nd->dtab.as<UidSlot>(), nd->htab.size() - 1}};
+    return NodeRef{nd->ctx, nd->pnc, nd->orset, DevUids{nd->dtab.as<UidSlot>(), nd->htab.size() - 1}, nd->max_set};
 }
+ShipState& node_ship(jg_node* nd) { return nd->ship; }
 }  // namespace jg
 
 extern "C" {

@@ -250,8 +250,11 @@ __global__ void k_enc_rec_text(EncRec G, const uint32_t* __restrict__ kidx, cons
 // jg_orset_encode_json: gather the sets' records below the limits, order them (runs by section and element, tags
 // by ord), size every state, then write them (see the header comment).  Two round trips: the record
 // count (gather) and the states' offsets; a third copy brings the bytes.
-void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* off, uint8_t* out,
-                 uint64_t cap, uint8_t* sha) {
+//
+// The size phase: everything up to the states' offsets (P.qoff, on the device) and the missing-name flag, which it
+// queues into the page-locked bytes at 0; the caller's pin_sync brings it.  The plan (jg_orset_wire::enc_plan) is what
+// the write phase needs of it: it holds until the next size phase on the store.
+void encode_size(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim) {
     jg_ctx* ctx = s->ctx;
     jg::orset_elem_table(s, true)->ensure_names(ctx, 0, 0);  // a store that never saw a name: empty tables
     jg_orset_wire* w = s->wire;
@@ -271,59 +274,88 @@ void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* a
         JG_HIP(hipMemcpyAsync(d_lim, l.data(), 2 * n * 8, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipStreamSynchronize(ctx->stream));  // l is a local
     }
-    const jg::OrsetGathered G = jg::orset_gather_sets(s, n, d_sets, d_lim, w->enc_g);
+    jg::OrsetEncPlan& P = w->enc_plan;
+    P.n = n;
+    P.G = jg::orset_gather_sets(s, n, d_sets, d_lim, w->enc_g);
+    const jg::OrsetGathered& G = P.G;
     const uint64_t R = G.R;
     const EncRec E{G.key, G.tlo, G.thi, G.ord, G.qs};
     // the encoder's arrays, one block
     const uint64_t R1 = R + 1;
-    uint32_t *kidx, *hf, *rid, *rstart, *rend, *rfirst, *rval, *srun, *rrank, *sfirst, *recv, *srec;
-    ull *K, *nruns, *rkey, *skey, *cnt, *tlen, *rpos, *cpos, *qsec, *qlen, *qoff, *reck, *reck2, *rtags;
+    uint32_t *hf, *rend, *rfirst, *rval, *recv;
+    ull *rkey, *cnt, *qlen, *reck, *reck2;
     unsigned* err;
     jg::Layout L;
-    L.add(kidx, R), L.add(K, 1), L.add(hf, R), L.add(rid, R), L.add(rstart, R), L.add(rend, R), L.add(rfirst, R), L.add(nruns, 1);
-    L.add(rkey, R), L.add(rval, R), L.add(skey, R), L.add(srun, R), L.add(rrank, R), L.add(cnt, R1), L.add(tlen, R1), L.add(rpos, R1), L.add(cpos, R1);
-    L.add(qsec, 4 * n), L.add(sfirst, 4 * n), L.add(qlen, n + 1), L.add(qoff, n + 1);
-    L.add(reck, R), L.add(recv, R), L.add(reck2, R), L.add(srec, R), L.add(rtags, R), L.add(err, 1);
+    L.add(P.kidx, R), L.add(P.K, 1), L.add(hf, R), L.add(P.rid, R), L.add(P.rstart, R), L.add(rend, R), L.add(rfirst, R), L.add(P.nruns, 1);
+    L.add(rkey, R), L.add(rval, R), L.add(P.skey, R), L.add(P.srun, R), L.add(P.rrank, R), L.add(cnt, R1), L.add(P.tlen, R1), L.add(P.rpos, R1), L.add(P.cpos, R1);
+    L.add(P.qsec, 4 * n), L.add(P.sfirst, 4 * n), L.add(qlen, n + 1), L.add(P.qoff, n + 1);
+    L.add(reck, R), L.add(recv, R), L.add(reck2, R), L.add(P.srec, R), L.add(P.rtags, R), L.add(err, 1);
     ensure(w->enc, L.bytes());
     L.bind(w->enc.p);
-    JG_HIP(hipMemsetAsync(qsec, 0, 4 * n * 8, ctx->stream));
-    JG_HIP(hipMemsetAsync(sfirst, 0xFF, 4 * n * 4, ctx->stream));
+    JG_HIP(hipMemsetAsync(P.qsec, 0, 4 * n * 8, ctx->stream));
+    JG_HIP(hipMemsetAsync(P.sfirst, 0xFF, 4 * n * 4, ctx->stream));
     JG_HIP(hipMemsetAsync(err, 0, 4, ctx->stream));
-    JG_HIP(hipMemsetAsync(K, 0, 8, ctx->stream));
-    JG_HIP(hipMemsetAsync(nruns, 0, 8, ctx->stream));
+    JG_HIP(hipMemsetAsync(P.K, 0, 8, ctx->stream));
+    JG_HIP(hipMemsetAsync(P.nruns, 0, 8, ctx->stream));
     const unsigned gR = blocks_for(R);
     if (R) {
         const int n_R = jg::cub_count(R, "records"), n_R1 = jg::cub_count(R1, "records");
         const auto tmp = jg::cub_in(w->cub);
         hipcub::CountingInputIterator<uint32_t> iota(0);
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceSelect::Flagged(temp, bytes, iota, G.keep, kidx, K, n_R, ctx->stream); });
-        hipLaunchKernelGGL(k_enc_heads, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, R, hf);
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(temp, bytes, hf, rid, n_R, ctx->stream); });
-        hipLaunchKernelGGL(k_enc_runs, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rstart, rend, rfirst, nruns);
-        hipLaunchKernelGGL(k_enc_first_ord, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rfirst);
-        hipLaunchKernelGGL(k_enc_run_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, rstart, rfirst, nruns, R, rkey, rval);
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceSelect::Flagged(temp, bytes, iota, G.keep, P.kidx, P.K, n_R, ctx->stream); });
+        hipLaunchKernelGGL(k_enc_heads, dim3(gR), dim3(kBlock), 0, ctx->stream, E, P.kidx, P.K, R, hf);
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(temp, bytes, hf, P.rid, n_R, ctx->stream); });
+        hipLaunchKernelGGL(k_enc_runs, dim3(gR), dim3(kBlock), 0, ctx->stream, E, P.kidx, P.K, P.rid, P.rstart, rend, rfirst, P.nruns);
+        hipLaunchKernelGGL(k_enc_first_ord, dim3(gR), dim3(kBlock), 0, ctx->stream, E, P.kidx, P.K, P.rid, rfirst);
+        hipLaunchKernelGGL(k_enc_run_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, P.kidx, P.rstart, rfirst, P.nruns, R, rkey, rval);
         JG_HIP(hipGetLastError());
         jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, rkey, skey, rval, srun, n_R, 0, 64, ctx->stream);
+            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, rkey, P.skey, rval, P.srun, n_R, 0, 64, ctx->stream);
         });
-        hipLaunchKernelGGL(k_enc_run_len, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, kidx, rstart, rend, skey, srun, nruns, R, rrank, cnt, tlen, qsec,
-                           sfirst, err);
-        hipLaunchKernelGGL(k_enc_rec_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, rid, rrank, R, reck, recv);
+        hipLaunchKernelGGL(k_enc_run_len, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, P.kidx, P.rstart, rend, P.skey, P.srun, P.nruns, R, P.rrank, cnt,
+                           P.tlen, P.qsec, P.sfirst, err);
+        hipLaunchKernelGGL(k_enc_rec_keys, dim3(gR), dim3(kBlock), 0, ctx->stream, E, P.kidx, P.K, P.rid, P.rrank, R, reck, recv);
         JG_HIP(hipGetLastError());
         jg::cub_run(tmp, [&](void* temp, size_t& bytes) {
-            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, reck, reck2, recv, srec, n_R, 0, 64, ctx->stream);
+            return hipcub::DeviceRadixSort::SortPairs(temp, bytes, reck, reck2, recv, P.srec, n_R, 0, 64, ctx->stream);
         });
-        JG_HIP(hipMemsetAsync(tlen + R, 0, 8, ctx->stream));
+        JG_HIP(hipMemsetAsync(P.tlen + R, 0, 8, ctx->stream));
         JG_HIP(hipMemsetAsync(cnt + R, 0, 8, ctx->stream));
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, tlen, rpos, n_R1, ctx->stream); });
-        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, cpos, n_R1, ctx->stream); });
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, P.tlen, P.rpos, n_R1, ctx->stream); });
+        jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, cnt, P.cpos, n_R1, ctx->stream); });
     }
-    hipLaunchKernelGGL(k_enc_qlen, dim3(blocks_for(n + 1)), dim3(kBlock), 0, ctx->stream, qsec, n, qlen);
+    hipLaunchKernelGGL(k_enc_qlen, dim3(blocks_for(n + 1)), dim3(kBlock), 0, ctx->stream, P.qsec, n, qlen);
     JG_HIP(hipGetLastError());
     const int n_q = jg::cub_count(n + 1, "sets");
-    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, qlen, qoff, n_q, ctx->stream); });
-    JG_HIP(hipMemcpyAsync(off, qoff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    jg::pin_get(ctx, 0, err, 4);
+    jg::cub_run(jg::cub_in(w->cub), [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, qlen, P.qoff, n_q, ctx->stream); });
+    P.err = err;
+}
+
+// The write phase of the store's last size phase, at its offsets into dout (device; P.qoff[n] bytes).
+void encode_write(jg_orset* s, uint8_t* dout) {
+    jg_ctx* ctx = s->ctx;
+    jg_orset_wire* w = s->wire;
+    const Names N = w->names.view();
+    const jg::OrsetEncPlan& P = w->enc_plan;
+    const jg::OrsetGathered& G = P.G;
+    const EncRec E{G.key, G.tlo, G.thi, G.ord, G.qs};
+    const unsigned gR = blocks_for(G.R);
+    hipLaunchKernelGGL(k_enc_fixed, dim3(blocks_for(P.n)), dim3(kBlock), 0, ctx->stream, P.qoff, P.qsec, P.n, dout);
+    if (G.R) {
+        hipLaunchKernelGGL(k_enc_run_text, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, P.kidx, P.rstart, P.skey, P.srun, P.nruns, P.rpos, P.tlen, P.sfirst,
+                           P.qoff, P.qsec, P.rtags, dout);
+        hipLaunchKernelGGL(k_enc_rec_text, dim3(gR), dim3(kBlock), 0, ctx->stream, E, P.kidx, P.K, P.srec, P.rid, P.rrank, P.cpos, P.rtags, dout);
+    }
+    JG_HIP(hipGetLastError());
+}
+
+void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* off, uint8_t* out,
+                 uint64_t cap, uint8_t* sha) {
+    jg_ctx* ctx = s->ctx;
+    encode_size(s, n, set, add_lim, rem_lim);
+    const jg::OrsetEncPlan& P = s->wire->enc_plan;
+    JG_HIP(hipMemcpyAsync(off, P.qoff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    jg::pin_get(ctx, 0, P.err, 4);
     jg::pin_sync(ctx);  // the stream's copies above are done too
     unsigned e;
     std::memcpy(&e, jg::pin_at(ctx, 0), 4);
@@ -331,19 +363,28 @@ void encode_sets(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* a
     if (!out) return;  // size query
     JG_REQUIRE(off[n] <= cap, JG_ESTATE, "jg_orset_encode_json: %llu bytes exceed cap %llu", (unsigned long long)off[n], (unsigned long long)cap);
     auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, off[n] + 64));
-    hipLaunchKernelGGL(k_enc_fixed, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, qoff, qsec, n, dout);
-    if (R) {
-        hipLaunchKernelGGL(k_enc_run_text, dim3(gR), dim3(kBlock), 0, ctx->stream, E, N, kidx, rstart, skey, srun, nruns, rpos, tlen, sfirst, qoff, qsec,
-                           rtags, dout);
-        hipLaunchKernelGGL(k_enc_rec_text, dim3(gR), dim3(kBlock), 0, ctx->stream, E, kidx, K, srec, rid, rrank, cpos, rtags, dout);
-    }
-    JG_HIP(hipGetLastError());
-    if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(qoff), n, sha);  // each state's SHA-256 (ComputeDigest's first level)
+    encode_write(s, dout);
+    if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(P.qoff), n, sha);  // each state's SHA-256 (ComputeDigest's first level)
     JG_HIP(hipMemcpyAsync(out, dout, off[n], hipMemcpyDeviceToHost, ctx->stream));
     JG_HIP(hipStreamSynchronize(ctx->stream));
 }
 
 }  // namespace
+
+// jg_node_update_keys_ship (update.hip): the two phases with the offsets and the bytes left on the device
+bool jg::orset_encode_size_locked(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* h_off) {
+    jg_ctx* ctx = s->ctx;
+    encode_size(s, n, set, add_lim, rem_lim);
+    const jg::OrsetEncPlan& P = s->wire->enc_plan;
+    JG_HIP(hipMemcpyAsync(h_off, P.qoff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    jg::pin_get(ctx, 0, P.err, 4);
+    jg::pin_sync(ctx);
+    unsigned e;
+    std::memcpy(&e, jg::pin_at(ctx, 0), 4);
+    return e == 0;
+}
+
+void jg::orset_encode_write_locked(jg_orset* s, uint8_t* d_out) { encode_write(s, d_out); }
 
 extern "C" int jg_orset_encode_json(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* off,
                                     uint8_t* out, uint64_t cap, uint8_t* sha) {

@@ -141,4 +141,5 @@ struct jg_orset_wire {
     std::vector<unsigned long long> lc;  // host copy of ovf (overflow word, sub-list counts) taken by the check
     uint64_t last_cnt[2] = {0, 0};  // distinct records (add, tombstone) the last commit merged: the next wave's estimate
     jg::DevBuf enc_g, enc;       // jg_orset_encode_json (orset_encode.hip): the gathered records, the encoder's arrays
+    jg::OrsetEncPlan enc_plan;   // its last size phase, for the write phase that follows
 };

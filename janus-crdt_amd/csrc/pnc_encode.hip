@@ -2,6 +2,7 @@
 // messages the reference's nodes send (jg_pnc_encode_json, _before), and a batch of own-column client ops applied with
 // the rewinds or the snapshots SafeCRDT.Update ships for them (jg_pnc_apply_ops_rewind, _encode).  json.hip reads them.
 #include "pnc_table.hpp"
+#include "snap_survivors.hpp"
 
 namespace {
 
@@ -345,33 +346,12 @@ const unsigned long long* key_amounts(jg_pnc* p, const DevOps& d, uint64_t n, ui
 
 // ---- the snapshots of a batch resolved on the device (jg_node_update_keys_encode) -----------------
 // The batch is sorted with the commands that apply no PN-Counter op under row `none_row` (the store's n_keys), behind
-// every real row.  Sorted position s heads its row's run when its row differs from the one before it; an inclusive
-// max-scan of (head ? s : 0) then gives every position its run's head.
-__global__ void k_snap_heads(const uint32_t* __restrict__ seg, uint64_t n, uint32_t* __restrict__ head) {
-    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s < n) head[s] = s && seg[s] != seg[s - 1] ? (uint32_t)s : 0u;
-}
+// every real row; who ships is snap_survivors.hpp's rule over the row.
 
-// the batcher's compaction (SafeCRDTManager.cs:179, 186-187): per run, the latest position with snap == 2, + 1
-__global__ void k_snap_latest(const unsigned long long* __restrict__ sorted, uint64_t n, const uint32_t* __restrict__ seg, uint32_t none_row,
-                              const uint8_t* __restrict__ snap, const uint32_t* __restrict__ head, uint32_t* __restrict__ latest) {
+// sorted position s: its object key (jg_node_update_keys_ship's OR-Set commands, keyed by set id)
+__global__ void k_obj_seg(const unsigned long long* __restrict__ sorted, uint64_t n, uint32_t* __restrict__ seg) {
     const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s >= n || seg[s] == none_row) return;
-    if (snap[(uint32_t)sorted[s]] == 2) atomicMax(&latest[head[s]], (uint32_t)s + 1);
-}
-
-// command i ships a snapshot: an applied PN-Counter command with snap 1, or with snap 2 and no later 2 on its row.
-// none[i] = it does not (the hashes' zero flag), take[i] = it does (the flags the positions are scanned from).
-__global__ void k_snap_take(const unsigned long long* __restrict__ sorted, uint64_t n, const uint32_t* __restrict__ seg, uint32_t none_row,
-                            const uint8_t* __restrict__ snap, const uint32_t* __restrict__ head, const uint32_t* __restrict__ latest,
-                            uint8_t* __restrict__ none, uint32_t* __restrict__ take) {
-    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s >= n) return;
-    const uint32_t i = (uint32_t)sorted[s];
-    const uint32_t sn = snap ? snap[i] : 1;
-    const bool t = seg[s] != none_row && (sn == 1 || (sn == 2 && latest[head[s]] == (uint32_t)s + 1));
-    none[i] = !t;
-    take[i] = t;
+    if (s < n) seg[s] = (uint32_t)(sorted[s] >> 32);
 }
 
 // the encode list: the taken commands' rows and rewinds at their positions (pos = exclusive count of taken commands)
@@ -428,15 +408,7 @@ void pnc_snap_plan_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint32_t col,
     const unsigned long long* sorted = key_amounts<false>(p, d, n, p->n_keys + 1, keys, vals, excl, seg, tmp);
     hipLaunchKernelGGL(k_prefix_scatter, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, vals, excl, ddp, ddn);
     // the survivors of snap == 2, then who ships a snapshot
-    hipLaunchKernelGGL(k_snap_heads, dim3(g), dim3(kBlock), 0, ctx->stream, seg, n, mark);
-    JG_HIP(hipGetLastError());
-    jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::InclusiveScan(temp, bytes, mark, head, hipcub::Max(), n_i, ctx->stream); });
-    if (s.snap) {
-        JG_HIP(hipMemsetAsync(latest, 0, n * 4, ctx->stream));
-        hipLaunchKernelGGL(k_snap_latest, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, seg, none_row, s.snap, head, latest);
-    }
-    hipLaunchKernelGGL(k_snap_take, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, seg, none_row, s.snap, head, latest, s.none, take);
-    JG_HIP(hipGetLastError());
+    snap_survivors(ctx, sorted, seg, n, n_i, none_row, s.snap, mark, head, latest, s.none, take, tmp);
     JG_HIP(hipMemsetAsync(take + n, 0, 4, ctx->stream));
     jg::cub_run(tmp, [&](void* temp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(temp, bytes, take, pos, n1_i, ctx->stream); });
     hipLaunchKernelGGL(k_snap_list, dim3(g), dim3(kBlock), 0, ctx->stream, take, pos, n, s.row, ddp, ddn, s.erow, s.edp, s.edn);
@@ -461,6 +433,32 @@ void pnc_snap_plan_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint32_t col,
     JG_HIP(hipStreamSynchronize(ctx->stream));
 }
 
+const uint8_t* pnc_snap_bytes_locked(jg_pnc* p, const PncSnap& s, uint64_t m, uint64_t bytes, uint32_t col) {
+    jg_ctx* ctx = p->ctx;
+    auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, bytes + 64));
+    encode_write(p, m, col, Encode{s.erow, s.edp, s.edn, nullptr, s.eoff, nullptr, nullptr, 0, nullptr}, dout);
+    return dout;
+}
+
+void snap_survivors_locked(jg_ctx* ctx, const uint32_t* d_obj, uint64_t n, uint32_t none_obj, const uint8_t* d_snap, uint8_t* d_none) {
+    const int n_i = jg::cub_count(n, "commands");
+    const size_t t_scan = jg::cub_temp_bytes([&](void* temp, size_t& bytes) {
+        return hipcub::DeviceScan::InclusiveScan(temp, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, hipcub::Max(), n_i, ctx->stream);
+    });
+    unsigned long long* keys;
+    uint32_t *seg, *mark, *head, *latest, *take;
+    uint8_t* dtmp;
+    jg::Layout A;
+    A.add(keys, n), A.add(seg, n), A.add(mark, n), A.add(head, n), A.add(latest, n), A.add(take, n), A.add(dtmp, t_scan + 256);
+    A.bind(jg::scratch(ctx, ctx->scratch, A.bytes()));
+    const unsigned g = blocks_for(n);
+    hipLaunchKernelGGL(k_make_keys<false>, dim3(g), dim3(kBlock), 0, ctx->stream, d_obj, n, keys);
+    JG_HIP(hipGetLastError());
+    const unsigned long long* sorted = sort_keys(ctx, keys, n, (uint64_t)none_obj + 1);
+    hipLaunchKernelGGL(k_obj_seg, dim3(g), dim3(kBlock), 0, ctx->stream, sorted, n, seg);
+    snap_survivors(ctx, sorted, seg, n, n_i, none_obj, d_snap, mark, head, latest, d_none, take, jg::cub_in(dtmp, t_scan));
+}
+
 void pnc_snap_write_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint64_t m, uint64_t bytes, uint32_t col, uint8_t* out, uint8_t* sha,
                            hipEvent_t* ev) {
     jg_ctx* ctx = p->ctx;
@@ -472,8 +470,7 @@ void pnc_snap_write_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint64_t m, 
         for (int k = 2; k < 5; ++k) stamp(k);
         return;
     }
-    auto* dout = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch2, bytes + 64));
-    encode_write(p, m, col, Encode{s.erow, s.edp, s.edn, nullptr, s.eoff, nullptr, nullptr, 0, nullptr}, dout);
+    const uint8_t* dout = pnc_snap_bytes_locked(p, s, m, bytes, col);
     stamp(2);
     if (sha) jg::sha256_device(ctx, dout, reinterpret_cast<const uint64_t*>(s.snap_off), n, sha, s.none);
     stamp(3);

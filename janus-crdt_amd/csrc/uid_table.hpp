@@ -3,6 +3,8 @@
 // the reads by key name (query.hip).
 #pragma once
 
+#include <memory>
+
 #include "jg_internal.hpp"
 
 namespace jg {
@@ -37,8 +39,20 @@ struct NodeRef {
     jg_pnc* pnc;
     jg_orset* orset;
     DevUids uids;
+    uint32_t max_set;  // the largest set id registered (0 without one)
 };
 jg_ctx* node_ctx(const jg_node* nd);
 NodeRef node_query_ref(jg_node* nd, const char* fn);
+
+// What jg_node_update_keys_ship (update.hip) keeps on the node from one call to the next: the merged image of the last
+// call's snapshots, held for jg_node_shipped while `held`, and the regions the rounds' OR-Set states are written to
+// (reused, grown as needed).
+struct ShipState {
+    DevBuf image;
+    uint64_t bytes = 0;
+    bool held = false;
+    std::vector<std::unique_ptr<DevBuf>> region;
+};
+ShipState& node_ship(jg_node* nd);
 
 }  // namespace jg

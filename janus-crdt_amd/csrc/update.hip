@@ -1,5 +1,6 @@
-// update.hip — client writes by key name, resolved on the device: jg_node_update_keys, and the same
-// call shipping the PN-Counter snapshots SafeCRDT.Update sends next: jg_node_update_keys_encode.
+// update.hip — client writes by key name, resolved on the device: jg_node_update_keys, the same call
+// shipping the PN-Counter snapshots SafeCRDT.Update sends next: jg_node_update_keys_encode, and the same
+// call shipping every kind's snapshots in one image: jg_node_update_keys_ship, jg_node_shipped.
 //
 // The reference's "i" / "d" / "a" / "r" / "c" commands (CRDTCommands/PNCounterCommand.cs:42-53, ORSetCommand.cs:43-61) go
 // KeySpaceManager.GetKVPair -> SafeCRDT.Update (SafeCRDT.cs:39-47) -> prospectiveState.Update(operationID, args) in
@@ -25,15 +26,24 @@
 //                pass) before the OR-Set side, so the size check refuses before anything is written, and writes them
 //                behind it and in front of the adds: both passes read the rows as they stood before the call.
 //
+//   every kind   (jg_node_update_keys_ship only) the OR-Set commands' survivors are decided on the device like the
+//                PN-Counter commands' (snap_survivors.hpp), the host splits them into rounds around the Clears that follow
+//                a shipping command, each round is applied and its shipping commands encoded into a region of its own
+//                (orset_encode.hip's two phases), and ship_move.hpp's mover merges the regions and the PN-Counter list
+//                into one image in command order, which is hashed, copied out once (or held on the node) and followed
+//                by the adds.
+//
 // The resolve is a dependent chain of random lines: the kernel waits on memory, uses no LDS and few registers, so
 // occupancy is what hides the latency.  Nothing is published inside a launch: the kernel boundaries publish the list
 // and its count.
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "launch.hpp"
 #include "orset_names.hpp"
+#include "ship_move.hpp"
 #include "tpset_dict.hpp"
 #include "uid_table.hpp"
 #include "wave_append.hpp"
@@ -128,6 +138,29 @@ void check_offsets(const char* what, uint64_t n, const uint64_t* off) {
     JG_REQUIRE(off[n] < (1ull << 40), JG_EINVAL, "jg_node_update_keys: batch too large");
 }
 
+// What every entry point of this file refuses from the arguments alone (n > 0), and how many commands carry each flag.
+struct FlagCounts { uint64_t n[4]; };
+FlagCounts check_batch(const jg_node* node, const jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                       const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
+                       const uint64_t* tag_hi, const uint8_t* status, const uint8_t* result) {
+    JG_REQUIRE(node && ks && op && arg_flag && status && result, JG_EINVAL, "jg_node_update_keys: NULL argument");
+    JG_REQUIRE(jg::node_ctx(node) == ks->ctx, JG_EINVAL, "jg_node_update_keys: the key space and the node belong to different contexts");
+    JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_node_update_keys: at most 2^31 commands per call");
+    JG_REQUIRE(key_off, JG_EINVAL, "jg_node_update_keys: key_off is NULL");
+    check_offsets("key", n, key_off);
+    JG_REQUIRE(key_off[n] == 0 || key_bytes, JG_EINVAL, "jg_node_update_keys: key_bytes is NULL");
+    if (elem_off) check_offsets("elem", n, elem_off);
+    FlagCounts c{{0, 0, 0, 0}};
+    for (uint64_t i = 0; i < n; ++i) {
+        JG_REQUIRE(arg_flag[i] <= 3, JG_EINVAL, "jg_node_update_keys: arg_flag[%llu] = %u (0 none, 1 string, 2 null, 3 integer)", (ull)i, arg_flag[i]);
+        ++c.n[arg_flag[i]];
+    }
+    JG_REQUIRE(c.n[3] == 0 || amount, JG_EINVAL, "jg_node_update_keys: a command carries an integer and amount is NULL");
+    JG_REQUIRE(c.n[1] == 0 || (elem_off && elem_bytes), JG_EINVAL, "jg_node_update_keys: a command carries a string and elem_off or elem_bytes is NULL");
+    JG_REQUIRE(c.n[1] + c.n[2] == 0 || (tag_lo && tag_hi), JG_EINVAL, "jg_node_update_keys: a command carries an element and tag_lo or tag_hi is NULL");
+    return c;
+}
+
 // what jg_node_update_keys_encode adds to jg_node_update_keys' arguments
 struct Enc {
     const uint8_t* snap;
@@ -150,20 +183,8 @@ int update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_
             return;
         }
         // every refusal below is decided from the arguments: nothing has been copied or written yet
-        JG_REQUIRE(node && ks && op && arg_flag && status && result, JG_EINVAL, "jg_node_update_keys: NULL argument");
-        JG_REQUIRE(jg::node_ctx(node) == ks->ctx, JG_EINVAL, "jg_node_update_keys: the key space and the node belong to different contexts");
-        JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_node_update_keys: at most 2^31 commands per call");
+        const FlagCounts n_flag = check_batch(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, status, result);
         JG_REQUIRE(!add_lim == !rem_lim, JG_EINVAL, "jg_node_update_keys: add_lim and rem_lim go together");
-        JG_REQUIRE(key_off, JG_EINVAL, "jg_node_update_keys: key_off is NULL");
-        check_offsets("key", n, key_off);
-        JG_REQUIRE(key_off[n] == 0 || key_bytes, JG_EINVAL, "jg_node_update_keys: key_bytes is NULL");
-        if (elem_off) check_offsets("elem", n, elem_off);
-        uint64_t n_flag[4] = {0, 0, 0, 0};
-        for (uint64_t i = 0; i < n; ++i) {
-            JG_REQUIRE(arg_flag[i] <= 3, JG_EINVAL, "jg_node_update_keys: arg_flag[%llu] = %u (0 none, 1 string, 2 null, 3 integer)", (ull)i,
-                       arg_flag[i]);
-            ++n_flag[arg_flag[i]];
-        }
         if (enc) {  // a snapshot needs an applied PN-Counter command, which needs an integer: decided from the arguments
             bool may_ship = false;
             for (uint64_t i = 0; i < n; ++i) {
@@ -173,11 +194,6 @@ int update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_
             }
             JG_REQUIRE(!may_ship || enc->out, JG_EINVAL, "jg_node_update_keys_encode: a command may ship a snapshot and out is NULL");
         }
-        JG_REQUIRE(n_flag[3] == 0 || amount, JG_EINVAL, "jg_node_update_keys: a command carries an integer and amount is NULL");
-        JG_REQUIRE(n_flag[1] == 0 || (elem_off && elem_bytes), JG_EINVAL,
-                   "jg_node_update_keys: a command carries a string and elem_off or elem_bytes is NULL");
-        JG_REQUIRE(n_flag[1] + n_flag[2] == 0 || (tag_lo && tag_hi), JG_EINVAL,
-                   "jg_node_update_keys: a command carries an element and tag_lo or tag_hi is NULL");
         jg_ctx* ctx = ks->ctx;
         jg::ensure_device(ctx);
         const jg::NodeRef nd = jg::node_query_ref(node, "jg_node_update_keys");  // pending registrations to the device
@@ -190,7 +206,7 @@ int update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_
         // keys, ops, flags and amounts in one staging copy: koff | amount | key bytes | op | flag.  The elements stay on the
         // host: only the OR-Set side reads them, compacted.
         const uint64_t kb = key_off[n];
-        const bool ints = n_flag[3] != 0;
+        const bool ints = n_flag.n[3] != 0;
         UIn in{};
         UOut o{};
         jg::Layout L;
@@ -351,6 +367,305 @@ int update_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_
     });
 }
 
+// ---- jg_node_update_keys_ship: every snapshot of the batch, OR-Set keys included ---------------------
+// command i's object among the OR-Set sets: its set id, or none_obj for every command that is not an applied OR-Set command
+__global__ __launch_bounds__(kBlock) void k_u_ship_obj(const uint8_t* __restrict__ status, const uint8_t* __restrict__ kind,
+                                                       const uint32_t* __restrict__ idx, uint64_t n, uint32_t none_obj, uint32_t* __restrict__ obj) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) obj[i] = status[i] == JG_U_OK && kind[i] == 1 ? idx[i] : none_obj;
+}
+
+int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                     const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
+                     const uint64_t* tag_hi, uint32_t col, const uint8_t* snap, uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx,
+                     uint32_t* elem, jg_guid* guid, uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap, uint8_t* sha, uint32_t* n_rounds) {
+    return jg::guard([&] {
+        auto lk_ = jg::lock(ks);
+        JG_REQUIRE(snap_off && n_bytes, JG_EINVAL, "jg_node_update_keys_ship: snap_off or n_bytes is NULL");
+        if (n == 0) {
+            snap_off[0] = 0, *n_bytes = 0;
+            if (n_rounds) *n_rounds = 0;
+            return;
+        }
+        // every refusal below is decided from the arguments: nothing has been copied or written yet
+        const FlagCounts n_flag = check_batch(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, status, result);
+        for (uint64_t i = 0; snap && i < n; ++i)
+            JG_REQUIRE(snap[i] <= 2, JG_EINVAL, "jg_node_update_keys_ship: snap[%llu] = %u (0 none, 1 this command's, 2 the latest)", (ull)i, snap[i]);
+        JG_REQUIRE(out || cap == 0, JG_EINVAL, "jg_node_update_keys_ship: out is NULL and cap is not 0");
+        jg_ctx* ctx = ks->ctx;
+        jg::ensure_device(ctx);
+        const jg::NodeRef nd = jg::node_query_ref(node, "jg_node_update_keys_ship");
+        JG_REQUIRE(!nd.pnc || col < nd.pnc->R, JG_EINVAL, "jg_node_update_keys_ship: column %u outside the PN-Counter store's %u", col,
+                   nd.pnc ? nd.pnc->R : 0);
+        jg::require_writable(nd.pnc, "jg_node_update_keys_ship");
+        jg::require_writable(nd.orset, "jg_node_update_keys_ship");
+        JG_REQUIRE(!nd.orset || !jg::orset_wave_open(nd.orset), JG_EINVAL, "jg_node_update_keys_ship: a wave is open on the OR-Set store");
+        jg::ShipState& ship = jg::node_ship(node);
+
+        // the batch as jg_node_update_keys_encode stages it, and behind it what only this call needs: the OR-Set objects,
+        // their no-snapshot flags, and the mover's list (source address, merged offset, merged no-snapshot flag)
+        const uint64_t kb = key_off[n];
+        const bool ints = n_flag.n[3] != 0, snaps = snap != nullptr, plan = nd.pnc != nullptr;
+        UIn in{};
+        UOut o{};
+        jg::Layout L;
+        L.add(in.koff, n + 1, 8), L.add(in.amount, ints ? n : 0, 8), L.add(in.kbytes, kb, 8), L.add(in.op, n, 1), L.add(in.flag, n, 1);
+        L.add(in.snap, snaps ? n : 0, 1);
+        const size_t stage = L.skip(0, 8);
+        std::vector<uint8_t> h(stage);
+        L.bind(h.data());
+        std::memcpy(h.data(), key_off, (n + 1) * 8);
+        if (ints) std::memcpy(const_cast<long long*>(in.amount), amount, n * 8);
+        if (kb) std::memcpy(const_cast<uint8_t*>(in.kbytes), key_bytes, kb);
+        std::memcpy(const_cast<uint8_t*>(in.op), op, n);
+        std::memcpy(const_cast<uint8_t*>(in.flag), arg_flag, n);
+        if (snaps) std::memcpy(const_cast<uint8_t*>(in.snap), snap, n);
+        L.skip(16);
+        L.add(o.count, 1, 8), L.add(o.guid, guid ? n : 0, 8), L.add(o.pamt, n, 8), L.add(o.prow, n, 4);
+        L.add(o.idx, n, 4), L.add(o.status, n, 1), L.add(o.kind, n, 1), L.add(o.pisn, n, 1);
+        jg::PncSnap sn{};
+        L.add(o.eamt, n, 8), L.add(o.erow, n, 4), L.add(o.eisn, n, 1);
+        if (plan) sn.carve(L, n);
+        uint32_t* oobj;
+        uint8_t *onone, *mlist;
+        ull *msrc, *moff;
+        uint8_t* mnone;
+        L.add(oobj, n, 4), L.add(onone, n, 1);
+        const size_t mlist_at = L.add(msrc, n, 16), mlist_bytes = n * 8 + (n + 1) * 8 + n;  // one stretch, one copy up
+        L.add(moff, n + 1, 8), L.add(mnone, n, 1);
+        auto* d = static_cast<uint8_t*>(jg::scratch(ctx, ctx->scratch_u, L.bytes() + 64));
+        L.bind(d);
+        mlist = d + mlist_at;
+        if (!ints) in.amount = nullptr;
+        if (!snaps) in.snap = nullptr;
+        sn.row = o.erow, sn.amount = o.eamt, sn.is_n = o.eisn, sn.snap = in.snap;
+        if (!guid) o.guid = nullptr;
+
+        // JANUS_TRACE_UPDATE: the steps by the host's clock (each ends at a wait on the stream) and, by hipEvents, the
+        // mover, the hashes and the copy
+        static const bool tr = std::getenv("JANUS_TRACE_UPDATE") != nullptr;
+        double t_mark = jg::now_us();
+        const auto lap = [&] {
+            const double t = jg::now_us(), ms = (t - t_mark) * 1e-3;
+            t_mark = t;
+            return ms;
+        };
+        hipEvent_t ev[4] = {};
+        const auto stamp = [&](int k) {
+            if (!tr) return;
+            JG_HIP(hipEventCreate(&ev[k]));
+            JG_HIP(hipEventRecord(ev[k], ctx->stream));
+        };
+
+        JG_HIP(hipMemcpyAsync(d, h.data(), stage, hipMemcpyHostToDevice, ctx->stream));
+        JG_HIP(hipMemsetAsync(o.count, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_u_resolve<true>, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
+                           nd.pnc ? nd.pnc->n_keys : 0, nd.orset != nullptr, in, n, o);
+        JG_HIP(hipGetLastError());
+        std::vector<uint8_t> hres(n * 6), hnone(n, 1);
+        const auto* h_idx = reinterpret_cast<const uint32_t*>(hres.data());
+        const uint8_t *h_status = hres.data() + n * 4, *h_kind = hres.data() + n * 5;
+        JG_HIP(hipMemcpyAsync(hres.data(), o.idx, n * 6, hipMemcpyDeviceToHost, ctx->stream));
+        double ms_resolve = 0, ms_surv = 0, ms_pnc = 0, ms_dry = 0, ms_apply = 0, ms_enc = 0;
+        if (tr) {
+                JG_HIP(hipStreamSynchronize(ctx->stream));
+                ms_resolve = lap();
+            }
+        // the survivors of both kinds on the device (snap_survivors.hpp): the OR-Set commands by set id here, the PN-Counter
+        // commands by row in the plan below.  The OR-Set flags come down with idx | status | kind.
+        try {
+            if (nd.orset) {
+                const uint32_t none_obj = nd.max_set + 1;
+                hipLaunchKernelGGL(k_u_ship_obj, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, o.status, o.kind, o.idx, n, none_obj, oobj);
+                JG_HIP(hipGetLastError());
+                jg::snap_survivors_locked(ctx, oobj, n, none_obj, in.snap, onone);
+                JG_HIP(hipMemcpyAsync(hnone.data(), onone, n, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            if (tr) {
+                JG_HIP(hipStreamSynchronize(ctx->stream));
+                ms_surv = lap();
+            }
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);  // the copies into hres and hnone
+            throw;
+        }
+        // the PN-Counter snapshots planned and sized (§14's step 1; it reads only and waits on the stream)
+        std::vector<uint64_t> hoff_p(n + 1, 0);
+        uint64_t n_snap = 0;
+        try {
+            if (plan) jg::pnc_snap_plan_locked(nd.pnc, sn, n, col, &n_snap, hoff_p.data(), nullptr);
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);
+            throw;
+        }
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+        if (tr) ms_pnc = lap();
+
+        // the OR-Set commands in batch order, who of them ships, and each one's round: per set, a Clear starts a new round
+        // iff a shipping command on the set lies between the set's previous Clear (or the batch start) and it
+        std::vector<uint32_t> at;
+        for (uint64_t i = 0; i < n; ++i)
+            if (h_status[i] == JG_U_OK && h_kind[i] == 1) at.push_back((uint32_t)i);
+        const uint64_t n_o = nd.orset ? at.size() : 0;
+        std::vector<uint32_t> round(n_o, 0);
+        uint32_t rounds = n_o ? 1 : 0;
+        uint64_t max_adds = 0;
+        std::vector<uint32_t> ship_sets;
+        if (n_o) {
+            struct PerSet { uint32_t round = 0, adds = 0; bool open = false, ships = false; };  // open: a command shipped since the last Clear
+            std::vector<PerSet> per((size_t)nd.max_set + 1);
+            for (uint64_t k = 0; k < n_o; ++k) {
+                const uint32_t i = at[k];
+                PerSet& ps = per[h_idx[i]];
+                if (op[i] == 3 && ps.open) ++ps.round, ps.open = false;
+                round[k] = ps.round;
+                rounds = std::max(rounds, ps.round + 1);
+                if (!hnone[i]) {
+                    if (!ps.ships) ship_sets.push_back(h_idx[i]);
+                    ps.open = ps.ships = true;
+                }
+                if (op[i] == 1 && arg_flag[i] == 1) max_adds = std::max<uint64_t>(max_adds, ++ps.adds);
+            }
+        }
+        // refusals that need the stores, still before anything is written: a shipping set with a record whose element id has
+        // no name (the encoder's size phase, without limits, over the distinct shipping sets), and a batch of several rounds
+        // that could run a set out of element ids in a later round
+        std::vector<uint64_t> roff;
+        if (!ship_sets.empty()) {
+            roff.resize(ship_sets.size() + 1);
+            JG_REQUIRE(jg::orset_encode_size_locked(nd.orset, ship_sets.size(), ship_sets.data(), nullptr, nullptr, roff.data()), JG_ESTATE,
+                       "jg_node_update_keys_ship: a set that would ship holds a record whose element id has no name in the element table (names not "
+                       "synced; nothing applied)");
+        }
+        if (rounds > 1) {
+            jg::ElemTable& T = *jg::orset_elem_table(nd.orset, true);
+            if (T.id_bound + max_adds >= kNever) T.tight_id_bound(ctx, ctx->scratch3);
+            JG_REQUIRE(T.id_bound + max_adds < kNever, JG_ESTATE,
+                       "jg_node_update_keys_ship: a batch of %u rounds could leave a set without element ids (nothing applied)", rounds);
+        }
+        if (tr) ms_dry = lap();
+
+        // the rounds: apply round r's commands in batch order, then size and write its shipping commands' states at the ord
+        // limits the apply returned, into the round's own region.  Round 0's apply can still refuse; nothing is written then.
+        std::vector<uint8_t> res(n, 0);
+        std::vector<uint32_t> el(elem ? n : 0, kNever);
+        std::vector<uint64_t> len(n, 0), src(n, 0);
+        for (uint32_t r = 0; r < rounds; ++r) {
+            std::vector<uint32_t> cmd, oset, oel;
+            std::vector<uint8_t> oop, onull, ores, obytes;
+            std::vector<uint64_t> ooff{0}, olo, ohi;
+            for (uint64_t k = 0; k < n_o; ++k) {
+                if (round[k] != r) continue;
+                const uint32_t i = at[k];
+                cmd.push_back(i), oset.push_back(h_idx[i]), oop.push_back(op[i]), onull.push_back(op[i] != 3 && arg_flag[i] == 2);
+                olo.push_back(tag_lo ? tag_lo[i] : 0), ohi.push_back(tag_hi ? tag_hi[i] : 0);
+                if (op[i] != 3 && arg_flag[i] == 1) obytes.insert(obytes.end(), elem_bytes + elem_off[i], elem_bytes + elem_off[i + 1]);
+                ooff.push_back(obytes.size());
+            }
+            const uint64_t n_r = cmd.size();
+            if (obytes.empty()) obytes.push_back(0);
+            ores.resize(n_r), oel.resize(n_r);
+            std::vector<uint64_t> oal(n_r), orl(n_r);
+            jg::orset_apply_ops_names_locked(nd.orset, n_r, oset.data(), oop.data(), ooff.data(), obytes.data(), onull.data(), olo.data(), ohi.data(),
+                                             ores.data(), oel.data(), oal.data(), orl.data());
+            std::vector<uint32_t> scmd, sset;
+            std::vector<uint64_t> sal, srl;
+            for (uint64_t k = 0; k < n_r; ++k) {
+                const uint32_t i = cmd[k];
+                res[i] = ores[k];
+                if (elem) el[i] = oel[k];
+                if (!hnone[i]) scmd.push_back(i), sset.push_back(oset[k]), sal.push_back(oal[k]), srl.push_back(orl[k]);
+            }
+            if (tr) ms_apply += lap();
+            const uint64_t n_s = scmd.size();
+            if (n_s) {
+                roff.resize(n_s + 1);
+                JG_REQUIRE(jg::orset_encode_size_locked(nd.orset, n_s, sset.data(), sal.data(), srl.data(), roff.data()), JG_ESTATE,
+                           "jg_node_update_keys_ship: a record names an element id the element table does not hold");
+                while (ship.region.size() <= r) ship.region.push_back(std::make_unique<jg::DevBuf>());
+                jg::DevBuf& reg = *ship.region[r];
+                jg::ensure(reg, roff[n_s] + 64);
+                jg::orset_encode_write_locked(nd.orset, reg.as<uint8_t>());
+                for (uint64_t k = 0; k < n_s; ++k) len[scmd[k]] = roff[k + 1] - roff[k], src[scmd[k]] = (uint64_t)(uintptr_t)reg.p + roff[k];
+            }
+            if (tr) {
+                JG_HIP(hipStreamSynchronize(ctx->stream));
+                ms_enc += lap();
+            }
+        }
+        // the PN-Counter list's bytes (the rows as they stand: the adds land behind the image), then the mover's list
+        if (n_snap) {
+            const uint8_t* dpnc = jg::pnc_snap_bytes_locked(nd.pnc, sn, n_snap, hoff_p[n], col);
+            for (uint64_t i = 0; i < n; ++i)
+                if (hoff_p[i + 1] != hoff_p[i]) len[i] = hoff_p[i + 1] - hoff_p[i], src[i] = (uint64_t)(uintptr_t)dpnc + hoff_p[i];
+        }
+        std::vector<uint8_t> hm(mlist_bytes);
+        auto* h_src = reinterpret_cast<uint64_t*>(hm.data());
+        auto* h_off = h_src + n;
+        uint8_t* h_none = reinterpret_cast<uint8_t*>(h_off + n + 1);
+        h_off[0] = 0;
+        for (uint64_t i = 0; i < n; ++i) h_src[i] = src[i], h_off[i + 1] = h_off[i] + len[i], h_none[i] = len[i] == 0;
+        const uint64_t total = h_off[n];
+        stamp(0);
+        if (total) {
+            ship.held = false;  // the image an earlier call left is overwritten here
+            jg::ensure(ship.image, total + 64);
+            JG_HIP(hipMemcpyAsync(mlist, hm.data(), mlist_bytes, hipMemcpyHostToDevice, ctx->stream));
+            ship_move(ctx->stream, msrc, moff, n, ship.image.as<uint8_t>());
+            JG_HIP(hipGetLastError());
+        }
+        stamp(1);
+        if (sha && total) jg::sha256_device(ctx, ship.image.as<uint8_t>(), reinterpret_cast<const uint64_t*>(moff), n, sha, mnone);
+        stamp(2);
+        const bool fits = total <= cap;
+        if (total && fits) JG_HIP(hipMemcpyAsync(out, ship.image.p, total, hipMemcpyDeviceToHost, ctx->stream));
+        stamp(3);
+        if (nd.pnc) jg::pnc_add_list_device(nd.pnc, o.prow, o.pamt, o.pisn, o.count, n, col);
+        if (guid) JG_HIP(hipMemcpyAsync(guid, o.guid, n * sizeof(jg_guid), hipMemcpyDeviceToHost, ctx->stream));
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+        ship.bytes = total;
+        ship.held = total != 0 && !fits;
+        for (uint64_t i = 0; i < n; ++i)
+            if (h_status[i] == JG_U_OK && h_kind[i] == 0) res[i] = 1;
+        std::memcpy(status, h_status, n);
+        std::memcpy(result, res.data(), n);
+        if (kind) std::memcpy(kind, h_kind, n);
+        if (idx) std::memcpy(idx, h_idx, n * 4);
+        if (elem) std::memcpy(elem, el.data(), n * 4);
+        std::memcpy(snap_off, h_off, (n + 1) * 8);
+        *n_bytes = total;
+        if (sha && !total) std::memset(sha, 0, n * 32);
+        if (n_rounds) *n_rounds = rounds;
+        if (tr) {
+            float mv = 0, hs = 0, cp = 0;
+            JG_HIP(hipEventElapsedTime(&mv, ev[0], ev[1]));
+            JG_HIP(hipEventElapsedTime(&hs, ev[1], ev[2]));
+            JG_HIP(hipEventElapsedTime(&cp, ev[2], ev[3]));
+            std::fprintf(stderr, "update_keys_ship(%llu commands, %llu OR-Set, %u rounds, %llu bytes): upload + resolve %.3f ms, OR-Set survivors %.3f ms, "
+                         "PN-Counter plan %.3f ms, rounds on the host + dry size phase %.3f ms, applies %.3f ms, encodes %.3f ms, mover %.3f ms, "
+                         "hashes %.3f ms, copy %.3f ms\n", (ull)n, (ull)n_o, rounds, (ull)total, ms_resolve, ms_surv, ms_pnc, ms_dry, ms_apply, ms_enc,
+                         mv, hs, cp);
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        }
+    });
+}
+
+int node_shipped(jg_node* node, uint64_t* n_bytes, uint8_t* out, uint64_t cap) {
+    return jg::guard([&] {
+        JG_REQUIRE(node && n_bytes, JG_EINVAL, "jg_node_shipped: NULL argument");
+        jg_ctx* ctx = jg::node_ctx(node);
+        auto lk_ = jg::lock(ctx);
+        jg::ShipState& ship = jg::node_ship(node);
+        *n_bytes = ship.held ? ship.bytes : 0;
+        if (!ship.held || !out) return;  // nothing held, or a size query
+        JG_REQUIRE(ship.bytes <= cap, JG_ESTATE, "jg_node_shipped: %llu bytes exceed cap %llu (the image stays held)", (ull)ship.bytes, (ull)cap);
+        jg::ensure_device(ctx);
+        JG_HIP(hipMemcpyAsync(out, ship.image.p, ship.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        JG_HIP(hipStreamSynchronize(ctx->stream));
+        ship.held = false;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -372,5 +687,16 @@ int jg_node_update_keys_encode(jg_node* node, jg_keyspace* ks, uint64_t n, const
     return update_keys(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, col, status, result, kind, idx, elem,
                        guid, add_lim, rem_lim, &enc);
 }
+
+int jg_node_update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
+                             const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes,
+                             const uint64_t* tag_lo, const uint64_t* tag_hi, uint32_t col, const uint8_t* snap, uint8_t* status, uint8_t* result,
+                             uint8_t* kind, uint32_t* idx, uint32_t* elem, jg_guid* guid, uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap,
+                             uint8_t* sha, uint32_t* n_rounds) {
+    return update_keys_ship(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, col, snap, status, result, kind,
+                            idx, elem, guid, snap_off, n_bytes, out, cap, sha, n_rounds);
+}
+
+int jg_node_shipped(jg_node* node, uint64_t* n_bytes, uint8_t* out, uint64_t cap) { return node_shipped(node, n_bytes, out, cap); }
 
 }  // extern "C"

@@ -818,10 +818,17 @@ std::vector<KeyUpdate> GpuStableStore::UpdateKeysEncode(GpuKeySpace& ks, const s
     return update_keys(ks, commands, &snap, &messages);
 }
 
-// Both: messages NULL = jg_node_update_keys, else jg_node_update_keys_encode (once more with room for every byte when
-// the first buffer was too small: nothing was applied).
+std::vector<KeyUpdate> GpuStableStore::UpdateKeysShip(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
+                                                      std::vector<KeyMessage>& messages, uint32_t* n_rounds) {
+    if (!snap.empty() && snap.size() != commands.size()) throw EngineError(JG_EINVAL, "UpdateKeysShip: one snap entry per command");
+    return update_keys(ks, commands, &snap, &messages, true, n_rounds);
+}
+
+// All three: messages NULL = jg_node_update_keys, else jg_node_update_keys_encode (once more with room for every byte when
+// the first buffer was too small: nothing was applied) or, ship, jg_node_update_keys_ship (everything is applied whatever
+// the buffer holds: a short one is followed by jg_node_shipped).
 std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>* snap,
-                                                   std::vector<KeyMessage>* messages) {
+                                                   std::vector<KeyMessage>* messages, bool ship, uint32_t* n_rounds) {
     const size_t n = commands.size();
     std::vector<KeyUpdate> out(n);
     if (messages) messages->assign(n, KeyMessage{});
@@ -859,12 +866,26 @@ std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::v
                                               status.data(), result.data(), kind.data(), idx.data(), elem.data(), nullptr, nullptr, nullptr,
                                               snap_off.data(), bytes.data(), bytes.size(), sha.data());
         };
-        int rc = call();
-        if (rc == JG_ESTATE && snap_off[n] > bytes.size()) {
-            bytes.resize(snap_off[n]);
-            rc = call();
+        if (ship) {
+            uint64_t nb = 0;
+            uint32_t rounds = 0;
+            check(jg_node_update_keys_ship(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(), elem_off.data(),
+                                           elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, snap->empty() ? nullptr : snap->data(), status.data(),
+                                           result.data(), kind.data(), idx.data(), elem.data(), nullptr, snap_off.data(), &nb, bytes.data(), bytes.size(),
+                                           sha.data(), &rounds));
+            if (nb > bytes.size()) {
+                bytes.resize(nb);
+                check(jg_node_shipped(node_, &nb, bytes.data(), bytes.size()));
+            }
+            if (n_rounds) *n_rounds = rounds;
+        } else {
+            int rc = call();
+            if (rc == JG_ESTATE && snap_off[n] > bytes.size()) {
+                bytes.resize(snap_off[n]);
+                rc = call();
+            }
+            check(rc);
         }
-        check(rc);
         for (size_t i = 0; i < n; ++i) {
             (*messages)[i].message.assign(reinterpret_cast<const char*>(bytes.data()) + snap_off[i], snap_off[i + 1] - snap_off[i]);
             std::memcpy((*messages)[i].sha256.data(), sha.data() + 32 * i, 32);

@@ -302,6 +302,11 @@ class GpuStableStore {
     // not switched over to it.
     std::vector<KeyUpdate> UpdateKeysEncode(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
                                             std::vector<KeyMessage>& messages);
+    // The same for every kind of key (jg_node_update_keys_ship): OR-Set commands get their messages too, ORSetMsg.Encode()
+    // of the set right after the command, with the rounds around a Clear run inside the library.  *n_rounds (optional):
+    // the OR-Set rounds the call ran.  A first buffer that was short is followed by jg_node_shipped.
+    std::vector<KeyUpdate> UpdateKeysShip(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
+                                          std::vector<KeyMessage>& messages, uint32_t* n_rounds = nullptr);
     // GetLastSynchronizedUpdate().Encode() of PN-Counter keys, encoded on the device — the payload
     // SafeCRDT.Update ships after a client op (SafeCRDT.cs:49; batch producer).
     std::vector<std::string> EncodePNCStates(const std::vector<Guid>& uids);
@@ -427,9 +432,9 @@ class GpuStableStore {
     const KeyRef& ref(const Guid& uid, CrdtType want) const;
     void check(int rc) const;
     void flush_registrations();  // pending CreateSafeCRDT registrations -> jg_node_register + jg_pnc_intern
-    // UpdateKeys (messages NULL) and UpdateKeysEncode
+    // UpdateKeys (messages NULL), UpdateKeysEncode and (ship) UpdateKeysShip
     std::vector<KeyUpdate> update_keys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>* snap,
-                                       std::vector<KeyMessage>* messages);
+                                       std::vector<KeyMessage>* messages, bool ship = false, uint32_t* n_rounds = nullptr);
     // ApplyCommitted / ReceivedBlock: flatten the messages into the jg_commit arrays, one library call.
     std::vector<uint64_t> apply(const std::vector<const UpdateMessage*>& blocks, SafeUpdateTracker* tracker, bool block_mode);
     size_t index_blocks(const std::vector<const UpdateMessage*>& blocks);  // block_off_ + the flattened arrays' room

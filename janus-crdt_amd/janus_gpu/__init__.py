@@ -46,6 +46,7 @@ EXPORTS = [
     "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
     "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys", "jg_node_update_keys", "jg_node_update_keys_encode",
+    "jg_node_update_keys_ship", "jg_node_shipped",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
     "jg_rows_set_narrow", "jg_rows_form",
@@ -175,6 +176,9 @@ _SIGS = {
     "jg_node_update_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "jg_node_update_keys_encode": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _u64, _vp], C.c_int),
+    "jg_node_update_keys_ship": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _u64, _vp, _vp], C.c_int),
+    "jg_node_shipped": ([_vp, _vp, _vp, _u64], C.c_int),
     "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
@@ -1108,6 +1112,64 @@ class Node:
         if ords:
             out["add_lim"], out["rem_lim"] = al, rl
         return out
+
+    def update_keys_ship(self, keyspace: "KeySpace", keys, ops, args, snap=None, tags=None, col: int = 0, sha: bool = False, cap=None,
+                         with_guid: bool = False):
+        """jg_node_update_keys_ship: update_keys, and the snapshot SafeCRDT.Update ships for each command of either kind
+        (the OR-Set rounds around a Clear run inside the library).  snap as update_keys_encode takes it.  Returns
+        update_keys' dict plus states (bytes per command, b"" where there is none), snap_off (u64[n+1]), n_bytes, n_rounds
+        and with sha: sha (u8[n, 32], zeros where there is none).  cap None: a generous buffer, and the image the node
+        holds fetched through shipped() when it was short; a number: that many bytes, and states is None when the image
+        did not fit (n_bytes > cap: it is held for shipped())."""
+        n = len(keys)
+        koff, kdata, op, flag, amount, eoff, edata = pack_commands(keys, ops, args)
+        lo, hi = (None, None) if tags is None else (_arr(tags[0], np.uint64), _arr(tags[1], np.uint64))
+        if lo is not None and (lo.size != n or hi.size != n):
+            raise ValueError("update_keys_ship: one tag per command")
+        sn = None if snap is None else _arr(snap, np.uint8)
+        if sn is not None and sn.size != n:
+            raise ValueError("update_keys_ship: one snap entry per command")
+        out = {"status": np.zeros(n, np.uint8), "result": np.zeros(n, np.uint8), "kind": np.zeros(n, np.uint8),
+               "idx": np.zeros(n, np.uint32), "elem": np.zeros(n, np.uint32)}
+        guid = np.zeros(n, GUID_DTYPE) if with_guid else None
+        soff = np.zeros(n + 1, np.uint64)
+        h = np.zeros((n, 32), np.uint8) if sha else None
+        nb, nr = C.c_uint64(0), C.c_uint32(0)
+        buf = np.empty(max(16, n * 512 if cap is None else cap), np.uint8)
+        _check(load().jg_node_update_keys_ship(
+            self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(op), _ptr(flag), _ptr(amount), _ptr(eoff), _ptr(edata), _ptr(lo), _ptr(hi), col,
+            _ptr(sn), _ptr(out["status"]), _ptr(out["result"]), _ptr(out["kind"]), _ptr(out["idx"]), _ptr(out["elem"]), _ptr(guid), _ptr(soff),
+            C.addressof(nb), _ptr(buf), buf.size if cap is None else cap, _ptr(h), C.addressof(nr)))
+        total = int(nb.value)
+        fits = total <= (buf.size if cap is None else cap)
+        if not fits and cap is None:
+            buf, fits = self.shipped(), True
+        if fits:
+            b = buf[:total].tobytes()
+            out["states"] = [b[int(soff[i]):int(soff[i + 1])] for i in range(n)]
+        else:
+            out["states"] = None
+        out["snap_off"], out["n_bytes"], out["n_rounds"] = soff, total, int(nr.value)
+        if sha:
+            out["sha"] = h
+        if with_guid:
+            out["guid"] = guid
+        return out
+
+    def shipped(self, cap=None):
+        """jg_node_shipped: the image the last update_keys_ship left on the node (u8 array; empty with nothing held).
+        cap: fetch into that many bytes (JG_ESTATE if short, the image stays held); None: sized by a query first."""
+        nb = C.c_uint64(0)
+        _check(load().jg_node_shipped(self._h, C.addressof(nb), None, 0))
+        buf = np.empty(max(1, int(nb.value) if cap is None else cap), np.uint8)
+        _check(load().jg_node_shipped(self._h, C.addressof(nb), _ptr(buf), int(nb.value) if cap is None else cap))
+        return buf[:int(nb.value)]
+
+    def shipped_size(self) -> int:
+        """jg_node_shipped's size query: the bytes of the held image, 0 with nothing held."""
+        nb = C.c_uint64(0)
+        _check(load().jg_node_shipped(self._h, C.addressof(nb), None, 0))
+        return int(nb.value)
 
     def _commit(self, lo, hi, types, seqs, msgs=None, data=None, off=None, pinned=None):
         if msgs is not None:
