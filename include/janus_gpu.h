@@ -945,6 +945,66 @@ int jg_node_update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n,
 int jg_node_shipped(jg_node* node, uint64_t* n_bytes, uint8_t* out, uint64_t cap);
 
 /* ---------------------------------------------------------------------------------------------
+ * CRDT creation on the device (csrc/adopt.hip) — additive to ABI v10.
+ * The reference creates a CRDT on its receive path: ReplicationManager.ReceivedNewObjectSyncMsg
+ * (ReplicationManager.cs:310-324) records uid -> type when a ManagerMsg_Create arrives (CreateCRDTInstance), and
+ * KeySpaceManager.OnNext (KeySpaceManager.cs:151-178) calls SafeCRDTManager.CreateSafeCRDT(key, guid)
+ * (SafeCRDTManager.cs:86-101) for every key it learns, which reads the type back with rm.GetCRDTType(guid) and creates
+ * the stable instance.  Here the node allocates the rows: the caller keeps neither a row allocator nor a
+ * uid -> (type, row) map, and a learnt key becomes a usable CRDT without leaving the device.
+ *
+ * ALLOCATION (per node, per kind).  The next PN-Counter row is one past the largest row registered on the node by any
+ * path (jg_node_register included), 0 with none; the next set id likewise.  Within one call the created entries of a
+ * kind take consecutive indices in call order.  jg_node_next_idx reads both (either pointer may be NULL).
+ * When the rows a call needs pass the store's n_keys the store grows as jg_pnc_reserve grows it, to
+ * max(needed, 2 x n_keys) clipped to max_keys; JG_ESTATE when needed > max_keys (max_keys 0: the store never grows),
+ * when the set ids would pass 2^31 - 16, or when `replica` has no free column in a row someone interned by hand.
+ * jg_pnc_reserve's own refusals (an open jg_pnc_wave_begin wave: JG_EINVAL; allocation: JG_ENOMEM) pass through.
+ * ALL OR NOTHING: a call that returns a code other than JG_OK has changed no table, no store and no output.
+ *
+ * jg_node_create_uids — a batch of ReceivedNewObjectSyncMsg / CreateCRDTInstance, in call order.  type[i]: 0 PNCounter,
+ * 1 ORSet (the caller maps NetworkProtocol.type strings; an unregistered type string is its ArgumentException).
+ * replica: NULL, or one Guid per entry: a created PN-Counter's replica[i] is interned in the new row as jg_pnc_intern
+ * would intern it (the PNCounter() constructor's {self: 0}, PNCounters.cs:73-81; column 0 of a fresh row); ignored for
+ * ORSet entries; with NULL no column is interned.  status[i]: JG_C_CREATED, or JG_C_EXISTS when the uid is on the node
+ * already, however it got there, or is repeated earlier in the batch (the first occurrence in call order wins): then
+ * no row is consumed and nothing is interned.  idx[i] (optional) = the entry's row / set id, the existing one for
+ * JG_C_EXISTS (which may be of the other kind than type[i]).
+ * DEPARTURE (stated): the reference's objectLookupTable[uid] = crdtObject (ReplicationManager.cs:320) replaces the
+ * object of an uid created twice with an empty one; here the first creation stands.
+ * JG_EINVAL, decided before anything is written: NULL node, uid, type or status with n > 0; Guid.Empty; a type above 1;
+ * a kind whose store the node lacks; n >= 2^31 - 16; a streamed wave of the node open, or a wave holding a store.
+ * A created uid of another shard turns the shard shortcut off as jg_node_register does.  n == 0 returns JG_OK.
+ *
+ * jg_node_adopt_keys — OnNext's CreateSafeCRDT(key, guid) for journal records [from, to) of `ks` (the journal
+ * jg_keyspace_new_keys reads; to <= its length), in journal order, on the `stable` copy; the records never leave the
+ * device.  Outputs at j - from.  status:
+ *   JG_A_SKIPPED   the record's journal status is 1, 2 or 3 (no key was added);
+ *   JG_A_NO_TYPE   `prospective` holds no CRDT under the record's Guid: GetCRDTType throws KeyNotFoundException
+ *                  (ReplicationManager.cs:329).  The dictionary holds the key already, so reads and writes by that name
+ *                  answer NO_CRDT, as in the reference, until the uid is created and the range adopted again;
+ *   JG_A_HAVE      `stable` holds the Guid, or an earlier record of the range names it (two keys bound to one Guid:
+ *                  the departure stated at jg_node_query_keys): kind / idx of that entry;
+ *   JG_A_ADOPTED   the kind is read from `prospective`, a row or set id is allocated on `stable` and the uid
+ *                  registered; a PN-Counter's replica[j - from] is interned in the new row when replica is not NULL.
+ * kind (0 PNCounter, 1 ORSet) and idx are optional; a record that is neither adopted nor held gets 255 / 0xFFFFFFFF.
+ * `prospective` is only read (its pending registrations are uploaded first, as for the by-name calls).  The call may
+ * be repeated over a range: records that are JG_A_HAVE by then change nothing.
+ * JG_EINVAL as for jg_node_create_uids, and: NULL stable, prospective, ks or status; from > to or to past the journal;
+ * handles of different contexts; a kind `stable` has no store for. */
+#define JG_C_CREATED 0
+#define JG_C_EXISTS  1
+#define JG_A_ADOPTED 0
+#define JG_A_HAVE    1
+#define JG_A_NO_TYPE 2
+#define JG_A_SKIPPED 3
+int jg_node_next_idx(jg_node* node, uint32_t* next_row, uint32_t* next_set);
+int jg_node_create_uids(jg_node* node, uint64_t n, const jg_guid* uid, const uint8_t* type,
+                        const jg_guid* replica, uint64_t max_keys, uint8_t* status, uint32_t* idx);
+int jg_node_adopt_keys(jg_node* stable, jg_node* prospective, jg_keyspace* ks, uint64_t from, uint64_t to,
+                       const jg_guid* replica, uint64_t max_keys, uint8_t* status, uint8_t* kind, uint32_t* idx);
+
+/* ---------------------------------------------------------------------------------------------
  * Synthetic workloads (bench / size-independent parity): device-side counter-based generators,
  * defined in DESIGN.md §Synthetic inputs and mirrored on the host by the test oracle.
  * ------------------------------------------------------------------------------------------- */

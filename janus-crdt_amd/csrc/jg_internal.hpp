@@ -309,6 +309,10 @@ WideRows rows_wide(const jg_rows* r);
 // one doubling of R under jg_pnc_set_max_replicas' bound (false: at the bound).
 void pnc_grow(jg_pnc* p, uint64_t n_keys, uint32_t n_replicas);
 bool pnc_auto_widen(jg_pnc* p);
+// json.hip: the store's replica table, allocated on first use (pnc_table.hpp): [n_keys x R] 16-byte Guids (lo, hi) and
+// [n_keys] column counts.  For adopt.hip, which interns a created row's own replica.
+struct PncTable { unsigned long long* cols; uint32_t* ncols; uint32_t R; };
+PncTable pnc_replica_table(jg_pnc* p);
 // pnc.hip: jg_pnc_values' kernel over n device rows (d_keys NULL: rows 0..n), queued on the store's stream.  d_at /
 // d_count (query.hip): answer q into slot d_at[q], for the first *d_count rows only; an overflow is written as of_code.
 void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long* d_out, uint8_t* d_ovf, const uint32_t* d_at,

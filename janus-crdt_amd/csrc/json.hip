@@ -476,6 +476,11 @@ void pnc_node_undo(jg_pnc* p, const uint32_t* rows) {
     p->wave.scan_hi = 0;
 }
 
+PncTable pnc_replica_table(jg_pnc* p) {
+    ensure_table(p);
+    return PncTable{p->cols.as<unsigned long long>(), p->ncols.as<uint32_t>(), p->R};
+}
+
 }  // namespace jg
 
 // Device-resident wave of encoded state messages (bench / pre-staged waves).

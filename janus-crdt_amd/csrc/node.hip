@@ -21,7 +21,8 @@
 //
 // Uid table: open addressing over 32-B slots {uid lo, uid hi, type << 31 | idx}, (0, 0) = empty (Guid.Empty
 // is never a key, :134); load <= 1/2.  The library keeps the authoritative copy on the host (registration
-// is rare: key creation) and uploads the slots a registration touched before the next wave.
+// is rare: key creation) and uploads the slots a registration touched before the next wave; adopt.hip's kernels insert
+// into the device copy and hand the slots they claimed back for the host copy (node_insert_begin / _commit below).
 // Tracker: open addressing over 16-B slots {identity, origin}, 0 = empty, ~0 = removed (a tombstone:
 // concurrent probes never see an entry move); rebuilt without tombstones when live + removed pass 1/2, but never
 // while a wave is open on it (jg_tracker::waves > 0: a streamed wave keeps the table pointer, claim pointer and mask
@@ -442,6 +443,7 @@ struct jg_node {
     std::vector<UidSlot> htab;
     uint64_t n_keys = 0, n_pnc = 0, n_orset = 0;
     uint32_t max_set = 0;
+    uint32_t next_row = 0, next_set = 0;  // one past the largest row / set id registered by any path (adopt.hip allocates from them)
     jg::DevBuf dtab;
     bool upload_all = true;
     std::vector<uint32_t> dirty;
@@ -1064,6 +1066,32 @@ NodeRef node_query_ref(jg_node* nd, const char* fn) {
     return NodeRef{nd->ctx, nd->pnc, nd->orset, DevUids{nd->dtab.as<UidSlot>(), nd->htab.size() - 1}, nd->max_set};
 }
 ShipState& node_ship(jg_node* nd) { return nd->ship; }
+
+NodeInsert node_insert_begin(jg_node* nd, uint64_t n_more, const char* fn) {
+    JG_REQUIRE(!nd->run.active, JG_EINVAL, "%s: a streamed wave is open on this node (jg_apply_stream_end first)", fn);
+    require_writable(nd->pnc, fn);  // another node's streamed wave holds a shared store
+    require_writable(nd->orset, fn);
+    nd->grow(nd->n_keys + n_more);  // sized before the kernels run: an insert never meets a table more than half full
+    nd->sync_table();
+    return NodeInsert{nd->ctx, nd->pnc, nd->orset, nd->dtab.as<UidSlot>(), nd->htab.size() - 1, nd->next_row, nd->next_set};
+}
+
+void node_insert_commit(jg_node* nd, uint64_t n, const jg_guid* uid, const uint32_t* slot, const uint32_t* val) {
+    for (uint64_t i = 0; i < n; ++i) {
+        if (slot[i] == kNoSlot) continue;
+        nd->htab[slot[i]] = UidSlot{uid[i].lo, uid[i].hi, val[i], 0, 0};  // the slot the device claimed: both copies probe alike
+        const uint32_t idx = val[i] & ~kOrSetBit;
+        if (val[i] & kOrSetBit) ++nd->n_orset, nd->max_set = std::max(nd->max_set, idx), nd->next_set = std::max(nd->next_set, idx + 1);
+        else ++nd->n_pnc, nd->next_row = std::max(nd->next_row, idx + 1);
+        ++nd->n_keys;
+        if (nd->shard_world > 1 && !nd->foreign && shard_of(uid[i].lo, uid[i].hi, nd->shard_world) != nd->shard_rank) nd->foreign = true;
+    }
+}
+
+void node_next_idx(const jg_node* nd, uint32_t* next_row, uint32_t* next_set) {
+    if (next_row) *next_row = nd->next_row;
+    if (next_set) *next_set = nd->next_set;
+}
 }  // namespace jg
 
 extern "C" {
@@ -1122,8 +1150,8 @@ int jg_node_register(jg_node* nd, uint64_t n, const jg_guid* uid, const uint8_t*
         nd->grow(nd->n_keys + n);
         for (uint64_t i = 0; i < n; ++i) {
             nd->insert(UidSlot{uid[i].lo, uid[i].hi, type[i] ? (idx[i] | kOrSetBit) : idx[i], 0, 0});
-            if (type[i]) ++nd->n_orset, nd->max_set = std::max(nd->max_set, idx[i]);
-            else ++nd->n_pnc;
+            if (type[i]) ++nd->n_orset, nd->max_set = std::max(nd->max_set, idx[i]), nd->next_set = std::max(nd->next_set, idx[i] + 1);
+            else ++nd->n_pnc, nd->next_row = std::max(nd->next_row, idx[i] + 1);
             if (nd->shard_world > 1 && shard_of(uid[i].lo, uid[i].hi, nd->shard_world) != nd->shard_rank) nd->foreign = true;
         }
         nd->n_keys += n;

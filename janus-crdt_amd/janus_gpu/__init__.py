@@ -47,6 +47,7 @@ EXPORTS = [
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
     "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys", "jg_node_update_keys", "jg_node_update_keys_encode",
     "jg_node_update_keys_ship", "jg_node_shipped",
+    "jg_node_next_idx", "jg_node_create_uids", "jg_node_adopt_keys",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
     "jg_rows_set_narrow", "jg_rows_form",
@@ -179,6 +180,9 @@ _SIGS = {
     "jg_node_update_keys_ship": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _u64, _vp, _vp], C.c_int),
     "jg_node_shipped": ([_vp, _vp, _vp, _u64], C.c_int),
+    "jg_node_next_idx": ([_vp, C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
+    "jg_node_create_uids": ([_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp], C.c_int),
+    "jg_node_adopt_keys": ([_vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp], C.c_int),
     "jg_pnc_shape": ([_vp, C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
@@ -192,6 +196,9 @@ GUID_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])  # jg_guid
 # jg_node_query_keys: status[i] and kind[i]
 JG_Q_OK, JG_Q_NO_KEY, JG_Q_NO_CRDT, JG_Q_OVERFLOW, JG_Q_NO_ARG = range(5)
 Q_PNCOUNTER, Q_ORSET, Q_UNRESOLVED = 0, 1, 255
+# jg_node_create_uids / jg_node_adopt_keys: status[i]
+JG_C_CREATED, JG_C_EXISTS = 0, 1
+JG_A_ADOPTED, JG_A_HAVE, JG_A_NO_TYPE, JG_A_SKIPPED = range(4)
 
 
 class _NullElem:
@@ -1030,6 +1037,41 @@ class Node:
 
     def set_shard(self, rank: int, world: int) -> None:
         _check(load().jg_node_set_shard(self._h, rank, world))
+
+    def next_idx(self) -> tuple[int, int]:
+        """jg_node_next_idx: (the next PN-Counter row, the next set id) the node would allocate."""
+        row, st = _u32(), _u32()
+        _check(load().jg_node_next_idx(self._h, C.byref(row), C.byref(st)))
+        return row.value, st.value
+
+    @staticmethod
+    def _replicas(replica, n):
+        if replica is None:
+            return None
+        r = np.ascontiguousarray(replica, GUID_DTYPE) if isinstance(replica, np.ndarray) else np.array(replica, np.uint64).reshape(-1, 2).view(GUID_DTYPE).reshape(-1)
+        if r.size != n:
+            raise ValueError("one replica per entry")
+        return r
+
+    def create_uids(self, lo, hi, types, replica=None, max_keys: int = 0):
+        """jg_node_create_uids: a batch of ReceivedNewObjectSyncMsg, rows and set ids allocated by the node.  replica: None,
+        or one (lo, hi) per entry (a GUID_DTYPE array, or pairs).  Returns (status u8 (JG_C_*), idx u32)."""
+        g = np.empty(np.size(lo), GUID_DTYPE)
+        g["lo"], g["hi"] = lo, hi
+        t = _arr(types, np.uint8)
+        r = self._replicas(replica, g.size)
+        status, idx = np.zeros(g.size, np.uint8), np.zeros(g.size, np.uint32)
+        _check(load().jg_node_create_uids(self._h, g.size, _ptr(g), _ptr(t), _ptr(r), max_keys, _ptr(status), _ptr(idx)))
+        return status, idx
+
+    def adopt_keys(self, prospective: "Node", keyspace: "KeySpace", from_: int, to: int, replica=None, max_keys: int = 0):
+        """jg_node_adopt_keys on this (stable) copy: CreateSafeCRDT for journal records [from_, to) of the key space, the
+        kind read from `prospective`.  Returns (status u8 (JG_A_*), kind u8, idx u32)."""
+        n = max(to - from_, 0)
+        r = self._replicas(replica, n)
+        status, kind, idx = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        _check(load().jg_node_adopt_keys(self._h, prospective._h, keyspace._h, from_, to, _ptr(r), max_keys, _ptr(status), _ptr(kind), _ptr(idx)))
+        return status, kind, idx
 
     def query_keys(self, keyspace: "KeySpace", keys, elems=None, with_guid: bool = False):
         """jg_node_query_keys: "gp" / "gs" of this copy for a batch of key names, resolved on the device.  Returns
