@@ -945,6 +945,57 @@ int jg_node_update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n,
 int jg_node_shipped(jg_node* node, uint64_t* n_bytes, uint8_t* out, uint64_t cap);
 
 /* ---------------------------------------------------------------------------------------------
+ * Client batches by key name: reads in order among the writes (csrc/update.hip, csrc/pnc.hip) — additive to ABI v10.
+ * A connection's stream of commands as the reference's workloads send it: PNCWorkload draws "i" / "d" / "gp" over its
+ * keys round-robin (BenchmarkClient PNCWorkload.cs:44-59), ORSetWorkload "a" / "gp" on one key until its Clear
+ * (ORSetWorkload.cs:66-138), half of them reads, and the server runs each command to completion before the next
+ * (PNCounterCommand.cs:27-53, ORSetCommand.cs:28-69, under lock (instance)): a "gp" sees exactly the writes before it.
+ * The call behaves as if the commands ran one at a time, in batch order, on `node`: a write (cmd[i] == 0,
+ * SafeCRDT.Update, SafeCRDT.cs:39-62) as a one-command jg_node_update_keys_ship, a read (cmd[i] == 1,
+ * SafeCRDT.QueryProspective, SafeCRDT.cs:64-78) as a one-command jg_node_query_keys, with one exception: the survivors
+ * of snap == 2 are decided over the whole call as jg_node_update_keys_ship decides them (one call is one batcher batch).
+ * `node` is usually the prospective copy (either copy is accepted, and a read answers from whichever copy it is);
+ * "gs" reads do not depend on the batch and stay with jg_node_query_keys on the stable node.
+ *   Writes.    Every argument, status (JG_U_*), output, snapshot, hash, round, refusal and all-or-nothing rule is
+ *              jg_node_update_keys_ship's.  Reads are invisible to writes: deleting the reads from a batch leaves the same
+ *              stores, element table and names log, the same status / result / kind / idx / elem / guid for the writes,
+ *              the same image bytes in the same order, the same sha and the same *n_rounds.  value[i] of a write is 0.
+ *   Reads.     status[i] is a JG_Q_* code under jg_node_query_keys' rules: the key's CRDT decides, a PN-Counter key
+ *              ignores any argument, an OR-Set key with arg_flag 0 is JG_Q_NO_ARG (with 1 or 2 it reads the string or the
+ *              null element); JG_Q_NO_KEY / JG_Q_NO_CRDT as there.  kind, idx (the row or set read) and guid as for
+ *              writes; elem is the id the read addressed, JG_NULL_ELEM - 1 where no record carries one; result[i] = 0.
+ *              A read never ships (snap_off[i+1] == snap_off[i], 32 zero bytes of sha), never opens or cuts a round,
+ *              and never counts as a later command for the snap == 2 rule of either kind.  snap[i], op[i], tag_*[i] and
+ *              amount[i] of a read are ignored.
+ *   PN-Counter read.  value[i] is PNCounter.Get (PNCounters.cs:87-90) of the row as it stood before the call plus every
+ *              applied PN-Counter write j < i of this call on the same row: op 1 amounts added to the P cell at column
+ *              col, op 2 amounts to the N cell, each wrapping at the store's width, then jg_pnc_values' checked sums in
+ *              column order: JG_Q_OVERFLOW with value 0 when a prefix of either sum leaves the range.  An overflow may
+ *              appear or disappear because of an earlier write of the batch; the write is applied either way.
+ *   OR-Set read.  value[i] is ORSet.Contains(args[0]) (ORSetWrapper.cs:24-28, ORSet.cs:204-237) on the set after every
+ *              applied OR-Set write j < i of this call on the same set.  The name resolves as a Remove's does
+ *              (jg_orset_apply_ops_names): a name first Added earlier in the batch has the id that Add was issued, a
+ *              name the set never held, or dropped by a Clear and not re-added, is absent; a read interns nothing.
+ *              Membership is Remove's own test over the element's tags at that point.  A batch whose OR-Set commands
+ *              are all reads writes neither the store, the element table nor the names log.
+ * JG_EINVAL, decided from the arguments with everything untouched: jg_node_update_keys_ship's list with cmd and value
+ * added to the required pointers; a cmd[i] above 1; a read with arg_flag 3.  tag_lo / tag_hi are required only when a
+ * WRITE carries an element, amount only when a write carries an integer, op only when the batch has a write: a batch
+ * of reads only is legal with op, amount, the tags and snap NULL.  Like jg_node_update_keys_ship, and unlike
+ * jg_node_query_keys, the call is refused while a wave holds a store.
+ * An image larger than cap is held on the node and fetched with jg_node_shipped.  n == 0 as jg_node_update_keys_ship. */
+int jg_node_exec_keys(jg_node* node, jg_keyspace* ks, uint64_t n,
+                      const uint64_t* key_off, const uint8_t* key_bytes,
+                      const uint8_t* cmd,
+                      const uint8_t* op, const uint8_t* arg_flag, const int64_t* amount,
+                      const uint64_t* elem_off, const uint8_t* elem_bytes,
+                      const uint64_t* tag_lo, const uint64_t* tag_hi, uint32_t col, const uint8_t* snap,
+                      uint8_t* status, uint8_t* result, int64_t* value, uint8_t* kind, uint32_t* idx, uint32_t* elem,
+                      jg_guid* guid,
+                      uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap, uint8_t* sha,
+                      uint32_t* n_rounds);
+
+/* ---------------------------------------------------------------------------------------------
  * CRDT creation on the device (csrc/adopt.hip) — additive to ABI v10.
  * The reference creates a CRDT on its receive path: ReplicationManager.ReceivedNewObjectSyncMsg
  * (ReplicationManager.cs:310-324) records uid -> type when a ManagerMsg_Create arrives (CreateCRDTInstance), and

@@ -317,6 +317,11 @@ PncTable pnc_replica_table(jg_pnc* p);
 // d_count (query.hip): answer q into slot d_at[q], for the first *d_count rows only; an overflow is written as of_code.
 void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long* d_out, uint8_t* d_ovf, const uint32_t* d_at,
                        const unsigned long long* d_count, uint8_t of_code);
+// pnc.hip: the same in the middle of a batch (jg_node_exec_keys): read q is command d_at[q] on row d_keys[q], and the
+// cell at column col counts as cell - d_dp[d_at[q]] (P) / cell - d_dn[d_at[q]] (N), wrapping at the width: the per-command
+// rewinds PncSnap keeps in pdp / pdn.  Queued in front of the batch's adds.
+void pnc_values_at_device(jg_pnc* p, uint32_t col, const uint32_t* d_keys, uint64_t n, const long long* d_dp, const long long* d_dn, long long* d_out,
+                          uint8_t* d_ovf, const uint32_t* d_at, const unsigned long long* d_count, uint8_t of_code);
 // pnc.hip: jg_pnc_apply_ops' wrapping atomic adds over a device list (update.hip): entry i adds d_amount[i] to P (or N
 // where d_is_n[i]) at (d_row[i], col), for the first min(*d_count, n_max) entries; queued on the store's stream.  The
 // rows are the caller's to check; the column is checked here.  Writes through rw_P / rw_N.
@@ -403,8 +408,12 @@ struct PncSnap {
     uint32_t* erow;                // [n]
     long long *edp, *edn;          // [n] the row's rewind to the state right after the command (k_encode subtracts it)
     unsigned long long* eoff;      // [n + 1] the list's byte offsets
-    template <class L> void carve(L& l, uint64_t n) {
+    // NULL, or [n] each (jg_node_exec_keys): every command's own rewind by command index, kept for the batch's reads;
+    // with NULL they are temporaries of the plan
+    long long *pdp = nullptr, *pdn = nullptr;
+    template <class L> void carve(L& l, uint64_t n, bool keep_prefixes = false) {
         l.add(none, n), l.add(snap_off, n + 1), l.add(erow, n), l.add(edp, n), l.add(edn, n), l.add(eoff, n + 1);
+        if (keep_prefixes) l.add(pdp, n), l.add(pdn, n);
     }
 };
 // Step 1 reads only: per-row prefixes, the survivors of snap == 2, the encode list and its length pass.  Returns with

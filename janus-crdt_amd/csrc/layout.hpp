@@ -86,7 +86,7 @@ public:
 
 private:
     struct Item { void* target; size_t off; void (*set)(void* target, char* at); };
-    static constexpr int kMax = 32;
+    static constexpr int kMax = 40;  // (jg_node_exec_keys carves 36)
     Item items_[kMax];
     size_t end_ = 0, align_ = 1;
     int n_ = 0;

@@ -587,7 +587,8 @@ void load_group(const jg_tagrec* b, const jg_tagrec* e, std::vector<TagKey>& ord
 // set's last Clear).  Ords of the batch's records count from 0 in op order (the union puts them after
 // the store's): an Add's tag is appended to its element's HashSet (:145-149); a Remove appends the
 // element's add tags it lacks to the tombstone set, in the add set's enumeration order (UnionWith /
-// the copy constructor of addSet[item], :175-183).
+// the copy constructor of addSet[item], :175-183).  Op 4 is internal (jg_node_exec_keys' reads; the public
+// entry points refuse it): Contains at that point of the batch, answered in result[i].
 void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
                const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim = nullptr, uint64_t* rem_lim = nullptr) {
     static const bool tr = std::getenv("JANUS_TRACE_APPLY") != nullptr;
@@ -606,11 +607,20 @@ void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t*
         for (uint64_t i = 0; i < n_ops; ++i) order[i] = i;
         std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return set[a] < set[b]; });
     }
-    std::vector<unsigned long long> need;
-    for (uint64_t i = 0; i < n_ops; ++i)
-        if (op[i] == 2) need.push_back(((unsigned long long)set[i] << 32) | elem[i]);
+    // need: the elements whose stored runs are fetched.  need_w marks those a Remove touches: only they load the runs into
+    // the state the writes share, as before reads existed; an element only reads touch gets a state of its own (below), so
+    // an Add of a tag the store already holds issues the same record and ord with the read in the batch as without it
+    std::vector<unsigned long long> need, need_rm;
+    for (uint64_t i = 0; i < n_ops; ++i) {
+        if (op[i] == 2 || op[i] == 4) need.push_back(((unsigned long long)set[i] << 32) | elem[i]);
+        if (op[i] == 2) need_rm.push_back(((unsigned long long)set[i] << 32) | elem[i]);
+    }
     std::sort(need.begin(), need.end());
     need.erase(std::unique(need.begin(), need.end()), need.end());
+    const bool any_read = std::find(op, op + n_ops, (uint8_t)4) != op + n_ops;
+    std::sort(need_rm.begin(), need_rm.end());
+    need_rm.erase(std::unique(need_rm.begin(), need_rm.end()), need_rm.end());
+    const auto removed = [&](unsigned long long key) { return !any_read || std::binary_search(need_rm.begin(), need_rm.end(), key); };
     if (tr) tp[1] = now();
     const Runs runs = fetch_runs(s, need);
     if (tr) tp[2] = now();
@@ -636,7 +646,7 @@ void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t*
     auto one_group = [&](size_t q) {
         const uint64_t g = gbeg[q], h = gbeg[q + 1];
         const uint32_t sid = set[order[g]];
-        std::unordered_map<uint32_t, ElemState> st;
+        std::unordered_map<uint32_t, ElemState> st, rd;  // rd: the elements only reads (and Adds) touch, as the reads see them
         bool was_cleared = false;
         std::vector<jg_tagrec>& sa = ga[q];
         std::vector<jg_tagrec>& sr = gr[q];
@@ -647,12 +657,27 @@ void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t*
             ElemState es;
             const unsigned long long key = ((unsigned long long)sid << 32) | e;
             auto nk = std::lower_bound(need.begin(), need.end(), key);
-            if (!was_cleared && nk != need.end() && *nk == key) {
+            if (!was_cleared && nk != need.end() && *nk == key && removed(key)) {
                 const size_t k = nk - need.begin();
                 load_group(runs.add.data() + runs.add_off[k], runs.add.data() + runs.add_off[k + 1], es.add, es.add_has);
                 load_group(runs.rem.data() + runs.rem_off[k], runs.rem.data() + runs.rem_off[k + 1], es.rem, es.rem_has);
             }
             return st.emplace(e, std::move(es)).first->second;
+        };
+        // a read's view of an element no Remove of the batch touches: the stored runs plus the batch's Adds so far
+        auto read_state = [&](uint32_t e) -> ElemState* {
+            const unsigned long long key = ((unsigned long long)sid << 32) | e;
+            auto nk = std::lower_bound(need.begin(), need.end(), key);
+            if (nk == need.end() || *nk != key) return nullptr;  // no read of the batch asks for it
+            auto it = rd.find(e);
+            if (it != rd.end()) return &it->second;
+            ElemState es;
+            if (!was_cleared) {
+                const size_t k = nk - need.begin();
+                load_group(runs.add.data() + runs.add_off[k], runs.add.data() + runs.add_off[k + 1], es.add, es.add_has);
+                load_group(runs.rem.data() + runs.rem_off[k], runs.rem.data() + runs.rem_off[k + 1], es.rem, es.rem_has);
+            }
+            return &rd.emplace(e, std::move(es)).first->second;
         };
         for (uint64_t x = g; x < h; ++x) {
             const uint64_t i = order[x];
@@ -664,6 +689,8 @@ void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t*
                     es.add.push_back(t);
                     sa.push_back(jg_tagrec{key, t.first, t.second, next_a++});
                 }
+                if (any_read && !removed(key))
+                    if (ElemState* v = read_state(elem[i])) v->add_has.insert(t);
                 result[i] = 1;
             } else if (op[i] == 2) {  // Remove: if Contains, tombstone every observed tag (ORSet.cs:161-186)
                 ElemState& es = state(elem[i]);
@@ -676,7 +703,13 @@ void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t*
                             sr.push_back(jg_tagrec{key, t.first, t.second, next_r++});
                         }
                 result[i] = present ? 1 : 0;
+            } else if (op[i] == 4) {  // Contains (ORSet.cs:204-237): Remove's test and nothing else; no record, no ord
+                const ElemState& es = removed(key) ? state(elem[i]) : *read_state(elem[i]);
+                const bool present = elem[i] == JG_NULL_ELEM ? es.add_has != es.rem_has
+                                                             : !es.add_has.empty() && (es.rem_has.empty() || es.add_has != es.rem_has);
+                result[i] = present ? 1 : 0;
             } else {  // Clear (ORSet.cs:192-198)
+                rd.clear();
                 st.clear();
                 sa.clear();
                 sr.clear();

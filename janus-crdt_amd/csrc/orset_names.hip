@@ -23,6 +23,8 @@
 //             k_nm_ids     every op's id: the resident id, or the new name's id from its first Add onward, else
 //                          JG_NULL_ELEM - 1.  The ids (4 B per op) go to the host for the record side
 //                          (jg_orset_apply_ops' walk and union), which runs BEFORE the table changes.
+//                          Op 4 (internal: a read inside a batch, jg_node_exec_keys) is resolved as a Remove: it
+//                          claims nothing and interns nothing.
 //             k_nm_put     appends the winners to the names log with gen = set_gen[set] + epoch; k_nm_sets then
 //                          advances next_id and set_gen.
 #include <hipcub/hipcub.hpp>
@@ -653,7 +655,7 @@ int jg_orset_lookup_all_names(jg_orset* s, uint64_t n, const uint32_t* set, uint
 // jg_orset_apply_ops_names under the context lock, for it and for update.hip (the OR-Set commands of a batch by key).
 void jg::orset_apply_ops_names_locked(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint8_t* op, const uint64_t* off, const uint8_t* bytes,
                                       const uint8_t* is_null, const uint64_t* tag_lo, const uint64_t* tag_hi, uint8_t* result, uint32_t* elem_out,
-                                      uint64_t* add_lim, uint64_t* rem_lim) {
+                                      uint64_t* add_lim, uint64_t* rem_lim, bool reads) {
     jg::require_writable(s, "jg_orset_apply_ops_names");
     JG_REQUIRE(s, JG_EINVAL, "jg_orset_apply_ops_names: store is NULL");
     if (n_ops == 0) return;
@@ -663,8 +665,8 @@ void jg::orset_apply_ops_names_locked(jg_orset* s, uint64_t n_ops, const uint32_
     JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_orset_apply_ops_names: at most 2^31 ops per call");
     const uint64_t n_sets = check_names("jg_orset_apply_ops_names", n, set, off, bytes, is_null);
     for (uint64_t i = 0; i < n; ++i)
-        JG_REQUIRE(op[i] >= 1 && op[i] <= 3, JG_EINVAL, "jg_orset_apply_ops_names: op[%llu] = %u is not 1 (Add), 2 (Remove) or 3 (Clear)",
-                   (unsigned long long)i, op[i]);
+        JG_REQUIRE(op[i] >= 1 && (op[i] <= 3 || (reads && op[i] == 4)), JG_EINVAL,
+                   "jg_orset_apply_ops_names: op[%llu] = %u is not 1 (Add), 2 (Remove) or 3 (Clear)", (unsigned long long)i, op[i]);
     jg_ctx* ctx = s->ctx;
     jg::ensure_device(ctx);
     jg::sync_counts(s);
@@ -797,7 +799,7 @@ int jg_orset_apply_ops_names(jg_orset* s, uint64_t n_ops, const uint32_t* set, c
                              uint64_t* add_lim, uint64_t* rem_lim) {
     return jg::guard([&] {
         auto lk_ = jg::lock(s);
-        jg::orset_apply_ops_names_locked(s, n_ops, set, op, off, bytes, is_null, tag_lo, tag_hi, result, elem_out, add_lim, rem_lim);
+        jg::orset_apply_ops_names_locked(s, n_ops, set, op, off, bytes, is_null, tag_lo, tag_hi, result, elem_out, add_lim, rem_lim, false);
     });
 }
 

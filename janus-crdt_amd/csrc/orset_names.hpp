@@ -142,8 +142,10 @@ struct ElemTable {
 ElemTable* orset_elem_table(jg_orset* s, bool create);
 bool orset_wave_open(const jg_orset* s);
 // orset_names.hip: jg_orset_apply_ops_names without its lock and guard (the caller holds the context's lock and
-// converts the errors), for update.hip.  Arguments, effects and refusals are that entry point's.
+// converts the errors), for update.hip.  Arguments, effects and refusals are that entry point's.  reads: op 4 is allowed,
+// Contains of the name at that point of the batch (result[i]): it resolves as a Remove, interns nothing, appends no
+// record and moves no ord; a batch of reads only writes neither the store nor the table.
 void orset_apply_ops_names_locked(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint8_t* op, const uint64_t* off, const uint8_t* bytes,
                                   const uint8_t* is_null, const uint64_t* tag_lo, const uint64_t* tag_hi, uint8_t* result, uint32_t* elem_out,
-                                  uint64_t* add_lim, uint64_t* rem_lim);
+                                  uint64_t* add_lim, uint64_t* rem_lim, bool reads = false);
 }  // namespace jg

@@ -209,16 +209,16 @@ __device__ __forceinline__ __int128 shfl_acc(__int128 v, int src) {
     return ((__int128)hi << 64) | (unsigned long long)lo;
 }
 
-// Returns the exact sum of row[0..R); sets `of` if any prefix leaves T's range.
-template <int EB>
-__device__ __forceinline__ typename Acc<EB>::T checked_row_sum(const typename Elem<EB>::T* row, uint32_t R, int lane, bool& of) {
+// Returns the exact sum of cell(0) .. cell(R - 1); sets `of` if any prefix leaves T's range.
+template <int EB, class Cell>
+__device__ __forceinline__ typename Acc<EB>::T checked_sum_of(Cell cell, uint32_t R, int lane, bool& of) {
     using T = typename Elem<EB>::T;
     using A = typename Acc<EB>::T;
     const A lo = EB == 4 ? (A)INT32_MIN : (A)INT64_MIN;
     const A hi = EB == 4 ? (A)INT32_MAX : (A)INT64_MAX;
     A carry = 0;
     for (uint32_t c0 = 0; c0 < R; c0 += 64) {
-        A x = (c0 + lane < R) ? (A)row[c0 + lane] : (A)0;
+        A x = (c0 + lane < R) ? (A)cell(c0 + lane) : (A)0;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             A y = shfl_up_acc(x, d);
@@ -230,6 +230,12 @@ __device__ __forceinline__ typename Acc<EB>::T checked_row_sum(const typename El
     }
     (void)sizeof(T);
     return carry;
+}
+
+// ... of row[0..R)
+template <int EB>
+__device__ __forceinline__ typename Acc<EB>::T checked_row_sum(const typename Elem<EB>::T* row, uint32_t R, int lane, bool& of) {
+    return checked_sum_of<EB>([row](uint32_t c) { return row[c]; }, R, lane, of);
 }
 
 // at / count / of_code serve the reads by key name (query.hip): answer q goes to slot at[q] (NULL: q), only the
@@ -256,6 +262,40 @@ __global__ __launch_bounds__(kBlock) void k_values(const typename Elem<EB>::T* _
             // ΣP and ΣN are in range when !of; '-' is unchecked: wrap at the width.
             const T v = (T)((UT)(T)sp - (UT)(T)sn);
             const uint64_t o = at ? at[q] : q;
+            out[o] = of ? 0 : (long long)v;
+            ovf[o] = of ? of_code : 0;
+        }
+    }
+}
+
+// PNCounter.Get in the middle of a batch (jg_node_exec_keys, update.hip): one wave per read, k_values'
+// checked sums over the row with the cell at column `col` replaced by cell + the amounts the batch's earlier commands
+// added to it, wrapping at the width as Increment / Decrement do.  Read q is command at[q] on row keys[q]; dp / dn hold,
+// by command index, MINUS the amounts on P / N of the row's commands up to and including that command
+// (pnc_encode.hip k_prefix_scatter's rewinds; a read adds 0).  It runs in front of k_add_list, so the rows are those
+// from before the call.  keys / count / of_code as for k_values; at is required.
+template <int EB>
+__global__ __launch_bounds__(kBlock) void k_values_at(const typename Elem<EB>::T* __restrict__ P, const typename Elem<EB>::T* __restrict__ N,
+                                                      uint32_t R, uint32_t col, const uint32_t* __restrict__ keys, uint64_t n,
+                                                      const long long* __restrict__ dp, const long long* __restrict__ dn,
+                                                      long long* __restrict__ out, uint8_t* __restrict__ ovf,
+                                                      const uint32_t* __restrict__ at, const unsigned long long* __restrict__ count,
+                                                      uint8_t of_code) {
+    using T = typename Elem<EB>::T;
+    using UT = std::make_unsigned_t<T>;
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    if (count && *count < n) n = *count;
+    for (uint64_t q = wave; q < n; q += n_waves) {
+        const uint64_t k = keys[q], o = at[q];
+        const T *rp = P + k * R, *rn = N + k * R;
+        const UT ap = (UT)(0ull - (unsigned long long)dp[o]), an = (UT)(0ull - (unsigned long long)dn[o]);
+        bool of = false;
+        const auto sp = checked_sum_of<EB>([=](uint32_t c) { return c == col ? (T)((UT)rp[c] + ap) : rp[c]; }, R, lane, of);
+        const auto sn = checked_sum_of<EB>([=](uint32_t c) { return c == col ? (T)((UT)rn[c] + an) : rn[c]; }, R, lane, of);
+        if (lane == 0) {
+            const T v = (T)((UT)(T)sp - (UT)(T)sn);
             out[o] = of ? 0 : (long long)v;
             ovf[o] = of ? of_code : 0;
         }
@@ -627,6 +667,19 @@ void pnc_values_device(jg_pnc* p, const uint32_t* d_keys, uint64_t n, long long*
         using T = typename Elem<EB()>::T;
         hipLaunchKernelGGL(k_values<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const T*)p->ro_P(), (const T*)p->ro_N(), p->R, d_keys, n, d_out,
                            d_ovf, d_at, d_count, of_code);
+    });
+    JG_HIP(hipGetLastError());
+}
+
+void pnc_values_at_device(jg_pnc* p, uint32_t col, const uint32_t* d_keys, uint64_t n, const long long* d_dp, const long long* d_dn, long long* d_out,
+                          uint8_t* d_ovf, const uint32_t* d_at, const unsigned long long* d_count, uint8_t of_code) {
+    jg_ctx* ctx = p->ctx;
+    JG_REQUIRE(col < p->R, JG_EINVAL, "pnc_values_at_device: column %u outside the store's %u", col, p->R);
+    const unsigned grid = jg::grid_for(ctx, n * 64, kBlock, 16);
+    dispatch_eb(p->eb, [&](auto EB) {
+        using T = typename Elem<EB()>::T;
+        hipLaunchKernelGGL(k_values_at<EB()>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const T*)p->ro_P(), (const T*)p->ro_N(), p->R, col, d_keys, n,
+                           d_dp, d_dn, d_out, d_ovf, d_at, d_count, of_code);
     });
     JG_HIP(hipGetLastError());
 }

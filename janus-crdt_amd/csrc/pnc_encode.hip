@@ -398,8 +398,10 @@ void pnc_snap_plan_locked(jg_pnc* p, const PncSnap& s, uint64_t n, uint32_t col,
     uint8_t* dtmp;
     jg::Layout A;
     A.add(keys, n), A.add(vals, n), A.add(excl, n), A.add(seg, n), A.add(mark, n), A.add(head, n), A.add(latest, n), A.add(take, n + 1), A.add(pos, n + 1);
-    A.add(ddp, n), A.add(ddn, n), A.add(len, n + 1), A.add(dtmp, t_all + 256);
+    if (!s.pdp) A.add(ddp, n), A.add(ddn, n);
+    A.add(len, n + 1), A.add(dtmp, t_all + 256);
     A.bind(jg::scratch(ctx, ctx->scratch, A.bytes()));
+    if (s.pdp) ddp = s.pdp, ddn = s.pdn;  // kept by the caller for the batch's reads
     const auto tmp = jg::cub_in(dtmp, t_all);
     const unsigned g = blocks_for(n);
     // each command's amounts up to and including it on its row, in batch order (the commands without a row add 0 to a

@@ -1,6 +1,7 @@
 // update.hip — client writes by key name, resolved on the device: jg_node_update_keys, the same call
 // shipping the PN-Counter snapshots SafeCRDT.Update sends next: jg_node_update_keys_encode, and the same
-// call shipping every kind's snapshots in one image: jg_node_update_keys_ship, jg_node_shipped.
+// call shipping every kind's snapshots in one image: jg_node_update_keys_ship, jg_node_shipped, and that
+// call with "gp" reads in order among the writes: jg_node_exec_keys.
 //
 // The reference's "i" / "d" / "a" / "r" / "c" commands (CRDTCommands/PNCounterCommand.cs:42-53, ORSetCommand.cs:43-61) go
 // KeySpaceManager.GetKVPair -> SafeCRDT.Update (SafeCRDT.cs:39-47) -> prospectiveState.Update(operationID, args) in
@@ -32,6 +33,15 @@
 //                (orset_encode.hip's two phases), and ship_move.hpp's mover merges the regions and the PN-Counter list
 //                into one image in command order, which is hashed, copied out once (or held on the node) and followed
 //                by the adds.
+//
+//   reads        (jg_node_exec_keys only; PNCounterCommand.cs:27-41, ORSetCommand.cs:28-42 between the writes of
+//                PNCWorkload.cs:44-59 / ORSetWorkload.cs:66-138) k_x_resolve is the same chain with the command kind: a read
+//                gets k_q_resolve's statuses, a resolved PN-Counter read enters the per-command arrays on its row with
+//                amount 0 and snap 0, so §14's per-row prefixes give it exactly the writes before it and it ships nothing,
+//                and each wave appends it to a read list (one ballot, one atomic).  pnc.hip's k_values_at answers the list
+//                in front of the adds: Get's checked sums over the row as it stood, with the cell at `col` moved by the
+//                prefix.  A resolved OR-Set read rides with the OR-Set commands as the internal op 4 (Contains): Remove's
+//                name resolution and membership test in apply_ops' walk, no record, no ord, no round.
 //
 // The resolve is a dependent chain of random lines: the kernel waits on memory, uses no LDS and few registers, so
 // occupancy is what hides the latency.  Nothing is published inside a launch: the kernel boundaries publish the list
@@ -76,11 +86,23 @@ struct UOut {
     uint8_t* eisn;
 };
 
-template <bool ORDERED>
-__global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D, jg::DevUids U, uint64_t pnc_rows, bool has_orset, UIn in, uint64_t n,
-                                                      UOut o) {
+// jg_node_exec_keys only: which commands are reads, and what the resolve writes for them
+struct URd {
+    const uint8_t* cmd;  // 0 = write | 1 = read
+    long long* value;    // [n] zeroed here; the reads' answers land in it
+    uint8_t* ovf;        // [n] zeroed here; k_values_at's overflow byte by command index
+    uint32_t *rrow, *rat;  // resolved PN-Counter reads: row, command index
+    ull* rcount;         // their number (zeroed before the launch)
+};
+
+// READS: a command with cmd 1 is a read.  It gets jg_node_query_keys' statuses; a resolved PN-Counter read enters the
+// per-command arrays on its row with amount 0 (so its prefix is the writes before it) and the read list, not the add
+// list; a resolved OR-Set read is marked OK for the OR-Set side like a write.
+template <bool ORDERED, bool READS>
+__device__ __forceinline__ void u_resolve(const jgt::Store& S, const jgt::Dict& D, const jg::DevUids& U, uint64_t pnc_rows, bool has_orset, const UIn& in,
+                                          uint64_t n, const UOut& o, const URd& rd) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    bool is_p = false;
+    bool is_p = false, is_r = false;
     uint32_t row = 0;
     long long amt = 0;
     uint8_t isn = 0;
@@ -95,7 +117,21 @@ __global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D,
             glo = D.glo[d], ghi = D.ghi[d];
             const uint32_t v = (glo | ghi) != 0 ? jg::uid_find(U, glo, ghi) : jg::kNoSlot;
             const uint32_t op = in.op[i], flag = in.flag[i];
-            if (v == jg::kNoSlot) {
+            if (READS && rd.cmd[i]) {  // JG_Q_* (query.hip k_q_resolve's rules)
+                if (v == jg::kNoSlot) {
+                    st = JG_Q_NO_CRDT;
+                } else if (!(v & jg::kOrSetBit)) {
+                    kd = 0;
+                    is_r = v < pnc_rows;
+                    st = is_r ? JG_Q_OK : JG_Q_NO_CRDT;
+                    if (is_r) ix = row = v;
+                } else {
+                    kd = 1;
+                    if (!has_orset) st = JG_Q_NO_CRDT;
+                    else if (flag == 0) st = JG_Q_NO_ARG;
+                    else st = JG_Q_OK, ix = v & ~jg::kOrSetBit;
+                }
+            } else if (v == jg::kNoSlot) {
                 st = JG_U_NO_CRDT;
             } else if (!(v & jg::kOrSetBit)) {
                 kd = 0;
@@ -124,10 +160,27 @@ __global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D,
         o.kind[i] = kd;
         o.idx[i] = ix;
         if (o.guid) o.guid[i] = jg_guid{glo, ghi};
-        if constexpr (ORDERED) o.erow[i] = is_p ? row : (uint32_t)pnc_rows, o.eamt[i] = amt, o.eisn[i] = isn;
+        if constexpr (ORDERED) o.erow[i] = is_p || is_r ? row : (uint32_t)pnc_rows, o.eamt[i] = amt, o.eisn[i] = isn;
+        if constexpr (READS) rd.value[i] = 0, rd.ovf[i] = 0;
     }
     const ull sp = jg::wave_append(is_p, o.count);
     if (is_p) o.prow[sp] = row, o.pamt[sp] = amt, o.pisn[sp] = isn;
+    if constexpr (READS) {
+        const ull sr = jg::wave_append(is_r, rd.rcount);
+        if (is_r) rd.rrow[sr] = row, rd.rat[sr] = (uint32_t)i;
+    }
+}
+
+template <bool ORDERED>
+__global__ __launch_bounds__(kBlock) void k_u_resolve(jgt::Store S, jgt::Dict D, jg::DevUids U, uint64_t pnc_rows, bool has_orset, UIn in, uint64_t n,
+                                                      UOut o) {
+    u_resolve<ORDERED, false>(S, D, U, pnc_rows, has_orset, in, n, o, URd{});
+}
+
+// jg_node_exec_keys' resolve: the same chain with the reads among the writes
+__global__ __launch_bounds__(kBlock) void k_x_resolve(jgt::Store S, jgt::Dict D, jg::DevUids U, uint64_t pnc_rows, bool has_orset, UIn in, uint64_t n,
+                                                      UOut o, URd rd) {
+    u_resolve<true, true>(S, D, U, pnc_rows, has_orset, in, n, o, rd);
 }
 
 void check_offsets(const char* what, uint64_t n, const uint64_t* off) {
@@ -138,12 +191,14 @@ void check_offsets(const char* what, uint64_t n, const uint64_t* off) {
     JG_REQUIRE(off[n] < (1ull << 40), JG_EINVAL, "jg_node_update_keys: batch too large");
 }
 
-// What every entry point of this file refuses from the arguments alone (n > 0), and how many commands carry each flag.
+// What every entry point of this file refuses from the arguments alone (n > 0), and how many writes carry each flag.
+// cmd (jg_node_exec_keys; NULL: every command is a write) marks the reads: a read may carry no integer, needs no op, no
+// amount and no tag, and a batch of reads only may leave op NULL.
 struct FlagCounts { uint64_t n[4]; };
 FlagCounts check_batch(const jg_node* node, const jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
                        const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
-                       const uint64_t* tag_hi, const uint8_t* status, const uint8_t* result) {
-    JG_REQUIRE(node && ks && op && arg_flag && status && result, JG_EINVAL, "jg_node_update_keys: NULL argument");
+                       const uint64_t* tag_hi, const uint8_t* status, const uint8_t* result, const uint8_t* cmd = nullptr) {
+    JG_REQUIRE(node && ks && (op || cmd) && arg_flag && status && result, JG_EINVAL, "jg_node_update_keys: NULL argument");
     JG_REQUIRE(jg::node_ctx(node) == ks->ctx, JG_EINVAL, "jg_node_update_keys: the key space and the node belong to different contexts");
     JG_REQUIRE(n < 0x7FFFFFF0ull, JG_EINVAL, "jg_node_update_keys: at most 2^31 commands per call");
     JG_REQUIRE(key_off, JG_EINVAL, "jg_node_update_keys: key_off is NULL");
@@ -151,12 +206,21 @@ FlagCounts check_batch(const jg_node* node, const jg_keyspace* ks, uint64_t n, c
     JG_REQUIRE(key_off[n] == 0 || key_bytes, JG_EINVAL, "jg_node_update_keys: key_bytes is NULL");
     if (elem_off) check_offsets("elem", n, elem_off);
     FlagCounts c{{0, 0, 0, 0}};
+    uint64_t n_str = 0, n_write = 0;
     for (uint64_t i = 0; i < n; ++i) {
         JG_REQUIRE(arg_flag[i] <= 3, JG_EINVAL, "jg_node_update_keys: arg_flag[%llu] = %u (0 none, 1 string, 2 null, 3 integer)", (ull)i, arg_flag[i]);
+        n_str += arg_flag[i] == 1;
+        if (cmd) {
+            JG_REQUIRE(cmd[i] <= 1, JG_EINVAL, "jg_node_exec_keys: cmd[%llu] = %u (0 write, 1 read)", (ull)i, cmd[i]);
+            JG_REQUIRE(!cmd[i] || arg_flag[i] != 3, JG_EINVAL, "jg_node_exec_keys: read %llu carries an integer", (ull)i);
+            if (cmd[i]) continue;
+        }
+        ++n_write;
         ++c.n[arg_flag[i]];
     }
+    JG_REQUIRE(n_write == 0 || op, JG_EINVAL, "jg_node_update_keys: NULL argument");
     JG_REQUIRE(c.n[3] == 0 || amount, JG_EINVAL, "jg_node_update_keys: a command carries an integer and amount is NULL");
-    JG_REQUIRE(c.n[1] == 0 || (elem_off && elem_bytes), JG_EINVAL, "jg_node_update_keys: a command carries a string and elem_off or elem_bytes is NULL");
+    JG_REQUIRE(n_str == 0 || (elem_off && elem_bytes), JG_EINVAL, "jg_node_update_keys: a command carries a string and elem_off or elem_bytes is NULL");
     JG_REQUIRE(c.n[1] + c.n[2] == 0 || (tag_lo && tag_hi), JG_EINVAL, "jg_node_update_keys: a command carries an element and tag_lo or tag_hi is NULL");
     return c;
 }
@@ -375,10 +439,18 @@ __global__ __launch_bounds__(kBlock) void k_u_ship_obj(const uint8_t* __restrict
     if (i < n) obj[i] = status[i] == JG_U_OK && kind[i] == 1 ? idx[i] : none_obj;
 }
 
+// jg_node_exec_keys' two arguments more; NULL: jg_node_update_keys_ship, which launches and answers as
+// it did before the other existed
+struct Exec {
+    const uint8_t* cmd;  // 0 = write | 1 = read
+    int64_t* value;      // the reads' answers, 0 for every other command
+};
+
 int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* op,
                      const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
                      const uint64_t* tag_hi, uint32_t col, const uint8_t* snap, uint8_t* status, uint8_t* result, uint8_t* kind, uint32_t* idx,
-                     uint32_t* elem, jg_guid* guid, uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap, uint8_t* sha, uint32_t* n_rounds) {
+                     uint32_t* elem, jg_guid* guid, uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap, uint8_t* sha, uint32_t* n_rounds,
+                     const Exec* ex = nullptr) {
     return jg::guard([&] {
         auto lk_ = jg::lock(ks);
         JG_REQUIRE(snap_off && n_bytes, JG_EINVAL, "jg_node_update_keys_ship: snap_off or n_bytes is NULL");
@@ -388,9 +460,16 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
             return;
         }
         // every refusal below is decided from the arguments: nothing has been copied or written yet
-        const FlagCounts n_flag = check_batch(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, status, result);
+        JG_REQUIRE(!ex || (ex->cmd && ex->value), JG_EINVAL, "jg_node_exec_keys: cmd or value is NULL");
+        const uint8_t* cmd = ex ? ex->cmd : nullptr;
+        const FlagCounts n_flag =
+            check_batch(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, status, result, cmd);
+        const auto reads = [&](uint64_t i) { return cmd && cmd[i]; };
+        uint64_t n_reads = 0;
+        for (uint64_t i = 0; cmd && i < n; ++i) n_reads += cmd[i];
         for (uint64_t i = 0; snap && i < n; ++i)
-            JG_REQUIRE(snap[i] <= 2, JG_EINVAL, "jg_node_update_keys_ship: snap[%llu] = %u (0 none, 1 this command's, 2 the latest)", (ull)i, snap[i]);
+            JG_REQUIRE(reads(i) || snap[i] <= 2, JG_EINVAL, "jg_node_update_keys_ship: snap[%llu] = %u (0 none, 1 this command's, 2 the latest)", (ull)i,
+                       snap[i]);
         JG_REQUIRE(out || cap == 0, JG_EINVAL, "jg_node_update_keys_ship: out is NULL and cap is not 0");
         jg_ctx* ctx = ks->ctx;
         jg::ensure_device(ctx);
@@ -405,27 +484,38 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
         // the batch as jg_node_update_keys_encode stages it, and behind it what only this call needs: the OR-Set objects,
         // their no-snapshot flags, and the mover's list (source address, merged offset, merged no-snapshot flag)
         const uint64_t kb = key_off[n];
-        const bool ints = n_flag.n[3] != 0, snaps = snap != nullptr, plan = nd.pnc != nullptr;
+        // with reads the snap bytes are always staged: a read's is 0, so it ships nothing and, in snap_survivors.hpp's
+        // rule, never stands for a later snap == 2 command of its object
+        const bool ints = n_flag.n[3] != 0, snaps = snap != nullptr || ex, plan = nd.pnc != nullptr;
         UIn in{};
         UOut o{};
+        URd rd{};
         jg::Layout L;
         L.add(in.koff, n + 1, 8), L.add(in.amount, ints ? n : 0, 8), L.add(in.kbytes, kb, 8), L.add(in.op, n, 1), L.add(in.flag, n, 1);
         L.add(in.snap, snaps ? n : 0, 1);
+        if (ex) L.add(rd.cmd, n, 1);
         const size_t stage = L.skip(0, 8);
         std::vector<uint8_t> h(stage);
         L.bind(h.data());
         std::memcpy(h.data(), key_off, (n + 1) * 8);
         if (ints) std::memcpy(const_cast<long long*>(in.amount), amount, n * 8);
         if (kb) std::memcpy(const_cast<uint8_t*>(in.kbytes), key_bytes, kb);
-        std::memcpy(const_cast<uint8_t*>(in.op), op, n);
+        if (op) std::memcpy(const_cast<uint8_t*>(in.op), op, n);  // (NULL: a batch of reads, the bytes stay 0)
         std::memcpy(const_cast<uint8_t*>(in.flag), arg_flag, n);
-        if (snaps) std::memcpy(const_cast<uint8_t*>(in.snap), snap, n);
+        if (snap) std::memcpy(const_cast<uint8_t*>(in.snap), snap, n);
+        if (ex) {
+            auto* hs = const_cast<uint8_t*>(in.snap);
+            std::memcpy(const_cast<uint8_t*>(rd.cmd), cmd, n);
+            for (uint64_t i = 0; i < n; ++i) hs[i] = cmd[i] ? 0 : snap ? snap[i] : 1;
+        }
         L.skip(16);
         L.add(o.count, 1, 8), L.add(o.guid, guid ? n : 0, 8), L.add(o.pamt, n, 8), L.add(o.prow, n, 4);
         L.add(o.idx, n, 4), L.add(o.status, n, 1), L.add(o.kind, n, 1), L.add(o.pisn, n, 1);
         jg::PncSnap sn{};
         L.add(o.eamt, n, 8), L.add(o.erow, n, 4), L.add(o.eisn, n, 1);
-        if (plan) sn.carve(L, n);
+        if (plan) sn.carve(L, n, ex != nullptr);
+        // the reads' answers and, for the PN-Counter reads, their list: value | rcount | rrow | rat | ovf
+        if (ex) L.add(rd.value, n, 8), L.add(rd.rcount, 1, 8), L.add(rd.rrow, n, 4), L.add(rd.rat, n, 4), L.add(rd.ovf, n, 1);
         uint32_t* oobj;
         uint8_t *onone, *mlist;
         ull *msrc, *moff;
@@ -459,8 +549,14 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
 
         JG_HIP(hipMemcpyAsync(d, h.data(), stage, hipMemcpyHostToDevice, ctx->stream));
         JG_HIP(hipMemsetAsync(o.count, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_u_resolve<true>, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
-                           nd.pnc ? nd.pnc->n_keys : 0, nd.orset != nullptr, in, n, o);
+        if (ex) {
+            JG_HIP(hipMemsetAsync(rd.rcount, 0, 8, ctx->stream));
+            hipLaunchKernelGGL(k_x_resolve, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
+                               nd.pnc ? nd.pnc->n_keys : 0, nd.orset != nullptr, in, n, o, rd);
+        } else {
+            hipLaunchKernelGGL(k_u_resolve<true>, dim3(jg::blocks_for(n)), dim3(kBlock), 0, ctx->stream, ks->set->view(), ks->dict(), nd.uids,
+                               nd.pnc ? nd.pnc->n_keys : 0, nd.orset != nullptr, in, n, o);
+        }
         JG_HIP(hipGetLastError());
         std::vector<uint8_t> hres(n * 6), hnone(n, 1);
         const auto* h_idx = reinterpret_cast<const uint32_t*>(hres.data());
@@ -507,8 +603,16 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
         for (uint64_t i = 0; i < n; ++i)
             if (h_status[i] == JG_U_OK && h_kind[i] == 1) at.push_back((uint32_t)i);
         const uint64_t n_o = nd.orset ? at.size() : 0;
+        // a read among them (status and kind say the same for both) runs as the internal op 4, Contains: it takes the round
+        // current for its set, opens and cuts none, and is not counted in *n_rounds
+        std::vector<uint8_t> eop_v;
+        if (ex) {
+            eop_v.resize(n);
+            for (uint64_t i = 0; i < n; ++i) eop_v[i] = cmd[i] ? 4 : op[i];
+        }
+        const uint8_t* eop = ex ? eop_v.data() : op;
         std::vector<uint32_t> round(n_o, 0);
-        uint32_t rounds = n_o ? 1 : 0;
+        uint32_t rounds = 0;
         uint64_t max_adds = 0;
         std::vector<uint32_t> ship_sets;
         if (n_o) {
@@ -517,16 +621,17 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
             for (uint64_t k = 0; k < n_o; ++k) {
                 const uint32_t i = at[k];
                 PerSet& ps = per[h_idx[i]];
-                if (op[i] == 3 && ps.open) ++ps.round, ps.open = false;
+                if (eop[i] == 3 && ps.open) ++ps.round, ps.open = false;
                 round[k] = ps.round;
-                rounds = std::max(rounds, ps.round + 1);
+                if (eop[i] != 4) rounds = std::max(rounds, ps.round + 1);
                 if (!hnone[i]) {
                     if (!ps.ships) ship_sets.push_back(h_idx[i]);
                     ps.open = ps.ships = true;
                 }
-                if (op[i] == 1 && arg_flag[i] == 1) max_adds = std::max<uint64_t>(max_adds, ++ps.adds);
+                if (eop[i] == 1 && arg_flag[i] == 1) max_adds = std::max<uint64_t>(max_adds, ++ps.adds);
             }
         }
+        const uint32_t passes = std::max<uint32_t>(rounds, n_o ? 1 : 0);  // a batch whose OR-Set commands are all reads: one pass, no round
         // refusals that need the stores, still before anything is written: a shipping set with a record whose element id has
         // no name (the encoder's size phase, without limits, over the distinct shipping sets), and a batch of several rounds
         // that could run a set out of element ids in a later round
@@ -550,29 +655,31 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
         std::vector<uint8_t> res(n, 0);
         std::vector<uint32_t> el(elem ? n : 0, kNever);
         std::vector<uint64_t> len(n, 0), src(n, 0);
-        for (uint32_t r = 0; r < rounds; ++r) {
-            std::vector<uint32_t> cmd, oset, oel;
+        std::vector<int64_t> val(ex ? n : 0, 0);
+        for (uint32_t r = 0; r < passes; ++r) {
+            std::vector<uint32_t> rcmd, oset, oel;
             std::vector<uint8_t> oop, onull, ores, obytes;
             std::vector<uint64_t> ooff{0}, olo, ohi;
             for (uint64_t k = 0; k < n_o; ++k) {
                 if (round[k] != r) continue;
                 const uint32_t i = at[k];
-                cmd.push_back(i), oset.push_back(h_idx[i]), oop.push_back(op[i]), onull.push_back(op[i] != 3 && arg_flag[i] == 2);
-                olo.push_back(tag_lo ? tag_lo[i] : 0), ohi.push_back(tag_hi ? tag_hi[i] : 0);
-                if (op[i] != 3 && arg_flag[i] == 1) obytes.insert(obytes.end(), elem_bytes + elem_off[i], elem_bytes + elem_off[i + 1]);
+                rcmd.push_back(i), oset.push_back(h_idx[i]), oop.push_back(eop[i]), onull.push_back(eop[i] != 3 && arg_flag[i] == 2);
+                olo.push_back(tag_lo && eop[i] != 4 ? tag_lo[i] : 0), ohi.push_back(tag_hi && eop[i] != 4 ? tag_hi[i] : 0);
+                if (eop[i] != 3 && arg_flag[i] == 1) obytes.insert(obytes.end(), elem_bytes + elem_off[i], elem_bytes + elem_off[i + 1]);
                 ooff.push_back(obytes.size());
             }
-            const uint64_t n_r = cmd.size();
+            const uint64_t n_r = rcmd.size();
             if (obytes.empty()) obytes.push_back(0);
             ores.resize(n_r), oel.resize(n_r);
             std::vector<uint64_t> oal(n_r), orl(n_r);
             jg::orset_apply_ops_names_locked(nd.orset, n_r, oset.data(), oop.data(), ooff.data(), obytes.data(), onull.data(), olo.data(), ohi.data(),
-                                             ores.data(), oel.data(), oal.data(), orl.data());
+                                             ores.data(), oel.data(), oal.data(), orl.data(), ex != nullptr);
             std::vector<uint32_t> scmd, sset;
             std::vector<uint64_t> sal, srl;
             for (uint64_t k = 0; k < n_r; ++k) {
-                const uint32_t i = cmd[k];
-                res[i] = ores[k];
+                const uint32_t i = rcmd[k];
+                if (reads(i)) val[i] = ores[k];  // Contains' answer; a read's result stays 0
+                else res[i] = ores[k];
                 if (elem) el[i] = oel[k];
                 if (!hnone[i]) scmd.push_back(i), sset.push_back(oset[k]), sal.push_back(oal[k]), srl.push_back(orl[k]);
             }
@@ -620,14 +727,34 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
         const bool fits = total <= cap;
         if (total && fits) JG_HIP(hipMemcpyAsync(out, ship.image.p, total, hipMemcpyDeviceToHost, ctx->stream));
         stamp(3);
+        // the PN-Counter reads in front of the adds: the rows as they stood before the call, plus each read's prefix
+        // (the read list holds at most n_reads entries: that sizes the grid; a batch without a read launches and copies nothing)
+        const bool answer = ex && plan && n_reads != 0;
+        std::vector<int64_t> hval(answer ? n : 0);
+        std::vector<uint8_t> hovf(answer ? n : 0);
+        const double t_tail = jg::now_us();
+        if (answer) {
+            jg::pnc_values_at_device(nd.pnc, col, rd.rrow, n_reads, sn.pdp, sn.pdn, rd.value, rd.ovf, rd.rat, rd.rcount, JG_Q_OVERFLOW);
+            JG_HIP(hipMemcpyAsync(hval.data(), rd.value, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+            JG_HIP(hipMemcpyAsync(hovf.data(), rd.ovf, n, hipMemcpyDeviceToHost, ctx->stream));
+        }
         if (nd.pnc) jg::pnc_add_list_device(nd.pnc, o.prow, o.pamt, o.pisn, o.count, n, col);
         if (guid) JG_HIP(hipMemcpyAsync(guid, o.guid, n * sizeof(jg_guid), hipMemcpyDeviceToHost, ctx->stream));
         JG_HIP(hipStreamSynchronize(ctx->stream));
+        const double ms_tail = (jg::now_us() - t_tail) * 1e-3, t_out = jg::now_us();
         ship.bytes = total;
         ship.held = total != 0 && !fits;
         for (uint64_t i = 0; i < n; ++i)
-            if (h_status[i] == JG_U_OK && h_kind[i] == 0) res[i] = 1;
+            if (h_status[i] == JG_U_OK && h_kind[i] == 0 && !reads(i)) res[i] = 1;
         std::memcpy(status, h_status, n);
+        if (ex) {
+            for (uint64_t i = 0; i < n; ++i)
+                if (answer && reads(i) && h_status[i] == JG_Q_OK && h_kind[i] == 0) {
+                    val[i] = hval[i];
+                    if (hovf[i]) status[i] = hovf[i];
+                }
+            std::memcpy(ex->value, val.data(), n * 8);
+        }
         std::memcpy(result, res.data(), n);
         if (kind) std::memcpy(kind, h_kind, n);
         if (idx) std::memcpy(idx, h_idx, n * 4);
@@ -643,8 +770,9 @@ int update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t*
             JG_HIP(hipEventElapsedTime(&cp, ev[2], ev[3]));
             std::fprintf(stderr, "update_keys_ship(%llu commands, %llu OR-Set, %u rounds, %llu bytes): upload + resolve %.3f ms, OR-Set survivors %.3f ms, "
                          "PN-Counter plan %.3f ms, rounds on the host + dry size phase %.3f ms, applies %.3f ms, encodes %.3f ms, mover %.3f ms, "
-                         "hashes %.3f ms, copy %.3f ms\n", (ull)n, (ull)n_o, rounds, (ull)total, ms_resolve, ms_surv, ms_pnc, ms_dry, ms_apply, ms_enc,
-                         mv, hs, cp);
+                         "hashes %.3f ms, copy %.3f ms; behind them (by the host's clock) %llu reads' answers + adds + the wait for the stream %.3f ms, "
+                         "outputs %.3f ms\n", (ull)n, (ull)n_o, rounds, (ull)total, ms_resolve, ms_surv, ms_pnc, ms_dry, ms_apply, ms_enc, mv, hs, cp,
+                         (ull)n_reads, ms_tail, (jg::now_us() - t_out) * 1e-3);
             for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         }
     });
@@ -695,6 +823,16 @@ int jg_node_update_keys_ship(jg_node* node, jg_keyspace* ks, uint64_t n, const u
                              uint8_t* sha, uint32_t* n_rounds) {
     return update_keys_ship(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, col, snap, status, result, kind,
                             idx, elem, guid, snap_off, n_bytes, out, cap, sha, n_rounds);
+}
+
+int jg_node_exec_keys(jg_node* node, jg_keyspace* ks, uint64_t n, const uint64_t* key_off, const uint8_t* key_bytes, const uint8_t* cmd, const uint8_t* op,
+                      const uint8_t* arg_flag, const int64_t* amount, const uint64_t* elem_off, const uint8_t* elem_bytes, const uint64_t* tag_lo,
+                      const uint64_t* tag_hi, uint32_t col, const uint8_t* snap, uint8_t* status, uint8_t* result, int64_t* value, uint8_t* kind,
+                      uint32_t* idx, uint32_t* elem, jg_guid* guid, uint64_t* snap_off, uint64_t* n_bytes, uint8_t* out, uint64_t cap, uint8_t* sha,
+                      uint32_t* n_rounds) {
+    const Exec ex{cmd, value};
+    return update_keys_ship(node, ks, n, key_off, key_bytes, op, arg_flag, amount, elem_off, elem_bytes, tag_lo, tag_hi, col, snap, status, result, kind,
+                            idx, elem, guid, snap_off, n_bytes, out, cap, sha, n_rounds, &ex);
 }
 
 int jg_node_shipped(jg_node* node, uint64_t* n_bytes, uint8_t* out, uint64_t cap) { return node_shipped(node, n_bytes, out, cap); }

@@ -824,11 +824,17 @@ std::vector<KeyUpdate> GpuStableStore::UpdateKeysShip(GpuKeySpace& ks, const std
     return update_keys(ks, commands, &snap, &messages, true, n_rounds);
 }
 
-// All three: messages NULL = jg_node_update_keys, else jg_node_update_keys_encode (once more with room for every byte when
+std::vector<KeyUpdate> GpuStableStore::ExecKeys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
+                                                std::vector<KeyMessage>& messages, uint32_t* n_rounds) {
+    if (!snap.empty() && snap.size() != commands.size()) throw EngineError(JG_EINVAL, "ExecKeys: one snap entry per command");
+    return update_keys(ks, commands, &snap, &messages, true, n_rounds, true);
+}
+
+// All four (exec: jg_node_exec_keys, the ship call with the reads among the writes): messages NULL = jg_node_update_keys, else jg_node_update_keys_encode (once more with room for every byte when
 // the first buffer was too small: nothing was applied) or, ship, jg_node_update_keys_ship (everything is applied whatever
 // the buffer holds: a short one is followed by jg_node_shipped).
 std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>* snap,
-                                                   std::vector<KeyMessage>* messages, bool ship, uint32_t* n_rounds) {
+                                                   std::vector<KeyMessage>* messages, bool ship, uint32_t* n_rounds, bool exec) {
     const size_t n = commands.size();
     std::vector<KeyUpdate> out(n);
     if (messages) messages->assign(n, KeyMessage{});
@@ -836,8 +842,8 @@ std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::v
     flush_registrations();  // CreateSafeCRDTs not yet sent: the node's uid table
     flush_names();          // names interned here that the engine's element table has not seen
     std::vector<uint64_t> key_off(n + 1, 0), elem_off(n + 1, 0), tag_lo(n), tag_hi(n);
-    std::vector<uint8_t> key_bytes, elem_bytes, op(n), flag(n);
-    std::vector<int64_t> amount(n);
+    std::vector<uint8_t> key_bytes, elem_bytes, op(n), flag(n), cmd(exec ? n : 0);
+    std::vector<int64_t> amount(n), value(exec ? n : 0);
     for (size_t i = 0; i < n; ++i) {
         const KeyCommand& c = commands[i];
         key_bytes.insert(key_bytes.end(), c.key.begin(), c.key.end());
@@ -848,6 +854,7 @@ std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::v
         if (c.arg == 1) elem_bytes.insert(elem_bytes.end(), c.elem.begin(), c.elem.end());
         elem_off[i + 1] = elem_bytes.size();
         tag_lo[i] = c.tag.lo, tag_hi[i] = c.tag.hi;
+        if (exec) cmd[i] = c.read;
     }
     if (key_bytes.empty()) key_bytes.push_back(0);
     if (elem_bytes.empty()) elem_bytes.push_back(0);
@@ -869,10 +876,16 @@ std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::v
         if (ship) {
             uint64_t nb = 0;
             uint32_t rounds = 0;
-            check(jg_node_update_keys_ship(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(), elem_off.data(),
-                                           elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, snap->empty() ? nullptr : snap->data(), status.data(),
-                                           result.data(), kind.data(), idx.data(), elem.data(), nullptr, snap_off.data(), &nb, bytes.data(), bytes.size(),
-                                           sha.data(), &rounds));
+            if (exec)
+                check(jg_node_exec_keys(node_, ks.handle(), n, key_off.data(), key_bytes.data(), cmd.data(), op.data(), flag.data(), amount.data(),
+                                        elem_off.data(), elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, snap->empty() ? nullptr : snap->data(),
+                                        status.data(), result.data(), value.data(), kind.data(), idx.data(), elem.data(), nullptr, snap_off.data(), &nb,
+                                        bytes.data(), bytes.size(), sha.data(), &rounds));
+            else
+                check(jg_node_update_keys_ship(node_, ks.handle(), n, key_off.data(), key_bytes.data(), op.data(), flag.data(), amount.data(),
+                                               elem_off.data(), elem_bytes.data(), tag_lo.data(), tag_hi.data(), 0, snap->empty() ? nullptr : snap->data(),
+                                               status.data(), result.data(), kind.data(), idx.data(), elem.data(), nullptr, snap_off.data(), &nb,
+                                               bytes.data(), bytes.size(), sha.data(), &rounds));
             if (nb > bytes.size()) {
                 bytes.resize(nb);
                 check(jg_node_shipped(node_, &nb, bytes.data(), bytes.size()));
@@ -897,7 +910,8 @@ std::vector<KeyUpdate> GpuStableStore::update_keys(GpuKeySpace& ks, const std::v
     // nothing is left pending for jg_orset_names_sync.
     std::unordered_map<uint32_t, std::pair<uint32_t, uint32_t>> walk;  // set -> (ids issued so far, ids dead at its last Clear)
     for (size_t i = 0; i < n; ++i) {
-        out[i] = KeyUpdate{status[i], result[i], kind[i], idx[i]};
+        out[i] = KeyUpdate{status[i], result[i], kind[i], idx[i], exec ? value[i] : 0};
+        if (exec && cmd[i]) continue;  // a read touches no table
         if (status[i] != JG_U_OK || kind[i] != 1) continue;
         auto it = walk.find(idx[i]);
         if (it == walk.end()) {

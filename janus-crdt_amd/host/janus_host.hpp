@@ -164,6 +164,7 @@ struct KeyCommand {
     int64_t amount = 0;
     std::string elem;
     Guid tag;                         // ORSet.Add's Guid.NewGuid()
+    bool read = false;                // ExecKeys only: a "gp" (SafeCRDT.QueryProspective) at this point of the batch; arg 0, 1 or 2
 };
 // What SafeCRDT.Update ships for one command of UpdateKeysEncode: empty where the command ships nothing.
 struct KeyMessage {
@@ -175,6 +176,7 @@ struct KeyUpdate {
     uint8_t result = 0;       // Update's bool; 0 for a failed command
     uint8_t kind = 255;       // 0 PNCounter, 1 ORSet, 255 unresolved
     uint32_t idx = 0xFFFFFFFFu;  // the row or set the command touched
+    int64_t value = 0;        // ExecKeys: a read's answer (its status is a JG_Q_* code); 0 for a write
 };
 
 class GpuKeySpace;  // keyspace.hpp
@@ -307,6 +309,12 @@ class GpuStableStore {
     // the OR-Set rounds the call ran.  A first buffer that was short is followed by jg_node_shipped.
     std::vector<KeyUpdate> UpdateKeysShip(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
                                           std::vector<KeyMessage>& messages, uint32_t* n_rounds = nullptr);
+    // A connection's queue in one call (jg_node_exec_keys): the commands with `read` set are "gp" reads
+    // (PNCounterCommand.cs:27-41, ORSetCommand.cs:28-42) that see exactly the writes before them; everything else is
+    // UpdateKeysShip's, which the reads leave unchanged.  It flushes what UpdateKeysShip flushes and keeps the per-set
+    // tables after Clears as it does.
+    std::vector<KeyUpdate> ExecKeys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>& snap,
+                                    std::vector<KeyMessage>& messages, uint32_t* n_rounds = nullptr);
     // GetLastSynchronizedUpdate().Encode() of PN-Counter keys, encoded on the device — the payload
     // SafeCRDT.Update ships after a client op (SafeCRDT.cs:49; batch producer).
     std::vector<std::string> EncodePNCStates(const std::vector<Guid>& uids);
@@ -434,7 +442,7 @@ class GpuStableStore {
     void flush_registrations();  // pending CreateSafeCRDT registrations -> jg_node_register + jg_pnc_intern
     // UpdateKeys (messages NULL), UpdateKeysEncode and (ship) UpdateKeysShip
     std::vector<KeyUpdate> update_keys(GpuKeySpace& ks, const std::vector<KeyCommand>& commands, const std::vector<uint8_t>* snap,
-                                       std::vector<KeyMessage>* messages, bool ship = false, uint32_t* n_rounds = nullptr);
+                                       std::vector<KeyMessage>* messages, bool ship = false, uint32_t* n_rounds = nullptr, bool exec = false);
     // ApplyCommitted / ReceivedBlock: flatten the messages into the jg_commit arrays, one library call.
     std::vector<uint64_t> apply(const std::vector<const UpdateMessage*>& blocks, SafeUpdateTracker* tracker, bool block_mode);
     size_t index_blocks(const std::vector<const UpdateMessage*>& blocks);  // block_off_ + the flattened arrays' room
@@ -487,6 +495,12 @@ inline std::vector<KeyAnswer> QueryKeys(GpuKeySpace& ks, GpuStableStore& copy, c
 // "i" / "d" / "a" / "r" / "c" for a batch of key names on a copy of a node (usually the prospective store).
 inline std::vector<KeyUpdate> UpdateKeys(GpuKeySpace& ks, GpuStableStore& copy, const std::vector<KeyCommand>& commands) {
     return copy.UpdateKeys(ks, commands);
+}
+
+// A connection's queue of reads and writes by key name, in order, on a copy of a node (usually the prospective store).
+inline std::vector<KeyUpdate> ExecKeys(GpuKeySpace& ks, GpuStableStore& copy, const std::vector<KeyCommand>& commands,
+                                       const std::vector<uint8_t>& snap, std::vector<KeyMessage>& messages) {
+    return copy.ExecKeys(ks, commands, snap, messages);
 }
 
 }  // namespace janus

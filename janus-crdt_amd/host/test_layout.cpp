@@ -100,7 +100,7 @@ void test_layout() {
     M.bind(block[1]);
     CHECK((void*)a == (void*)block[1] && b == block[1] + 256);
 
-    // the default alignment is 256; a size that overflows size_t fails, and so does a 33rd array
+    // the default alignment is 256; a size that overflows size_t fails, and so does a 41st array
     uint8_t* d;
     uint64_t* big;
     jg::Layout D;

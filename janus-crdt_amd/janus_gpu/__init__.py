@@ -46,7 +46,7 @@ EXPORTS = [
     "jg_tpset_merge_json", "jg_tpset_encode_json", "jg_tpset_last_stats",
     "jg_keyspace_create", "jg_keyspace_destroy", "jg_keyspace_set", "jg_keyspace_create_keys", "jg_keyspace_receive",
     "jg_keyspace_new_keys", "jg_keyspace_lookup", "jg_node_query_keys", "jg_node_update_keys", "jg_node_update_keys_encode",
-    "jg_node_update_keys_ship", "jg_node_shipped",
+    "jg_node_update_keys_ship", "jg_node_shipped", "jg_node_exec_keys",
     "jg_node_next_idx", "jg_node_create_uids", "jg_node_adopt_keys",
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
@@ -180,6 +180,8 @@ _SIGS = {
     "jg_node_update_keys_ship": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _u64, _vp, _vp], C.c_int),
     "jg_node_shipped": ([_vp, _vp, _vp, _u64], C.c_int),
+    "jg_node_exec_keys": ([_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _u64, _vp, _vp], C.c_int),
     "jg_node_next_idx": ([_vp, C.POINTER(_u32), C.POINTER(_u32)], C.c_int),
     "jg_node_create_uids": ([_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp], C.c_int),
     "jg_node_adopt_keys": ([_vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp], C.c_int),
@@ -252,6 +254,31 @@ def pack_commands(keys, ops, args):
         if edata.size == 0:
             edata = np.zeros(1, np.uint8)  # a batch of "" alone still gives both pointers
     return koff, kdata, _arr(ops, np.uint8), flag, amount, eoff, edata
+
+
+def pack_exec(keys, cmds, ops, args):
+    """Node.exec_keys' packing: (key_off, key_bytes, cmd u8, op u8 | None, arg_flag u8, amount i64 | None, elem_off | None,
+    elem_bytes | None).  cmds[i]: 0 = write, 1 = read; ops and args as pack_commands takes them, a read's op is ignored
+    (None is allowed there and packed as 0) and its args entry is pack_queries' element.  ops may be None for a batch of
+    reads only, which then has op None."""
+    n = len(keys)
+    cmd = _arr(cmds, np.uint8)
+    if cmd.size != n or len(args) != n or (ops is not None and len(ops) != n):
+        raise ValueError("exec_keys: one cmd, one op and one args entry per key")
+    if ops is None and (cmd == 0).any():
+        raise ValueError("exec_keys: a write needs an op")
+    kdata, koff = pack_wave([_utf8(k) for k in keys])
+    is_int = [isinstance(a, (int, np.integer)) and not isinstance(a, bool) for a in args]
+    flag = np.array([0 if a is None else 2 if a is NULL_ARG else 3 if i else 1 for a, i in zip(args, is_int)], np.uint8)
+    w_int = [bool(i and not c) for i, c in zip(is_int, cmd)]
+    amount = np.array([int(a) if i else 0 for a, i in zip(args, is_int)], np.int64) if any(w_int) else None
+    eoff = edata = None
+    if (flag == 1).any():
+        edata, eoff = pack_wave([_utf8(a) if f == 1 else b"" for a, f in zip(args, flag)])
+        if edata.size == 0:
+            edata = np.zeros(1, np.uint8)
+    op = None if ops is None else np.array([0 if o is None else int(o) for o in ops], np.uint8)
+    return koff, kdata, cmd, op, flag, amount, eoff, edata
 
 
 class JanusError(RuntimeError):
@@ -1182,7 +1209,39 @@ class Node:
             self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(op), _ptr(flag), _ptr(amount), _ptr(eoff), _ptr(edata), _ptr(lo), _ptr(hi), col,
             _ptr(sn), _ptr(out["status"]), _ptr(out["result"]), _ptr(out["kind"]), _ptr(out["idx"]), _ptr(out["elem"]), _ptr(guid), _ptr(soff),
             C.addressof(nb), _ptr(buf), buf.size if cap is None else cap, _ptr(h), C.addressof(nr)))
-        total = int(nb.value)
+        return self._shipped_outputs(out, n, soff, int(nb.value), int(nr.value), buf, cap, h, guid)
+
+    def exec_keys(self, keyspace: "KeySpace", keys, cmds, ops, args, snap=None, tags=None, col: int = 0, sha: bool = False, cap=None,
+                  with_guid: bool = False):
+        """jg_node_exec_keys: a batch of reads (cmds[i] = 1, QueryProspective) and writes (cmds[i] = 0, SafeCRDT.Update) in
+        batch order: every read sees exactly the writes before it.  Packing as pack_exec; snap, tags, col, sha, cap and
+        with_guid as update_keys_ship takes them.  Returns update_keys_ship's dict plus value (i64: a read's answer, 0 for
+        every other command); a read's status is a JG_Q_* code, a write's a JG_U_* code."""
+        n = len(keys)
+        koff, kdata, cmd, op, flag, amount, eoff, edata = pack_exec(keys, cmds, ops, args)
+        lo, hi = (None, None) if tags is None else (_arr(tags[0], np.uint64), _arr(tags[1], np.uint64))
+        if lo is not None and (lo.size != n or hi.size != n):
+            raise ValueError("exec_keys: one tag per command")
+        sn = None if snap is None else _arr(snap, np.uint8)
+        if sn is not None and sn.size != n:
+            raise ValueError("exec_keys: one snap entry per command")
+        out = {"status": np.zeros(n, np.uint8), "result": np.zeros(n, np.uint8), "value": np.zeros(n, np.int64), "kind": np.zeros(n, np.uint8),
+               "idx": np.zeros(n, np.uint32), "elem": np.zeros(n, np.uint32)}
+        guid = np.zeros(n, GUID_DTYPE) if with_guid else None
+        soff = np.zeros(n + 1, np.uint64)
+        h = np.zeros((n, 32), np.uint8) if sha else None
+        nb, nr = C.c_uint64(0), C.c_uint32(0)
+        buf = np.empty(max(16, n * 512 if cap is None else cap), np.uint8)
+        _check(load().jg_node_exec_keys(
+            self._h, keyspace._h, n, _ptr(koff), _ptr(kdata), _ptr(cmd), _ptr(op), _ptr(flag), _ptr(amount), _ptr(eoff), _ptr(edata), _ptr(lo),
+            _ptr(hi), col, _ptr(sn), _ptr(out["status"]), _ptr(out["result"]), _ptr(out["value"]), _ptr(out["kind"]), _ptr(out["idx"]),
+            _ptr(out["elem"]), _ptr(guid), _ptr(soff), C.addressof(nb), _ptr(buf), buf.size if cap is None else cap, _ptr(h), C.addressof(nr)))
+        return self._shipped_outputs(out, n, soff, int(nb.value), int(nr.value), buf, cap, h, guid)
+
+    def _shipped_outputs(self, out, n, soff, total, rounds, buf, cap, h, guid):
+        """What update_keys_ship and exec_keys return behind their call: the image split into states (fetched through
+        shipped() where the generous buffer was short; None where the caller's cap was), snap_off, n_bytes, n_rounds, and
+        sha / guid where they were asked for."""
         fits = total <= (buf.size if cap is None else cap)
         if not fits and cap is None:
             buf, fits = self.shipped(), True
@@ -1191,10 +1250,10 @@ class Node:
             out["states"] = [b[int(soff[i]):int(soff[i + 1])] for i in range(n)]
         else:
             out["states"] = None
-        out["snap_off"], out["n_bytes"], out["n_rounds"] = soff, total, int(nr.value)
-        if sha:
+        out["snap_off"], out["n_bytes"], out["n_rounds"] = soff, total, rounds
+        if h is not None:
             out["sha"] = h
-        if with_guid:
+        if guid is not None:
             out["guid"] = guid
         return out
 
