@@ -285,6 +285,19 @@ int jg_orset_apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const u
  * records such a snapshot holds). */
 int jg_orset_apply_ops_ords(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
                             const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim, uint64_t* rem_lim);
+/* Where a store walks its batches of ORSet.Add / Remove / Clear (ORSet.cs:134-198) (additive entry points,
+ * JG_ABI_VERSION stays 10).  Every entry point that applies such ops (jg_orset_apply_ops, _ords, _names, the node's
+ * by-key-name calls, the producer path) turns the batch into records, ords and results by one walk in op order:
+ * mode 0 replays it on the host over the stored tag runs of every element a Remove or a read names, fetched from the
+ * device; mode 1 computes the same with sorts and prefix sums on the device, and no stored run crosses to the host;
+ * mode 2 (auto) picks by batch size.  Results, records, ords and limits are bit-identical in every mode.  A new store
+ * starts in auto, or in the mode the environment variable JANUS_ORSET_WALK = host | device | auto names (read once).
+ * Any other mode is JG_EINVAL. */
+int jg_orset_set_walk(jg_orset* s, int mode);
+/* The store's walks of ORSet.Add / Remove / Clear batches (ORSet.cs:134-198) since its creation: out[0] batches walked
+ * on the device, out[1] on the host, out[2] ops walked on the device, out[3] bytes of stored runs copied to the host
+ * by walks. */
+int jg_orset_walk_stats(jg_orset* s, uint64_t out[4]);
 /* ORSet.Contains (ORSet.cs:204-237) for (set[i], elem[i]): elem present iff its add set exists
  * and (it has no tombstone set or the two tag sets differ: !SetEquals); the null element is
  * present iff !SetEquals(nullRemove, nullAdd).  out[i] = 0/1. */

@@ -14,6 +14,11 @@
 #include "janus_gpu.h"
 #include "table_hash.hpp"
 
+namespace jgk {  // orset_union.hpp
+struct View;
+struct Drop;
+}
+
 namespace jg {
 
 // Row / set id of a message of another kind in a node wave (csrc/node.hip): the PN-Counter and OR-Set
@@ -249,8 +254,18 @@ void orset_wire_free(jg_orset_wire* w);
 void orset_wire_free_retired(jg_orset_wire* w);
 }
 
+namespace jg {
+int orset_walk_default();  // orset_walk.hip: JANUS_ORSET_WALK = host | device | auto, read once (0 | 1 | 2; unset: 2)
+}
+
 struct jg_orset {
     jg_ctx* ctx;
+    // the record walk of Add / Remove / Clear batches (jg_orset_set_walk): 0 on the host (orset.hip
+    // apply_ops), 1 on the device (orset_walk.hip), 2 auto; walk_stats: batches walked on the device, on the host, ops
+    // walked on the device, bytes of stored runs copied to the host by walks; walk_ws*: the device walk's blocks
+    int walk_mode = jg::orset_walk_default();
+    uint64_t walk_stats[4] = {0, 0, 0, 0};
+    jg::DevBuf walk_ws, walk_ws2, walk_ws3, walk_tmp;
     jg_stream_soa add, rem;
     jg_stream_soa spare_add, spare_rem;  // union target for in-place merges (swapped in)
     jg::DevBuf counts;     // device-side uint64 [2]: n_add, n_rem written by the union kernel
@@ -369,6 +384,17 @@ struct OrsetEncPlan {
 bool orset_encode_size_locked(jg_orset* s, uint64_t n, const uint32_t* set, const uint64_t* add_lim, const uint64_t* rem_lim, uint64_t* h_off);
 void orset_encode_write_locked(jg_orset* s, uint8_t* d_out);
 void orset_settle_pending(jg_orset* s, size_t at);
+// The record walk on the device (orset_walk.hip): apply_ops()' contract over the same host arrays, the store's counts
+// current.  In auto mode a batch goes there from kWalkAutoMinOps ops on: the smallest measured size at which it is not
+// slower than the host walk (host/bench_walk.cpp, DESIGN.md §18: 0.33 / 0.34 ms against 0.09 / 0.10 ms at 1 / 64 ops —
+// some forty launches and two waits whatever the size — 0.45 against 0.56 ms at 4096, 1.4 against 7.3 ms at 200,000).
+constexpr uint64_t kWalkAutoMinOps = 4096;
+void orset_walk_device(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
+                       const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim, uint64_t* rem_lim);
+// orset.hip, for the device walk: a stream's read view, and s = (s minus the sets flagged in `drop`) ∪ batch, synchronous;
+// *base_a / *base_r = the store's next ords the batch's records were appended at (read after any renumbering).
+jgk::View orset_view(const jg_stream_soa& s);
+void orset_walk_union(jg_orset* s, jg_orset* batch, jgk::Drop drop, uint64_t* base_a, uint64_t* base_r);
 // orset.hip: room in the store's union targets for that many more records (no sync; skipped while counts are pending).
 void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in);
 // orset.hip, for orset_names.hip: jg_orset_contains' kernel over n device queries (set << 32 | id); jg_orset_lookup_all's

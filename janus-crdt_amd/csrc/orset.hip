@@ -137,17 +137,9 @@ __global__ __launch_bounds__(kOB) void k_pack(View v, const uint32_t* __restrict
     }
 }
 
-__device__ __forceinline__ unsigned long long key_at(const View& v, uint64_t r) { return v.key[jgk::slot_of(v, r)]; }
-__device__ __forceinline__ uint64_t lower_key(const View& v, unsigned long long q) {
-    uint64_t lo = 0, hi = v.n;
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (key_at(v, m) < q) lo = m + 1; else hi = m; }
-    return lo;
-}
-__device__ __forceinline__ uint64_t upper_key(const View& v, unsigned long long q) {
-    uint64_t lo = 0, hi = v.n;
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (key_at(v, m) <= q) lo = m + 1; else hi = m; }
-    return lo;
-}
+using jgk::key_at;
+using jgk::lower_key;
+using jgk::upper_key;
 
 // at / count / out64 serve the reads by key name (query.hip): answer i goes to slot at[i] (NULL: i) of out64 (NULL:
 // of out), and only the first *count queries of the list are answered (NULL: all nq; the launch before appended them).
@@ -558,6 +550,7 @@ Runs fetch_runs(jg_orset* s, const std::vector<unsigned long long>& keys) {
     JG_HIP(hipStreamSynchronize(ctx->stream));
     gather_stream(ctx, s->add, bounds, 0, n, r.add, r.add_off);
     gather_stream(ctx, s->rem, bounds, 1, n, r.rem, r.rem_off);
+    s->walk_stats[3] += (r.add.size() + r.rem.size()) * sizeof(jg_tagrec);
     return r;
 }
 
@@ -591,6 +584,12 @@ void load_group(const jg_tagrec* b, const jg_tagrec* e, std::vector<TagKey>& ord
 // entry points refuse it): Contains at that point of the batch, answered in result[i].
 void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
                const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim = nullptr, uint64_t* rem_lim = nullptr) {
+    // the walk on the device (orset_walk.hip) unless the store is pinned to this one (jg_orset_set_walk)
+    if (s->walk_mode == 1 || (s->walk_mode == 2 && n_ops >= jg::kWalkAutoMinOps)) {
+        jg::orset_walk_device(s, n_ops, set, elem, op, tag_lo, tag_hi, result, add_lim, rem_lim);
+        return;
+    }
+    s->walk_stats[1] += 1;
     static const bool tr = std::getenv("JANUS_TRACE_APPLY") != nullptr;
     const auto now = [] { return jg::now_us() * 1e-3; };  // this trace line is in ms
     double tp[6] = {tr ? now() : 0};
@@ -1007,6 +1006,15 @@ void orset_merge_runs(jg_orset* s, uint32_t n_runs, const uint64_t* add_counts, 
 }
 
 void orset_merge_store(jg_orset* s, jg_orset* src, bool defer) { merge_into(s, src, defer); }
+
+jgk::View orset_view(const jg_stream_soa& s) { return view(s); }
+
+void orset_walk_union(jg_orset* s, jg_orset* batch, jgk::Drop drop, uint64_t* base_a, uint64_t* base_r) {
+    ensure_ord_room(s->ctx, s->add, batch->add);
+    ensure_ord_room(s->ctx, s->rem, batch->rem);
+    *base_a = s->add.next, *base_r = s->rem.next;
+    merge_into(s, batch, false, drop);
+}
 
 bool orset_pin_pending(jg_orset* s, size_t at) {
     if (!s->counts_pending) return false;

@@ -51,6 +51,7 @@ EXPORTS = [
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
     "jg_rows_set_narrow", "jg_rows_form",
+    "jg_orset_set_walk", "jg_orset_walk_stats",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -189,6 +190,8 @@ _SIGS = {
     "jg_pnc_reserve": ([_vp, _u64, _u32], C.c_int),
     "jg_pnc_set_max_replicas": ([_vp, _u32], C.c_int),
     "jg_pnc_set_dense_filter": ([_vp, C.c_int], C.c_int),
+    "jg_orset_set_walk": ([_vp, C.c_int], C.c_int),
+    "jg_orset_walk_stats": ([_vp, _vp], C.c_int),
     "jg_pnc_dense_filter_state": ([_vp, C.POINTER(C.c_int)], C.c_int),
     "jg_rows_set_narrow": ([_vp, C.c_int], C.c_int),
     "jg_rows_form": ([_vp, C.POINTER(C.c_int)], C.c_int),
@@ -757,6 +760,18 @@ class ORSetStore:
         _check(load().jg_orset_union(a._h, b._h, out._h, 1 if async_ else 0))
 
     ADD, REMOVE, CLEAR = 1, 2, 3
+    WALK_HOST, WALK_DEVICE, WALK_AUTO = 0, 1, 2
+
+    def set_walk(self, mode: int) -> None:
+        """Where the store walks its Add / Remove / Clear batches (jg_orset_set_walk): WALK_HOST, WALK_DEVICE or WALK_AUTO."""
+        _check(load().jg_orset_set_walk(self._h, int(mode)))
+
+    def walk_stats(self) -> dict:
+        """jg_orset_walk_stats: batches walked on the device and on the host, ops walked on the device, bytes of stored runs
+        copied to the host by walks, since the store's creation."""
+        out = np.zeros(4, np.uint64)
+        _check(load().jg_orset_walk_stats(self._h, _ptr(out)))
+        return {"device_batches": int(out[0]), "host_batches": int(out[1]), "device_ops": int(out[2]), "run_bytes": int(out[3])}
 
     def apply_ops(self, set_ids, elems, ops, tag_lo, tag_hi) -> np.ndarray:
         """ORSet.Add/Remove/Clear in order (jg_orset_apply_ops); returns each op's bool result."""
