@@ -298,6 +298,23 @@ int jg_orset_set_walk(jg_orset* s, int mode);
  * on the device, out[1] on the host, out[2] ops walked on the device, out[3] bytes of stored runs copied to the host
  * by walks. */
 int jg_orset_walk_stats(jg_orset* s, uint64_t out[4]);
+/* Whether the device walk of an ORSet.Add / Remove / Clear batch (ORSet.cs:134-198) may take its one-launch form
+ * (additive entry points, JG_ABI_VERSION stays 10): one kernel launch by one workgroup computes what the multi-launch
+ * device walk computes, for a batch of at most out[4] ops of jg_orset_walk_small_stats whose Removes and reads name
+ * at most out[5] stored add tags; a batch over that second budget is walked by the multi-launch form instead, never
+ * on the host.  Mode 0 is off, 1 on, 2 auto.  Under jg_orset_set_walk mode 0 the switch is ignored; under mode 1 a
+ * fitting batch takes the one-launch form iff the switch is on; under mode 2 a batch below the multi-launch form's
+ * threshold takes it if the switch is on and the batch fits, or if the switch is auto and the batch's size is in the
+ * measured range where the form is not slower than the host walk (from 256 ops up to the cap), and is walked on the
+ * host otherwise.  Results, records, ords and limits are bit-identical in every form.  A new store
+ * starts in auto, or in the mode the environment variable JANUS_ORSET_WALK_SMALL = off | on | auto names (read
+ * once).  Any other mode is JG_EINVAL and changes nothing. */
+int jg_orset_set_walk_small(jg_orset* s, int mode);
+/* The store's one-launch walks of ORSet.Add / Remove / Clear batches (ORSet.cs:134-198) since its creation: out[0]
+ * batches walked in one launch, out[1] their ops, out[2] batches that fit the op cap, exceeded the stored-tag budget
+ * and went to the multi-launch walk, out[3] reserved (0), out[4] the op cap, out[5] the stored-tag budget.  A
+ * one-launch batch is a device walk: it also counts in jg_orset_walk_stats out[0] and out[2]. */
+int jg_orset_walk_small_stats(jg_orset* s, uint64_t out[6]);
 /* ORSet.Contains (ORSet.cs:204-237) for (set[i], elem[i]): elem present iff its add set exists
  * and (it has no tombstone set or the two tag sets differ: !SetEquals); the null element is
  * present iff !SetEquals(nullRemove, nullAdd).  out[i] = 0/1. */

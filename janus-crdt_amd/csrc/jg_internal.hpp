@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "janus_gpu.h"
+#include "orset_walk_small.hpp"
 #include "table_hash.hpp"
 
 namespace jgk {  // orset_union.hpp
@@ -256,6 +257,8 @@ void orset_wire_free_retired(jg_orset_wire* w);
 
 namespace jg {
 int orset_walk_default();  // orset_walk.hip: JANUS_ORSET_WALK = host | device | auto, read once (0 | 1 | 2; unset: 2)
+int orset_walk_small_default();  // orset_walk_small.hip: JANUS_ORSET_WALK_SMALL = off | on | auto, read once (0 | 1 | 2; unset: 2)
+void orset_walk_small_free(jg_orset* batch);
 }
 
 struct jg_orset {
@@ -266,6 +269,14 @@ struct jg_orset {
     int walk_mode = jg::orset_walk_default();
     uint64_t walk_stats[4] = {0, 0, 0, 0};
     jg::DevBuf walk_ws, walk_ws2, walk_ws3, walk_tmp;
+    // the one-launch form of the device walk for small batches (jg_orset_set_walk_small): 0 off, 1 on, 2
+    // auto; walk_small_stats: batches walked in one launch, their ops, batches over the stored-tag budget that went to the
+    // multi-launch form; walk_small_ws: its fixed scratch, walk_small_batch: its two record streams at their caps (both
+    // allocated at the first such batch), walk_small_drop: a Clear drop bitmap of at most 1 MiB
+    int walk_small_mode = jg::orset_walk_small_default();
+    uint64_t walk_small_stats[3] = {0, 0, 0};
+    jg::DevBuf walk_small_ws, walk_small_drop;
+    jg_orset* walk_small_batch = nullptr;
     jg_stream_soa add, rem;
     jg_stream_soa spare_add, spare_rem;  // union target for in-place merges (swapped in)
     jg::DevBuf counts;     // device-side uint64 [2]: n_add, n_rem written by the union kernel
@@ -275,7 +286,10 @@ struct jg_orset {
     jg_orset() = default;
     jg_orset(const jg_orset&) = delete;
     jg_orset& operator=(const jg_orset&) = delete;
-    ~jg_orset() { jg::orset_wire_free(wire); }
+    ~jg_orset() {
+        jg::orset_wire_free(wire);
+        jg::orset_walk_small_free(walk_small_batch);
+    }
 };
 
 namespace jg {
@@ -394,6 +408,19 @@ void orset_walk_device(jg_orset* s, uint64_t n_ops, const uint32_t* set, const u
 // orset.hip, for the device walk: a stream's read view, and s = (s minus the sets flagged in `drop`) ∪ batch, synchronous;
 // *base_a / *base_r = the store's next ords the batch's records were appended at (read after any renumbering).
 jgk::View orset_view(const jg_stream_soa& s);
+// The same walk in one launch of one workgroup (orset_walk_small.hip) for a batch of at most
+// kWalkSmallMaxOps ops whose Removes and reads name at most kWalkSmallMaxStored stored add tags.  false: the batch
+// needs more stored tags than that; nothing has been written and the caller runs orset_walk_device.  In auto mode
+// (jg_orset_set_walk 2 with jg_orset_set_walk_small 2) a batch below kWalkAutoMinOps goes there from
+// kWalkSmallAutoMinOps ops on: the smallest measured size from which it is not slower than the host walk beyond the
+// A/A spread at every larger measured size up to the cap (host/bench_walk.cpp).
+constexpr uint64_t kWalkSmallMaxOps = jgs::kMaxOps, kWalkSmallMaxStored = jgs::kMaxStored;
+// Measured: 0.14-0.15 ms against the host walk's 0.09-0.10 ms at 1 op and 0.11-0.12 ms at 64 ops (missed), 0.14-0.15
+// against 0.15-0.16 ms at 256 ops and 0.16 against 0.25 ms at 1024 ops on ORSetWorkload (met; the Add/Remove mix is
+// met from 64 ops on).
+constexpr uint64_t kWalkSmallAutoMinOps = 256;
+bool orset_walk_small(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
+                      const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim, uint64_t* rem_lim);
 void orset_walk_union(jg_orset* s, jg_orset* batch, jgk::Drop drop, uint64_t* base_a, uint64_t* base_r);
 // orset.hip: room in the store's union targets for that many more records (no sync; skipped while counts are pending).
 void orset_reserve_union(jg_orset* s, uint64_t add_in, uint64_t rem_in);

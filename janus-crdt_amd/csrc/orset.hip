@@ -585,7 +585,16 @@ void load_group(const jg_tagrec* b, const jg_tagrec* e, std::vector<TagKey>& ord
 void apply_ops(jg_orset* s, uint64_t n_ops, const uint32_t* set, const uint32_t* elem, const uint8_t* op, const uint64_t* tag_lo,
                const uint64_t* tag_hi, uint8_t* result, uint64_t* add_lim = nullptr, uint64_t* rem_lim = nullptr) {
     // the walk on the device (orset_walk.hip) unless the store is pinned to this one (jg_orset_set_walk)
-    if (s->walk_mode == 1 || (s->walk_mode == 2 && n_ops >= jg::kWalkAutoMinOps)) {
+    // a batch that fits one workgroup takes the one-launch form of that walk where the store's second switch says so
+    // (jg_orset_set_walk_small, orset_walk_small.hip); over its stored-tag budget it goes on to the multi-launch form
+    bool device = s->walk_mode == 1 || (s->walk_mode == 2 && n_ops >= jg::kWalkAutoMinOps), small = false;
+    if (n_ops >= 1 && n_ops <= jg::kWalkSmallMaxOps) {
+        if (s->walk_mode == 1) small = s->walk_small_mode == 1;
+        else if (s->walk_mode == 2 && !device)
+            small = s->walk_small_mode == 1 || (s->walk_small_mode == 2 && n_ops >= jg::kWalkSmallAutoMinOps);
+    }
+    if (small && jg::orset_walk_small(s, n_ops, set, elem, op, tag_lo, tag_hi, result, add_lim, rem_lim)) return;
+    if (device || small) {
         jg::orset_walk_device(s, n_ops, set, elem, op, tag_lo, tag_hi, result, add_lim, rem_lim);
         return;
     }

@@ -17,8 +17,7 @@
 #include <cstring>
 
 #include "launch.hpp"
-#include "orset_view.hpp"
-#include "orset_walk.hpp"
+#include "orset_walk_types.hpp"
 
 namespace {
 
@@ -30,66 +29,16 @@ using jgk::ld_tag;
 
 #define JGW_EACH(i, n) for (uint64_t i = (uint64_t)blockIdx.x * kWB + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * kWB)
 
-// One Add (cls 0) or other op (cls 1) for the tag sort: by (cls, key, epoch, tag, op index).
-struct TagRec {
-    unsigned long long key, lo, hi;
-    uint32_t epoch_cls;  // cls << 31 | epoch
-    uint32_t idx;
-};
-struct TagLess {
-    __host__ __device__ bool operator()(const TagRec& a, const TagRec& b) const {
-        const uint32_t ca = a.epoch_cls >> 31, cb = b.epoch_cls >> 31;
-        if (ca != cb) return ca < cb;
-        if (a.key != b.key) return a.key < b.key;
-        if (a.epoch_cls != b.epoch_cls) return a.epoch_cls < b.epoch_cls;
-        if (a.lo != b.lo) return a.lo < b.lo;
-        if (a.hi != b.hi) return a.hi < b.hi;
-        return a.idx < b.idx;
-    }
-};
-// One stored add tag of a key the batch Removes or reads: seg = the key's first position in P2, or kNone when the tag has
-// a tombstone (not in U0); by (seg, ord, tag).
-struct Item {
-    uint32_t seg, ord;
-    unsigned long long lo, hi;
-};
-struct ItemLess {
-    __host__ __device__ bool operator()(const Item& a, const Item& b) const {
-        if (a.seg != b.seg) return a.seg < b.seg;
-        if (a.ord != b.ord) return a.ord < b.ord;
-        if (a.lo != b.lo) return a.lo < b.lo;
-        return a.hi < b.hi;
-    }
-};
-// One tombstone of the batch; by (key, tag).
-struct Tomb {
-    unsigned long long key, lo, hi;
-    uint32_t ord, pad;
-};
-struct TombLess {
-    __host__ __device__ bool operator()(const Tomb& a, const Tomb& b) const {
-        if (a.key != b.key) return a.key < b.key;
-        if (a.lo != b.lo) return a.lo < b.lo;
-        return a.hi < b.hi;
-    }
-};
+using jgw::Item;
+using jgw::ItemLess;
+using jgw::TagLess;
+using jgw::TagRec;
+using jgw::Tomb;
+using jgw::TombLess;
+using jgw::has_tag;
 
 // The counters (uint64 each, zeroed per call).
 enum : int { cNextA = 1, cNextR, cKeptA, cKeptR, cCleared, cMaxCleared, cSpanA, cSpanR, cCursor, cErr, cCount = 16 };
-
-// Whether tag t is in ranks [lo, end) of v (sorted by tag inside one key's run).
-__device__ __forceinline__ bool has_tag(const View& v, uint64_t lo, uint64_t end, unsigned long long tlo, unsigned long long thi) {
-    uint64_t hi = end;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        const Tag g = ld_tag(v.tag + jgk::slot_of(v, mid));
-        if (g.lo < tlo || (g.lo == tlo && g.hi < thi)) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= end) return false;
-    const Tag g = ld_tag(v.tag + jgk::slot_of(v, lo));
-    return g.lo == tlo && g.hi == thi;
-}
 
 __global__ __launch_bounds__(kWB) void k_prep(const uint32_t* __restrict__ set, const uint32_t* __restrict__ elem, uint64_t n,
                                               unsigned long long* __restrict__ key, uint32_t* __restrict__ idx) {
@@ -201,16 +150,8 @@ __global__ __launch_bounds__(kWB) void k_items(View a, View r, const unsigned lo
     }
 }
 
-// What a position's segment starts from: the stored runs in epoch 0 of a key a Remove or a read names, else nothing.
 __device__ __forceinline__ jgw::Base base_of(uint32_t ks, bool store, const unsigned long long* __restrict__ bnd, const uint32_t* __restrict__ u0n) {
-    jgw::Base b{0, 0, 0, 0};
-    if (store) {
-        b.nA0 = bnd[4 * (uint64_t)ks + 1] - bnd[4 * (uint64_t)ks];
-        b.nR0 = bnd[4 * (uint64_t)ks + 3] - bnd[4 * (uint64_t)ks + 2];
-        b.u0 = u0n[ks];
-        b.m0 = b.nR0 - (b.nA0 - b.u0);  // |R0| - |A0 ∩ R0|
-    }
-    return b;
+    return jgw::base_of(ks, store, bnd, store ? u0n[ks] : 0u);
 }
 
 // Per position of P2: the Add's flags (1 issues, 2 fills, 4 u-add as the state the Removes and reads see has it; issue_w:

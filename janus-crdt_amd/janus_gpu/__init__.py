@@ -51,7 +51,7 @@ EXPORTS = [
     "jg_pnc_shape", "jg_pnc_reserve", "jg_pnc_set_max_replicas",
     "jg_pnc_set_dense_filter", "jg_pnc_dense_filter_state",
     "jg_rows_set_narrow", "jg_rows_form",
-    "jg_orset_set_walk", "jg_orset_walk_stats",
+    "jg_orset_set_walk", "jg_orset_walk_stats", "jg_orset_set_walk_small", "jg_orset_walk_small_stats",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -192,6 +192,8 @@ _SIGS = {
     "jg_pnc_set_dense_filter": ([_vp, C.c_int], C.c_int),
     "jg_orset_set_walk": ([_vp, C.c_int], C.c_int),
     "jg_orset_walk_stats": ([_vp, _vp], C.c_int),
+    "jg_orset_set_walk_small": ([_vp, C.c_int], C.c_int),
+    "jg_orset_walk_small_stats": ([_vp, _vp], C.c_int),
     "jg_pnc_dense_filter_state": ([_vp, C.POINTER(C.c_int)], C.c_int),
     "jg_rows_set_narrow": ([_vp, C.c_int], C.c_int),
     "jg_rows_form": ([_vp, C.POINTER(C.c_int)], C.c_int),
@@ -772,6 +774,20 @@ class ORSetStore:
         out = np.zeros(4, np.uint64)
         _check(load().jg_orset_walk_stats(self._h, _ptr(out)))
         return {"device_batches": int(out[0]), "host_batches": int(out[1]), "device_ops": int(out[2]), "run_bytes": int(out[3])}
+
+    WALK_SMALL_OFF, WALK_SMALL_ON, WALK_SMALL_AUTO = 0, 1, 2
+
+    def set_walk_small(self, mode: int) -> None:
+        """Whether the device walk of a batch that fits one workgroup takes its one-launch form (jg_orset_set_walk_small):
+        WALK_SMALL_OFF, WALK_SMALL_ON or WALK_SMALL_AUTO."""
+        _check(load().jg_orset_set_walk_small(self._h, int(mode)))
+
+    def walk_small_stats(self) -> dict:
+        """jg_orset_walk_small_stats: batches walked in one launch and their ops, batches over the stored-tag budget that
+        went to the multi-launch walk, and the two caps."""
+        out = np.zeros(6, np.uint64)
+        _check(load().jg_orset_walk_small_stats(self._h, _ptr(out)))
+        return {"batches": int(out[0]), "ops": int(out[1]), "over_budget": int(out[2]), "max_ops": int(out[4]), "max_stored": int(out[5])}
 
     def apply_ops(self, set_ids, elems, ops, tag_lo, tag_hi) -> np.ndarray:
         """ORSet.Add/Remove/Clear in order (jg_orset_apply_ops); returns each op's bool result."""
